@@ -15,10 +15,16 @@ trajectory (weak scaling, value = all images' steps / max-over-ranks time).
 
 A "step" = one StableDiffusion.__call__ of the reference (variants/sd.py:56-59): CFG duplicate, one UNet forward
 at batch 2, CFG combine + DDIM update, replayed as one HIP graph.  Inputs are resident in HBM before timing.
-Extra objects on the JSON line: "roofline" (the implicit-GEMM conv/linear kernel family, timed per launch with
-HIP events on its own stream in an instrumented eager pass), "cpu_baseline" (the CPU oracle = the torch-CPU op
-path the reference's tests compare against, timed on this box's host cores; rank 0, N=1 only) and "e2e" (BASELINE config 3:
-CLIP text encoder x2 -> 50 graph-replayed steps -> VAE decode, img/s with the three segment times; N=1 only).
+
+A plain run sets up, warms up, times the --steps steps and prints the line.  ``--full`` adds the legs that take runs of
+their own (each still switched off by its --no-* option): "roofline" (the implicit-GEMM conv/linear kernel family, timed
+per launch with HIP events on its own stream in an instrumented eager pass), "cpu_baseline" (the CPU oracle = the torch-CPU
+op path the reference's tests compare against, timed on this box's host cores; rank 0, N=1 only), "e2e" (BASELINE config 3:
+CLIP text encoder x2 -> 50 graph-replayed steps -> VAE decode, img/s with the three segment times; N=1 only) and
+"config5" (4 images, 96x96 latents, fp16 and fp8; N=1 only).
+
+``--dump-outputs DIR`` writes what the timed steps computed -- the latent after the last timed step, fp32 (B,4,H,W) --
+as DIR/latent.npy (DIR/latent_rank<r>.npy per rank when N > 1).  Inputs are seeded: the same arguments give the same inputs.
 
 ``--dry-run`` rehearses the N>1 plumbing on CPU (gloo): arena broadcast + image shard + max-over-ranks, no kernels.
 """
@@ -48,6 +54,8 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true", help="also run the roofline, e2e, config5 and cpu_baseline legs (off by default: a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the latent after the last timed step to DIR/latent.npy (fp32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-e2e", action="store_true", help="skip the config-3 end-to-end leg (CLIP x2 -> 50 steps -> VAE decode)")
@@ -134,6 +142,21 @@ def launch_ranks(args, argv):
         return 1
     print(line, flush=True)
     return 0
+
+
+DUMP_BYTES = 64 << 20          # --dump-outputs: all files of one run together, every rank included
+
+
+def dump_outputs(d, arrays, share=1):
+    """--dump-outputs: each array as d/<name>.npy in fp32.  One larger than its share of DUMP_BYTES is replaced by a fixed, seeded sample
+    of its elements (flattened, indices ascending), the same from run to run, so that two builds still compare output for output."""
+    os.makedirs(d, exist_ok=True)
+    cap = DUMP_BYTES // 4 // (share * len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.size > cap:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def csrc_hash():
@@ -621,10 +644,12 @@ def main(argv=None):
                "note": "max over ranks; wall clock of each rank from interpreter entry of main() to the captured step graph (imports + device init, weight arena synthesis / broadcast, eager warm-up + capture)"}
     final = lat.numpy()
     assert np.isfinite(final).all(), "non-finite latent after the timed steps"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"latent" if world == 1 else f"latent_rank{rank}": final}, share=world)
 
     peak = PEAK_MFMA_TFLOPS[args.dtype]
     roofline = None
-    if not args.no_roofline and rank == 0:
+    if args.full and not args.no_roofline and rank == 0:
         roofline = roofline_leg(sd, run, max(1, min(args.steps, 5)), peak, (B, S, args.dtype) == (1, 64, "fp16"))
 
     if rank == 0:
@@ -649,11 +674,11 @@ def main(argv=None):
             "startup": startup,
             "roofline": roofline,
         }
-        if world == 1 and (B, S, args.dtype) == (1, 64, "fp16") and not args.no_e2e:
+        if args.full and world == 1 and (B, S, args.dtype) == (1, 64, "fp16") and not args.no_e2e:
             out["e2e"] = e2e_leg(sd, args.e2e_images, seed)
-        if world == 1 and (B, S, args.dtype) == (1, 64, "fp16") and not args.no_config5:
+        if args.full and world == 1 and (B, S, args.dtype) == (1, 64, "fp16") and not args.no_config5:
             out["config5"] = config5_leg(wstate, args.config5_steps, seed)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_steps)
         print(json.dumps(out), flush=True)
     if use_dist:

@@ -6,6 +6,9 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -106,3 +109,50 @@ def test_launcher_refuses_more_ranks_than_visible_gpus():
         r = _run(["--gpus", str(have + 1), "--steps", "1", "--warmup", "0"])
         assert r.returncode == 2 and f"only {have} GPU" in r.stderr
         assert not [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
+
+
+def test_full_is_off_by_default():
+    """A plain run times the steps only: roofline, e2e, config5 and cpu_baseline run with --full, where each --no-* option still drops its leg
+    (the GPU side: test_plain_run_line_and_dumped_latent)."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs == "" and a.steps == 7 and a.warmup == 2
+    a = bench.parse(["--full", "--no-e2e", "--dump-outputs", "d"])
+    assert a.full is True and a.no_e2e is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_fp32_and_samples_within_the_budget(tmp_path, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    small = np.arange(24, dtype=np.float64).reshape(2, 3, 4)
+    bench.dump_outputs(str(tmp_path / "a"), {"latent": small})
+    got = np.load(tmp_path / "a" / "latent.npy")
+    assert got.dtype == np.float32 and got.shape == small.shape and np.array_equal(got, small)
+    # larger than its share of the budget: a fixed, seeded sample of the flattened elements, the same on every call
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4 * 100)
+    big = np.random.default_rng(1).standard_normal((4, 4, 16, 16)).astype(np.float32)
+    bench.dump_outputs(str(tmp_path / "b"), {"x": big}, share=2)
+    bench.dump_outputs(str(tmp_path / "c"), {"x": big}, share=2)
+    b, c = np.load(tmp_path / "b" / "x.npy"), np.load(tmp_path / "c" / "x.npy")
+    assert b.shape == (50,) and np.array_equal(b, c) and np.isin(b, big).all()
+
+
+@pytest.mark.gpu
+def test_plain_run_line_and_dumped_latent(tmp_path):
+    """`bench.py --gpus 1` as the driver runs it: the headline fields and none of the --full legs; --dump-outputs writes the latent after the
+    last timed step, and a second run with the same arguments (same seeded inputs) writes the same latent."""
+    outs = []
+    for d in ("r1", "r2"):
+        r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / d)], timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        assert out["metric"] == "unet_denoise_steps_per_sec" and out["unit"] == "steps/s" and out["higher_is_better"] is True and out["dtype"] == "f16"
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+        assert out["roofline"] is None and not {"e2e", "config5", "cpu_baseline"} & set(out)
+        lat = np.load(tmp_path / d / "latent.npy")
+        assert lat.dtype == np.float32 and lat.shape == (1, 4, 64, 64) and np.isfinite(lat).all()
+        outs.append(lat)
+    np.testing.assert_array_equal(outs[0], outs[1])

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 pass() {   # name, counters...
   n=$1; shift
   rm -rf $O/prof_$n
-  timeout -k 10 200 rocprofv3 --kernel-trace --pmc "$@" -d $O/prof_$n --output-format csv -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-roofline --no-e2e > $O/prof_$n.log 2>&1
+  timeout -k 10 200 rocprofv3 --kernel-trace --pmc "$@" -d $O/prof_$n --output-format csv -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-roofline --no-e2e > $O/prof_$n.log 2>&1
   python3 $R/tools/pmc_sq_summary.py $O/prof_$n $O/pmc_mem_$n.json > /dev/null
   rm -rf $O/prof_$n
   echo "pass $n done"

@@ -25,7 +25,7 @@ if len(sys.argv) > 3:
     ns = sum(float(r["TotalDurationNs"]) for r in fam)
     rcalls = sum(int(r["Calls"]) for r in red)
     rns = sum(float(r["TotalDurationNs"]) for r in red)
-    json.dump({"csrc_sha16": csrc_hash(), "command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-config5",
+    json.dump({"csrc_sha16": csrc_hash(), "command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-config5",
                "k_igemm": {"launches_per_step": calls / steps, "ms_per_step": ns / 1e6 / steps, "avg_launch_us": ns / 1e3 / max(1, calls)},
                "k_splitk_reduce": {"launches_per_step": rcalls / steps, "ms_per_step": rns / 1e6 / steps, "avg_launch_us": rns / 1e3 / max(1, rcalls)},
                "k_igemm_plus_reduce": {"launches_per_step": (calls + rcalls) / steps, "ms_per_step": (ns + rns) / 1e6 / steps,

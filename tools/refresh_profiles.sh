@@ -8,9 +8,9 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py > $O/bench_n1.json 2> $O/bench_n1.err
+python3 $R/bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
 rm -rf $O/prof_stats $O/prof_fetch $O/prof_write $O/prof_sq
-rocprofv3 --kernel-trace --stats -d $O/prof_stats --output-format csv -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-config5 > $O/prof_stats.log 2>&1
+rocprofv3 --kernel-trace --stats -d $O/prof_stats --output-format csv -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-config5 > $O/prof_stats.log 2>&1
 python3 $R/tools/prof_summary.py $O/prof_stats 32 $O/kernel_family.json > $O/kernel_stats_per_step.txt      # steps executed: 2 in compile() + 5 warm-up + 20 timed + 5 instrumented
 cp $(ls $O/prof_stats/*/*kernel_stats.csv $O/prof_stats/*kernel_stats.csv 2>/dev/null | head -1) $O/kernel_stats.csv
 python3 $R/tools/step_profile.py $O/gemm_shapes.csv > $O/gemm_shapes.txt
@@ -32,7 +32,7 @@ for i in 1 2; do
 done
 # BASELINE config 5's per-GPU shape (4 images, 96 x 96 latents), fp16 and fp8: bench line, per-shape GEMM table, rocprofv3 kernel statistics
 for dt in fp16 fp8; do
-  python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-e2e --no-config5 --images 4 --latent 96 --dtype $dt > $O/bench_images4_latent96_$dt.json 2>/dev/null
+  python3 $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-e2e --no-config5 --images 4 --latent 96 --dtype $dt > $O/bench_images4_latent96_$dt.json 2>/dev/null
   python3 $R/tools/step_profile.py $O/gemm_shapes_images4_latent96_$dt.csv 4 96 $dt > $O/gemm_shapes_images4_latent96_$dt.txt 2>/dev/null
   rm -rf $O/prof_stats5
   rocprofv3 --kernel-trace --stats -d $O/prof_stats5 --output-format csv -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-roofline --no-e2e --no-config5 --images 4 --latent 96 --dtype $dt > $O/prof_stats5.log 2>&1
