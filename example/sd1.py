@@ -8,6 +8,7 @@ tokenizes a real prompt (tokenizer/clip.py).
 BASELINE config 3: full 50-step sampler, batch 1, end-to-end img/s.
 
     python -m example.sd1 --steps 50 [--ckpt sd-v1-4.ckpt] [--out rendered.npy]
+    python -m example.sd1 --steps 20 --sampler dpmpp2m          # DPM-Solver++(2M); also ddim, ddim-eta, euler-a (--eta)
 """
 import argparse
 import os
@@ -28,6 +29,9 @@ if __name__ == "__main__":
     ap.add_argument("--ckpt", default="", help="LDM checkpoint (.ckpt torch zip or .safetensors); default: synthetic weights")
     ap.add_argument("--vocab", default="", help="local bpe_simple_vocab_16e6.txt.gz for the prompt; default: seeded token ids")
     ap.add_argument("--prompt", default="a horse sized cat eating a bagel")
+    ap.add_argument("--sampler", choices=["ddim", "ddim-eta", "dpmpp2m", "euler-a"], default=None,
+                    help="run a sampler schedule (variants/samplers.py) with device-side noise from --seed; default: the reference's DDIM loop")
+    ap.add_argument("--eta", type=float, default=None, help="noise scale of ddim-eta (default 1) and euler-a (default 1)")
     args = ap.parse_args()
 
     import tinyfusers_amd.storage.tensor as T
@@ -70,13 +74,25 @@ if __name__ == "__main__":
     alphas = model.alphas_cumprod[timesteps]
     alphas_prev = np.concatenate((np.array([1.0]), alphas[:-1])).astype(np.float32)
     latent = model.latent_from_numpy(synth_normal(args.seed, "sd.latent", (1, 4, 64, 64)))
-    model.compile(unconditional_context, context, latent)
+    if args.sampler:
+        from tinyfusers_amd.variants.samplers import make
+        schedule = make(args.sampler, args.eta).schedule(args.steps)
+        print(f"sampler {schedule.sampler}: {len(schedule.timesteps)} steps, timesteps {schedule.timesteps[0]} .. {schedule.timesteps[-1]}")
+        model.compile(unconditional_context, context, latent, sampler=schedule)
+    else:
+        model.compile(unconditional_context, context, latent)
     times = []
     for n in range(args.images + 1):
-        model.set_latent(synth_normal(args.seed + n, "sd.latent", (1, 4, 64, 64)))
+        if args.sampler:
+            model.start(seed=args.seed, image_offset=n)          # image n of the seed: its latent and ancestral noise drawn on the device
+        else:
+            model.set_latent(synth_normal(args.seed + n, "sd.latent", (1, 4, 64, 64)))
         t0 = time.perf_counter()
-        for index, timestep in list(enumerate(timesteps))[::-1]:
-            model.step(timestep, alphas[index], alphas_prev[index], args.guidance)
+        if args.sampler:
+            model.run(args.guidance)
+        else:
+            for index, timestep in list(enumerate(timesteps))[::-1]:
+                model.step(timestep, alphas[index], alphas_prev[index], args.guidance)
         model.synchronize()
         t1 = time.perf_counter()
         assert np.isfinite(latent.numpy()).all(), f"image {n}: the sampler produced a non-finite latent"

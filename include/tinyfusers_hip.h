@@ -472,6 +472,22 @@ int tf_cfg_ddim_step_f32(void* latent_nchw_f32, const void* unet_out_2b_nhwc_f16
  * (variants/sd.py:31-45) run as two independent UNet chains on two streams / graph branches (config.cfg_parallel) */
 int tf_cfg_ddim_step2_f32(void* latent, const void* eps_uncond, const void* eps_cond, const void* step_params, int B, int C, int H, int W, tfStream_t s);
 
+/* ---- samplers beyond sigma = 0 DDIM (csrc/sampler.hip; generalises variants/sd.py:14-25 and the CFG combine of :27-46) -------------
+ * Noise: Philox4x32-10, key = (seed_lo, seed_hi), counter = (q, global image index, step, tag); counter q of an image gives its NCHW
+ * elements 4q .. 4q+3 (u = ((bits >> 8) + 0.5) 2^-24, Box-Muller on (u0, u1) and (u2, u3)).  Tag 0: initial latent; tag 1: the ancestral
+ * noise of schedule step `step`.  Image k's noise is independent of the batch size and of the rank that draws it. */
+/* out (images, per_image) fp32 N(0,1): images image_offset .. image_offset + images - 1 (per_image <= 2^32) */
+int tf_randn_f32(void* out, int images, long long per_image, unsigned seed_lo, unsigned seed_hi, int image_offset, int step, int tag, tfStream_t s);
+/* tf_set_step_params_copy (variants/sd.py:27-46 step scalars) extended to the sampler block of 8 words: [0..3] as there, then u32 [4] the
+ * schedule row, [5] [6] the seed, [7] the global index of image 0.  nbytes = 0 (dst, src may be NULL): no copy, the non-hoisted step */
+int tf_set_sampler_params(void* step_params, float timestep, float a_t, float a_prev, float guidance, int row, unsigned seed_lo, unsigned seed_hi, int image_offset,
+                          void* dst, const void* src, long long nbytes, tfStream_t s);
+/* the DDIM update of variants/sd.py:14-25 in the one form every sampler shares: e = e_u + g (e_c - e_u), x0 = (x - sqrt(1-a_t) e) / sqrt(a_t),
+ * x' = c_x x + c_0 x0 + c_1 x0_prev + c_n z (z: tag 1, step = row), x0_prev <- x0.  coeffs (rows, 4) fp32 [c_x, c_0, c_1, c_n]; the row and
+ * the seed come from step_params (tf_set_sampler_params).  x0_hist (B,C,H,W) fp32 is read only when c_1 != 0.  eps2 as tf_cfg_ddim_step_f32 */
+int tf_cfg_sampler_step_f32(void* latent, const void* eps2, void* x0_hist, const void* step_params, const void* coeffs, int rows, int B, int C, int H, int W, tfStream_t s);
+int tf_cfg_sampler_step_bf16(void* latent, const void* eps2, void* x0_hist, const void* step_params, const void* coeffs, int rows, int B, int C, int H, int W, tfStream_t s);
+
 #ifdef __cplusplus
 }
 #endif

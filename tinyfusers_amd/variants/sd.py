@@ -19,13 +19,13 @@ from .. import config
 from ..native import hip
 from ..storage.tensor import Branch, DeviceArray, Stream, _sh, asarray, bfloat16, pool, use_stream
 from ..vision.unet import SD15, StepParams, UNetModel
+from .samplers import Schedule, UnsupportedSamplerConfig, get_alphas_cumprod  # noqa: F401  (get_alphas_cumprod: variants/sd.py:61-65, re-exported)
 
 
-def get_alphas_cumprod(beta_start=0.00085, beta_end=0.0120, n_training_steps=1000):
-    """variants/sd.py:61-65 (host fp32: a 1000-entry table, not device work)."""
-    betas = np.linspace(beta_start ** 0.5, beta_end ** 0.5, n_training_steps, dtype=np.float32) ** 2
-    alphas = 1.0 - betas
-    return np.cumprod(alphas, axis=0)
+def _seed_words(seed):
+    """A seed (any int; taken mod 2^64) -> the two 32-bit key words of the device generator."""
+    seed = int(seed) % (1 << 64)
+    return seed & 0xFFFFFFFF, seed >> 32
 
 
 def _scalar(v):
@@ -130,8 +130,18 @@ class StableDiffusion:
         self._latent.copy_from_numpy(x)
         return self._latent
 
+    @staticmethod
+    def randn_latent(shape, seed, image_offset=0):
+        """A device fp32 NCHW latent (B,C,H,W) of N(0,1) noise drawn on the device (tf_randn_f32, tag 0): image b is global image
+        image_offset + b of ``seed``, whatever the batch it is drawn in (a rank of dist.shard_range reproduces a single-GPU run's images)."""
+        b = int(shape[0])
+        out = DeviceArray.empty(tuple(shape), np.float32, "row")
+        lo, hi = _seed_words(seed)
+        hip.tf_randn_f32(out.ptr, b, out.size // b if b else 0, lo, hi, int(image_offset), 0, 0, _sh())
+        return out
+
     # -- whole-step HIP graph ------------------------------------------------------------------------
-    def compile(self, unconditional_context, context, latent, stream=None, warmup=2, timesteps=None):
+    def compile(self, unconditional_context, context, latent, stream=None, warmup=2, timesteps=None, sampler=None):
         """Capture one denoising step for these (static) buffers into a HIP graph.  Afterwards
         ``step(timestep, a_t, a_prev, guidance)`` updates ``latent`` in place with one graph launch.
 
@@ -143,11 +153,29 @@ class StableDiffusion:
         The captured step reads PRIVATE buffers (the stacked context and, hoisted, its K|V projection): ``set_context`` is the only supported
         way to change the prompts of a compiled sampler -- writing into the arrays handed to ``compile`` (or into ``_ctx2``) changes nothing the
         cross-attention reads.  The hoisted tables are keyed by ``weights_key()``: eager steps (``step(..., eager=True)``) follow weights replaced
-        after ``compile``; the captured graph holds the addresses of the weights it was captured with, so a new weight set needs ``compile`` again."""
+        after ``compile``; the captured graph holds the addresses of the weights it was captured with, so a new weight set needs ``compile`` again.
+
+        ``sampler``: a ``Schedule`` (variants/samplers.py, e.g. ``DPMSolverPP2M().schedule(20)``).  The captured step then ends in the fused
+        sampler update (tf_cfg_sampler_step_*) instead of the DDIM one, its coefficient table is uploaded once, the model owns an fp32 x0 history,
+        and the sampler is driven by ``start`` / ``run`` / ``step_sampler``; ``step`` is refused.  Without one, nothing changes."""
         if config.is_bf16() and (config.parallel_branches or config.cfg_parallel):
             raise RuntimeError("StableDiffusion.compile: the bfloat16 step has no parallel-branch / two-chain CFG form (TF_PARALLEL_BRANCHES / TF_CFG_PARALLEL are fp16-only experiments)")
+        if sampler is not None:
+            if not isinstance(sampler, Schedule):
+                raise TypeError("StableDiffusion.compile: sampler= takes a Schedule (e.g. DPMSolverPP2M().schedule(20))")
+            if config.cfg_parallel:
+                raise UnsupportedSamplerConfig("StableDiffusion.compile: a sampler schedule has no two-chain CFG form (TF_CFG_PARALLEL is an fp16-only experiment)")
+            timesteps = sampler.timesteps
         self._stream = stream or Stream()
         self._latent, self._unc, self._ctx = latent, unconditional_context, context
+        self._sched = sampler
+        if sampler is not None:
+            with use_stream(self._stream):
+                self._params = StepParams.__new__(StepParams)          # the sampler block: the 4 step scalars + row, seed, image offset
+                self._params.dev = DeviceArray.zeros((8,), np.float32, "row")
+                self._coeffs = DeviceArray.from_numpy(np.asarray(sampler.coeffs, np.float32), np.float32, "row")
+                self._x0_hist = DeviceArray.zeros(latent.shape, np.float32, "row")
+            self._seed, self._image_offset, self._cursor = (0, 0), 0, 0
         sp = self._step_params()
         unet = self.model.diffusion_model
         with use_stream(self._stream):
@@ -165,7 +193,10 @@ class StableDiffusion:
             saved = DeviceArray.empty(latent.shape, np.float32, "row")
             hip.tf_memcpy_async(saved.ptr, latent.ptr, latent.nbytes, 3, _sh())
             for _ in range(warmup):                 # warms the pool and builds the lazily packed weights
-                sp.set(981.0, 0.5, 0.6, 7.5)
+                if sampler is not None:
+                    hip.tf_set_sampler_params(sp.dev.ptr, 981.0, 0.5, 0.6, 7.5, 0, 0, 0, 0, None, None, 0, _sh())
+                else:
+                    sp.set(981.0, 0.5, 0.6, 7.5)
                 self._eager_step(sp)
             hip.tf_memcpy_async(latent.ptr, saved.ptr, latent.nbytes, 3, _sh())
             self._stream.synchronize()
@@ -213,23 +244,23 @@ class StableDiffusion:
             out = unet(x2, sp, self._ctx2, shared=(None, self._emb_cur, self._kv_all))     # (step() has put this timestep's row into _emb_cur)
         else:
             out = unet(x2, sp, self._ctx2)
-        (hip.tf_cfg_ddim_step_bf16 if config.is_bf16() else hip.tf_cfg_ddim_step_f32)(self._latent.ptr, out.ptr, sp.dev.ptr, b, c, h, w, _sh())
+        if getattr(self, "_sched", None) is not None:
+            (hip.tf_cfg_sampler_step_bf16 if config.is_bf16() else hip.tf_cfg_sampler_step_f32)(
+                self._latent.ptr, out.ptr, self._x0_hist.ptr, sp.dev.ptr, self._coeffs.ptr, len(self._sched.timesteps), b, c, h, w, _sh())
+        else:
+            (hip.tf_cfg_ddim_step_bf16 if config.is_bf16() else hip.tf_cfg_ddim_step_f32)(self._latent.ptr, out.ptr, sp.dev.ptr, b, c, h, w, _sh())
         self._keep = (x2, out)      # graph nodes reference these blocks: keep them out of the pool
 
     def step(self, timestep, a_t, a_prev, guidance, eager=False):
         """One denoising step on the sampler stream, asynchronous.  The stream switch is un-ordered on purpose: an event
         edge between two graph launches costs 0.2 ms per step (measured, tools/ab3.sh), and consecutive steps are ordered by
         the stream itself.  Work on other streams that touches the latent goes through set_latent() / synchronize()."""
+        if getattr(self, "_sched", None) is not None:
+            raise UnsupportedSamplerConfig("StableDiffusion.step: this model was compiled with a sampler schedule -- drive it with start() / run() / step_sampler()")
         sp = self._params
         with use_stream(self._stream, ordered=False):
             if getattr(self, "_emb_cur", None) is not None:
-                key = self.model.diffusion_model.weights_key()
-                if getattr(self, "_kv_all", None) is not None and self._kv_key != key:
-                    # a to_k / to_v (or any hoisted) weight was replaced since compile(): the K|V projection the graph reads is stale -- refresh it in place
-                    kv = self.model.diffusion_model.context_kv(self._ctx2)
-                    hip.tf_memcpy_async(self._kv_all.ptr, kv.ptr, kv.nbytes, 3, _sh())
-                    self._kv_tmp, self._kv_key = kv, key
-                row = self._emb_row(float(timestep), key)     # (computed on this stream the first time a timestep is seen)
+                row = self._hoisted_row(timestep)
                 hip.tf_set_step_params_copy(sp.dev.ptr, float(timestep), float(a_t), float(a_prev), float(guidance), self._emb_cur.ptr, row.ptr, row.nbytes, _sh())
             else:
                 sp.set(timestep, a_t, a_prev, guidance)
@@ -237,6 +268,71 @@ class StableDiffusion:
                 self._eager_step(sp)
             else:
                 hip.tf_graph_launch(self._graph, self._stream.handle)
+
+    def _hoisted_row(self, timestep):
+        """The cached time-embedding row of this timestep for the replay's parameter launch; refreshes the hoisted K|V first if a weight changed."""
+        key = self.model.diffusion_model.weights_key()
+        if getattr(self, "_kv_all", None) is not None and self._kv_key != key:
+            # a to_k / to_v (or any hoisted) weight was replaced since compile(): the K|V projection the graph reads is stale -- refresh it in place
+            kv = self.model.diffusion_model.context_kv(self._ctx2)
+            hip.tf_memcpy_async(self._kv_all.ptr, kv.ptr, kv.nbytes, 3, _sh())
+            self._kv_tmp, self._kv_key = kv, key
+        return self._emb_row(float(timestep), key)     # (computed on this stream the first time a timestep is seen)
+
+    # -- sampler schedules (compile(..., sampler=Schedule)) -----------------------------------------------------------------------
+    def _require_sampler(self, what):
+        if getattr(self, "_sched", None) is None:
+            raise UnsupportedSamplerConfig(f"StableDiffusion.{what}: compile(..., sampler=<Schedule>) first (this model runs the DDIM step())")
+        return self._sched
+
+    def start(self, seed=None, noise=None, image_offset=0):
+        """A new image batch for the compiled sampler: sets the latent in place and rewinds the schedule.  ``seed``: the initial latent is
+        drawn on the device (tag 0; image b is global image image_offset + b), and the ancestral noise of every step comes from the same seed
+        (tag 1); ``noise``: a host (B,C,H,W) array for the initial latent instead (the ancestral noise then uses ``seed``, default 0).
+        Ordered after every step already queued."""
+        self._require_sampler("start")
+        if seed is None and noise is None:
+            raise ValueError("StableDiffusion.start: pass seed= (device noise) or noise= (a host array)")
+        if int(image_offset) < 0:
+            raise ValueError(f"StableDiffusion.start: image_offset must be >= 0, got {image_offset}")
+        self._seed, self._image_offset, self._cursor = _seed_words(0 if seed is None else seed), int(image_offset), 0
+        if noise is not None:
+            return self.set_latent(noise)
+        self.synchronize()
+        b = self._latent.shape[0]
+        with use_stream(self._stream):
+            hip.tf_randn_f32(self._latent.ptr, b, self._latent.size // b, self._seed[0], self._seed[1], self._image_offset, 0, 0, _sh())
+        return self._latent
+
+    def step_sampler(self, i, guidance, eager=False):
+        """Step i of the compiled schedule (asynchronous, on the sampler stream): one parameter launch (timestep scalars, schedule row, seed and
+        -- hoisted -- the cached time-embedding row) and one graph replay, the same launches as ``step``."""
+        sched = self._require_sampler("step_sampler")
+        n = len(sched.timesteps)
+        i = int(i)
+        if not 0 <= i < n:
+            raise IndexError(f"StableDiffusion.step_sampler: step {i} outside the schedule's {n} steps")
+        t = sched.timesteps[i]
+        with use_stream(self._stream, ordered=False):
+            if getattr(self, "_emb_cur", None) is not None:
+                row = self._hoisted_row(t)
+                dst, src, nbytes = self._emb_cur.ptr, row.ptr, row.nbytes
+            else:
+                dst, src, nbytes = None, None, 0
+            hip.tf_set_sampler_params(self._params.dev.ptr, float(t), float(sched.alphas[i]), float(sched.alphas_prev[i]), float(guidance), i,
+                                      self._seed[0], self._seed[1], self._image_offset, dst, src, nbytes, _sh())
+            if eager or self._graph is None:
+                self._eager_step(self._params)
+            else:
+                hip.tf_graph_launch(self._graph, self._stream.handle)
+        self._cursor = i + 1
+
+    def run(self, guidance, eager=False):
+        """Every remaining step of the schedule (all of them after ``start``); returns the latent (asynchronous: synchronize() to read it)."""
+        sched = self._require_sampler("run")
+        for i in range(self._cursor, len(sched.timesteps)):
+            self.step_sampler(i, guidance, eager=eager)
+        return self._latent
 
     def _emb_row(self, t, key=None):
         """The cached time-embedding row of timestep t (keyed by the weights it was computed from; at most 1024 rows are kept)."""

@@ -1,0 +1,134 @@
+#!/usr/bin/env python3
+"""Samplers on one box, one process (report, not a gate): the SD-1.5 compiled step with DPM-Solver++(2M) (the fused sampler update,
+tf_cfg_sampler_step_f32) against the DDIM step (tf_cfg_ddim_step_f32), 100 graph replays each, alternated over several rounds; and the
+config-3 end-to-end img/s (CLIP x2 -> steps -> VAE decode, batch 1) at 20 DPM++2M steps against 50 DDIM steps.
+
+    python tools/sampler_bench.py [--replays 100] [--rounds 5] [--images 3] [--dpm-steps 20]
+Prints one JSON line."""
+import argparse
+import contextlib
+import ctypes
+import io
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--replays", type=int, default=100)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--images", type=int, default=3)
+    ap.add_argument("--dpm-steps", type=int, default=20)
+    args = ap.parse_args()
+
+    import torch  # noqa: F401  (the weight arena is a torch allocation)
+    import tinyfusers_amd.storage.tensor as T
+    from bench import build_weight_arena
+    from tinyfusers_amd.native import hip
+    from tinyfusers_amd.storage.state import param_shapes, update_state
+    from tinyfusers_amd.storage.synth import synth_normal, synth_state_dict
+    from tinyfusers_amd.variants.samplers import DDIM, DPMSolverPP2M
+    from tinyfusers_amd.variants.sd import StableDiffusion
+
+    T.ensure_init(0)
+    ddim_m, dpm_m = StableDiffusion(), StableDiffusion()
+    arena, _, _, _, state = build_weight_arena(ddim_m.model.diffusion_model, 0, 1, 0)
+    update_state(dpm_m.model.diffusion_model, state, "")
+    with contextlib.redirect_stdout(io.StringIO()):
+        for name, sub in (("first_stage_model", ddim_m.first_stage_model), ("cond_stage_model", ddim_m.cond_stage_model)):
+            update_state(sub, synth_state_dict(param_shapes(sub, name), 0), name)
+    rng = np.random.default_rng(0)
+    prompt = np.full((1, 77), 49407, dtype=np.int64); prompt[0, 0] = 49406; prompt[0, 1:10] = rng.integers(0, 49406, 9)
+    empty = np.full((1, 77), 49407, dtype=np.int64); empty[0, 0] = 49406
+    text_model = ddim_m.cond_stage_model.transformer.text_model
+    text_model(prompt)
+    ctx, unc = text_model(prompt), text_model(empty)
+    hip.tf_stream_sync(None)
+
+    noise = synth_normal(1234, "sd.latent", (1, 4, 64, 64))
+    ddim_sched, dpm_sched = DDIM().schedule(50), DPMSolverPP2M().schedule(args.dpm_steps)
+    lat_a, lat_b = ddim_m.latent_from_numpy(noise), dpm_m.latent_from_numpy(noise)
+    ddim_m.compile(unc, ctx, lat_a, timesteps=ddim_sched.timesteps)                 # the DDIM step() path, exactly as bench.py captures it
+    dpm_m.compile(unc, ctx, lat_b, sampler=dpm_sched)
+    lat0 = T.DeviceArray.from_numpy(noise, np.float32, "row")
+    ts, al, ap_ = ddim_sched.timesteps, ddim_sched.alphas, ddim_sched.alphas_prev
+
+    def ddim_replays(n):
+        for s in range(n):
+            i = s % 50
+            if i == 0:
+                hip.tf_memcpy_async(lat_a.ptr, lat0.ptr, lat_a.nbytes, 3, ddim_m._stream.handle)   # a fresh trajectory every 50 steps
+            ddim_m.step(ts[i], al[i], ap_[i], 7.5)
+
+    def dpm_replays(n):
+        k = len(dpm_sched.timesteps)
+        for s in range(n):
+            i = s % k
+            if i == 0:
+                hip.tf_memcpy_async(lat_b.ptr, lat0.ptr, lat_b.nbytes, 3, dpm_m._stream.handle)
+            dpm_m.step_sampler(i, 7.5)
+
+    def timed(model, fn, n):
+        ev0, ev1, ms = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_float()
+        hip.tf_event_create(ctypes.byref(ev0)); hip.tf_event_create(ctypes.byref(ev1))
+        model.synchronize()
+        hip.tf_event_record(ev0, model._stream.handle)
+        fn(n)
+        hip.tf_event_record(ev1, model._stream.handle)
+        model.synchronize()
+        hip.tf_event_elapsed_ms(ctypes.byref(ms), ev0, ev1)
+        hip.tf_event_destroy(ev0); hip.tf_event_destroy(ev1)
+        return ms.value / n
+
+    ddim_replays(20); dpm_replays(20)
+    step_ms = {"ddim": [], "dpmpp2m": []}
+    for _ in range(args.rounds):
+        step_ms["ddim"].append(timed(ddim_m, ddim_replays, args.replays))
+        step_ms["dpmpp2m"].append(timed(dpm_m, dpm_replays, args.replays))
+    med = {k: float(np.median(v)) for k, v in step_ms.items()}
+
+    def e2e(model, steps, sample):
+        recs = []
+        for n in range(args.images + 1):
+            t0 = time.perf_counter()
+            c, u = text_model(prompt), text_model(empty)
+            hip.tf_stream_sync(None)
+            t1 = time.perf_counter()
+            model.set_context(u, c)
+            sample(n)
+            model.synchronize()
+            t2 = time.perf_counter()
+            with T.use_stream(model._stream):
+                img = ddim_m.decode(model._latent)
+            t3 = time.perf_counter()
+            assert img.shape == (512, 512, 3)
+            recs.append((t1 - t0, t2 - t1, t3 - t2))
+        c, s, d = (float(np.median([r[i] for r in recs[1:]])) for i in range(3))
+        return {"img_per_s": round(1.0 / (c + s + d), 3), "steps": steps, "clip_ms": round(c * 1e3, 2), "sampler_ms": round(s * 1e3, 2), "decode_ms": round(d * 1e3, 2)}
+
+    def ddim_sample(n):
+        ddim_m.set_latent(synth_normal(1234 + n, "sd.latent", (1, 4, 64, 64)))
+        for i in range(50):
+            ddim_m.step(ts[i], al[i], ap_[i], 7.5)
+
+    def dpm_sample(n):
+        dpm_m.start(seed=1234, image_offset=n)
+        dpm_m.run(7.5)
+
+    out = {"metric": "sd15_sampler_step_ms", "ddim_step_ms": round(med["ddim"], 4), "dpmpp2m_step_ms": round(med["dpmpp2m"], 4),
+           "dpmpp2m_over_ddim": round(med["dpmpp2m"] / med["ddim"], 4), "replays": args.replays, "rounds": args.rounds,
+           "step_ms_per_round": {k: [round(x, 4) for x in v] for k, v in step_ms.items()},
+           "e2e_ddim50": e2e(ddim_m, 50, ddim_sample), "e2e_dpmpp2m": e2e(dpm_m, len(dpm_sched.timesteps), dpm_sample)}
+    out["e2e_speedup"] = round(out["e2e_dpmpp2m"]["img_per_s"] / out["e2e_ddim50"]["img_per_s"], 3)
+    print(json.dumps(out))
+    del arena
+
+
+if __name__ == "__main__":
+    main()
