@@ -9,6 +9,7 @@ BASELINE config 3: full 50-step sampler, batch 1, end-to-end img/s.
 
     python -m example.sd1 --steps 50 [--ckpt sd-v1-4.ckpt] [--out rendered.npy]
     python -m example.sd1 --steps 20 --sampler dpmpp2m          # DPM-Solver++(2M); also ddim, ddim-eta, euler-a (--eta)
+    python -m example.sd1 --steps 20 --sampler dpmpp2m --init-image x.npy --strength 0.6 [--mask m.npy]   # img2img / inpainting
 """
 import argparse
 import os
@@ -32,7 +33,21 @@ if __name__ == "__main__":
     ap.add_argument("--sampler", choices=["ddim", "ddim-eta", "dpmpp2m", "euler-a"], default=None,
                     help="run a sampler schedule (variants/samplers.py) with device-side noise from --seed; default: the reference's DDIM loop")
     ap.add_argument("--eta", type=float, default=None, help="noise scale of ddim-eta (default 1) and euler-a (default 1)")
+    ap.add_argument("--init-image", default="", help="image-to-image from this (H,W,3) uint8 image: .npy, or .png / .jpg through PIL")
+    ap.add_argument("--strength", type=float, default=None, help="with --init-image: the part of the schedule that runs, in (0, 1] (default 0.6)")
+    ap.add_argument("--mask", default="", help="with --init-image: inpaint where this (H,W) mask is >= 0.5 (uint8: nonzero); .npy, .png or .jpg")
     args = ap.parse_args()
+    if (args.init_image or args.mask or args.strength is not None) and not args.sampler:
+        ap.error("--init-image, --strength and --mask need --sampler")
+    if (args.mask or args.strength is not None) and not args.init_image:
+        ap.error("--strength and --mask need --init-image")
+
+    def load_array(path, mode):
+        """.npy as stored; .png / .jpg through PIL (imported only here), mode "RGB" or "L"."""
+        if path.lower().endswith(".npy"):
+            return np.load(path)
+        from PIL import Image
+        return np.asarray(Image.open(path).convert(mode))
 
     import tinyfusers_amd.storage.tensor as T
     from tinyfusers_amd.storage.state import param_shapes, update_state
@@ -73,17 +88,42 @@ if __name__ == "__main__":
     timesteps = list(range(1, 1000, 1000 // args.steps))
     alphas = model.alphas_cumprod[timesteps]
     alphas_prev = np.concatenate((np.array([1.0]), alphas[:-1])).astype(np.float32)
-    latent = model.latent_from_numpy(synth_normal(args.seed, "sd.latent", (1, 4, 64, 64)))
+    init_image = mask = None
+    lat_hw = (64, 64)
+    if args.init_image:
+        init_image = load_array(args.init_image, "RGB")
+        if init_image.ndim == 3:
+            init_image = init_image[None]
+        if init_image.dtype != np.uint8 or init_image.ndim != 4 or init_image.shape[0] != 1 or init_image.shape[3] != 3:
+            sys.exit(f"--init-image: expected one uint8 (H,W,3) image, got {init_image.dtype} {init_image.shape}")
+        why = StableDiffusion.encoder_size_error(init_image.shape[1], init_image.shape[2])
+        if why:
+            sys.exit(f"--init-image: {why}")
+        lat_hw = (init_image.shape[1] // 8, init_image.shape[2] // 8)
+        if args.mask:
+            mask = load_array(args.mask, "L")
+            mask = StableDiffusion.latent_mask(mask[None] if mask.ndim == 2 else mask)
+    latent = model.latent_from_numpy(synth_normal(args.seed, "sd.latent", (1, 4) + lat_hw))
     if args.sampler:
         from tinyfusers_amd.variants.samplers import make
-        schedule = make(args.sampler, args.eta).schedule(args.steps)
-        print(f"sampler {schedule.sampler}: {len(schedule.timesteps)} steps, timesteps {schedule.timesteps[0]} .. {schedule.timesteps[-1]}")
-        model.compile(unconditional_context, context, latent, sampler=schedule)
+        strength = 1.0 if init_image is None else (0.6 if args.strength is None else args.strength)
+        schedule = make(args.sampler, args.eta).schedule(args.steps, strength=strength)
+        print(f"sampler {schedule.sampler}: {len(schedule.timesteps)} steps, timesteps {schedule.timesteps[0]} .. {schedule.timesteps[-1]}"
+              + (f" (strength {strength}{', inpainting' if mask is not None else ''})" if init_image is not None else ""))
+        model.compile(unconditional_context, context, latent, sampler=schedule, inpaint=mask is not None)
     else:
         model.compile(unconditional_context, context, latent)
     times = []
     for n in range(args.images + 1):
-        if args.sampler:
+        enc = 0.0
+        if init_image is not None:
+            t0 = time.perf_counter()
+            with T.use_stream(model._stream):
+                x0 = model.encode_image(init_image)              # the VAE encoder: x0 = 0.18215 x its means
+            model.synchronize()
+            enc = time.perf_counter() - t0
+            model.start(seed=args.seed, image_offset=n, init_latent=x0, mask=mask)   # x0 noised to the schedule's start level
+        elif args.sampler:
             model.start(seed=args.seed, image_offset=n)          # image n of the seed: its latent and ancestral noise drawn on the device
         else:
             model.set_latent(synth_normal(args.seed + n, "sd.latent", (1, 4, 64, 64)))
@@ -99,9 +139,15 @@ if __name__ == "__main__":
         with T.use_stream(model._stream):
             x = model.decode(latent)
         t2 = time.perf_counter()
-        times.append((t1 - t0, t2 - t1))
-        print(f"image {n}: {args.steps} steps {1e3 * (t1 - t0):.1f} ms ({args.steps / (t1 - t0):.1f} steps/s), decode {1e3 * (t2 - t1):.1f} ms, image {x.shape} mean {x.mean():.1f}")
-    s, d = np.median([t[0] for t in times[1:]]), np.median([t[1] for t in times[1:]])
-    print(f"end-to-end (sampler + VAE decode, batch 1): {1.0 / (s + d):.3f} img/s  [{args.steps} steps {1e3 * s:.1f} ms + decode {1e3 * d:.1f} ms]")
+        times.append((t1 - t0, t2 - t1, enc))
+        steps = len(schedule.timesteps) if init_image is not None else args.steps
+        print(f"image {n}: " + (f"encode {1e3 * enc:.1f} ms, " if init_image is not None else "")
+              + f"{steps} steps {1e3 * (t1 - t0):.1f} ms ({steps / (t1 - t0):.1f} steps/s), decode {1e3 * (t2 - t1):.1f} ms, image {x.shape} mean {x.mean():.1f}")
+    s, d, e = (np.median([t[i] for t in times[1:]]) for i in range(3))
+    if init_image is not None:
+        print(f"end-to-end (VAE encode + sampler + VAE decode, batch 1): {1.0 / (e + s + d):.3f} img/s  [encode {1e3 * e:.1f} ms + {steps} steps "
+              f"{1e3 * s:.1f} ms + decode {1e3 * d:.1f} ms]")
+    else:
+        print(f"end-to-end (sampler + VAE decode, batch 1): {1.0 / (s + d):.3f} img/s  [{steps} steps {1e3 * s:.1f} ms + decode {1e3 * d:.1f} ms]")
     if args.out:
         np.save(args.out, x)

@@ -488,6 +488,23 @@ int tf_set_sampler_params(void* step_params, float timestep, float a_t, float a_
 int tf_cfg_sampler_step_f32(void* latent, const void* eps2, void* x0_hist, const void* step_params, const void* coeffs, int rows, int B, int C, int H, int W, tfStream_t s);
 int tf_cfg_sampler_step_bf16(void* latent, const void* eps2, void* x0_hist, const void* step_params, const void* coeffs, int rows, int B, int C, int H, int W, tfStream_t s);
 
+/* ---- image-to-image and masked inpainting (csrc/img2img.hip): the encoder edges of vae/vae.py:12-15 (image -> means, only the means kept),
+ * the inverse of the decode scale and tail of variants/sd.py:48-54, and the sampler update of variants/sd.py:14-25 (tf_cfg_sampler_step_*)
+ * with a latent blend.  Philox tags: 0 the initial latent, 1 the ancestral noise, 2 the known region of an inpainting step. */
+/* uint8 (B,H,W,3) -> fp16 x / 127.5 - 1 in the same element order: the NHWC (B,3,H,W) image AutoencoderKL.encode reads; n = B*H*W*3 */
+int tf_image_from_u8_f16(void* out, const void* x, long long n, tfStream_t s);
+/* encoder means (B,4,H,W) fp16 NHWC -> x0 (B,4,H,W) fp32 NCHW = 0.18215 means (the decode side divides by it, variants/sd.py:49) */
+int tf_means_to_latent_f32(void* x0, const void* means, int B, int H, int W, tfStream_t s);
+/* out = sqrt(a) x0 + sqrt(1-a) z, z the tag-0 normal of global image image_offset + k at step 0 (tf_randn_f32's initial latent); out may
+ * be x0 itself; a in (0, 1] */
+int tf_noise_to_level_f32(void* out, const void* x0, int images, long long per_image, float a, unsigned seed_lo, unsigned seed_hi, int image_offset, tfStream_t s);
+/* tf_cfg_sampler_step_* then x' <- m x' + (1-m) (sqrt(a_s) x0_init + sqrt(1-a_s) z2): a_s = step_params[2] (a_prev), z2 the tag-2 normal at
+ * step = row; x0_init (B,C,H,W) fp32, mask (B,1,H,W) fp32, 1 = repaint (fractional values blend) */
+int tf_cfg_sampler_step_masked_f32(void* latent, const void* eps2, void* x0_hist, const void* step_params, const void* coeffs, int rows, const void* x0_init,
+                                   const void* mask, int B, int C, int H, int W, tfStream_t s);
+int tf_cfg_sampler_step_masked_bf16(void* latent, const void* eps2, void* x0_hist, const void* step_params, const void* coeffs, int rows, const void* x0_init,
+                                    const void* mask, int B, int C, int H, int W, tfStream_t s);
+
 #ifdef __cplusplus
 }
 #endif

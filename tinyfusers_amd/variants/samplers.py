@@ -15,8 +15,10 @@ once; the device kernel (tf_cfg_sampler_step_*, csrc/sampler.hip) is the same fo
                           step into sigma = 0 (a_s = 1, lambda = inf) are first order.
 
 ``Sampler.schedule(steps)`` walks the reference's timesteps (example/sd1.py:54-57: range(1, 1000, 1000 // steps), high to low, a_prev = 1
-after the last step) and returns a ``Schedule`` that ``StableDiffusion.compile(..., sampler=...)`` captures.
+after the last step) and returns a ``Schedule`` that ``StableDiffusion.compile(..., sampler=...)`` captures; ``schedule(steps, strength=s)``
+is the image-to-image suffix of that walk.
 """
+import math
 from collections import namedtuple
 
 import numpy as np
@@ -119,6 +121,13 @@ def default_timesteps(steps):
     return list(range(1, N_TRAIN, max(1, N_TRAIN // steps)))[::-1]
 
 
+def _check_strength(strength):
+    s = float(strength)
+    if not 0.0 < s <= 1.0:                                         # (False for nan)
+        raise ValueError(f"samplers: strength must lie in (0, 1], got {strength}")
+    return s
+
+
 def _check_timesteps(timesteps):
     ts = [int(t) for t in timesteps]
     if any(float(t) != float(u) for t, u in zip(ts, timesteps)):
@@ -140,9 +149,12 @@ class Sampler:
     def coefficients(self, alphas_cumprod):
         raise NotImplementedError
 
-    def schedule(self, steps=None, timesteps=None, alphas_cumprod=None):
+    def schedule(self, steps=None, timesteps=None, alphas_cumprod=None, strength=1.0):
         """The walk: timesteps (default example/sd1.py:54-57's for ``steps``), the alpha-bar pairs (a_prev = 1 after the last step) and the
-        coefficient table.  ``alphas_cumprod``: the 1000-entry training table (default variants/sd.py:61-65's, fp32 like the reference's)."""
+        coefficient table.  ``alphas_cumprod``: the 1000-entry training table (default variants/sd.py:61-65's, fp32 like the reference's).
+        ``strength`` in (0, 1]: image-to-image (SDEdit) keeps the last max(1, floor(n strength)) steps of the n-step walk, and the table is
+        built on that truncated walk (DPM-Solver++(2M)'s first kept step is first order).  An img2img run starts at level ``alphas[0]``."""
+        strength = _check_strength(strength)
         if timesteps is None:
             timesteps = default_timesteps(self.default_steps if steps is None else steps)
         elif steps is not None and int(steps) != len(timesteps):
@@ -150,6 +162,8 @@ class Sampler:
         ts = _check_timesteps(timesteps)
         ac = np.asarray(get_alphas_cumprod() if alphas_cumprod is None else alphas_cumprod, dtype=np.float64)
         walk = np.concatenate([ac[ts], [1.0]])
+        first = len(ts) - max(1, math.floor(len(ts) * strength))
+        ts, walk = ts[first:], walk[first:]
         return Schedule(self, ts, walk[:-1].copy(), walk[1:].copy(), self.coefficients(walk))
 
     def __repr__(self):

@@ -8,7 +8,8 @@ returns x_{t-1}.  Differences, all MI355X-first:
   * ``compile()`` captures the whole step (one launch per fused op) into one HIP graph replayed per step.
 Beyond the UNet denoising path the next rows are built too: first_stage_model (VAE decode side, 8(f1))
 and cond_stage_model.transformer.text_model (CLIP text encoder, 8(f2)), under the reference's attribute names so that
-update_state walks the same LDM checkpoint keys.
+update_state walks the same LDM checkpoint keys.  The encoder side of first_stage_model feeds image-to-image and inpainting
+(``encode_image``, ``start(init_image= / init_latent=, mask=)``, ``compile(..., inpaint=True)``).
 """
 import ctypes
 from collections import namedtuple
@@ -37,7 +38,7 @@ class StableDiffusion:
         self.alphas_cumprod = get_alphas_cumprod()
         self.model = namedtuple("DiffusionModel", ["diffusion_model"])(diffusion_model=UNetModel(cfg, init=init))
         from ..vae.vae import AutoencoderKL
-        self.first_stage_model = AutoencoderKL(init=init, init_encoder=False) if cfg is SD15 else None   # the sampler uses the decode side only: the encoder stays an empty tree until update_state fills it
+        self.first_stage_model = AutoencoderKL(init=init, init_encoder=False) if cfg is SD15 else None   # text-to-image uses the decode side only: the encoder stays an empty tree until update_state fills it (encode_image needs it)
         self.cond_stage_model = None
         if cfg is SD15:                  # variants/sd.py:12: cond_stage_model.transformer.text_model
             from ..vae.encoder import CLIPTextTransformer
@@ -93,6 +94,68 @@ class StableDiffusion:
         hip.tf_memcpy(host.ctypes.data, out.ptr, n, 2)
         return host
 
+    @staticmethod
+    def encoder_size_error(h, w):
+        """Why the VAE encoder cannot take an (h, w) image, or None: three stride-2 levels need multiples of 8, and the reference-exact
+        AttnBlock at the latent resolution (config.head_merge) runs the fused SDPA kernel with head size w / 8 (a multiple of 8 in [8, 160])."""
+        if h < 8 or w < 8 or h % 8 or w % 8:
+            return f"the image size {h}x{w} must be a positive multiple of 8 in both dimensions"
+        if config.head_merge == "reference_exact" and (w % 64 or w > 1280):
+            return f"the width {w} must be a multiple of 64 up to 1280 (the encoder's reference-exact AttnBlock runs a head size of width / 8)"
+        return None
+
+    def encode_image(self, images):
+        """vae/vae.py:12-15 for image-to-image: uint8 (B,H,W,3) images (host or device) -> x0 = 0.18215 x means, a device fp32 NCHW latent
+        (B,4,H/8,W/8) -- the inverse of decode's 1/0.18215 (variants/sd.py:49).  uint8 -> x/127.5 - 1 (tf_image_from_u8_f16) -> Encoder +
+        quant_conv, means only (AutoencoderKL.encode) -> tf_means_to_latent_f32.  Asynchronous, on the current stream."""
+        fsm = self.first_stage_model
+        if fsm is None:
+            raise RuntimeError("StableDiffusion.encode_image: this model has no first_stage_model (SD-1.5 configuration only)")
+        enc = fsm.encoder
+        if any(m.weight is None for m in (enc.conv_in, enc.conv_out, fsm.quant_conv)):
+            raise RuntimeError("StableDiffusion.encode_image: the VAE encoder has no weights -- it is built empty; fill it with update_state "
+                               "from an LDM checkpoint (or synth_state_dict(param_shapes(model)))")
+        if isinstance(images, DeviceArray):
+            dev = images
+        else:
+            images = np.asarray(images)
+            dev = None
+        if np.dtype(images.dtype) != np.uint8 or len(images.shape) != 4 or images.shape[3] != 3:
+            raise ValueError(f"StableDiffusion.encode_image: takes uint8 (B,H,W,3) images, got {np.dtype(images.dtype)} {tuple(images.shape)}")
+        b, h, w, _ = (int(v) for v in images.shape)
+        why = self.encoder_size_error(h, w)
+        if b < 1 or why:
+            raise ValueError(f"StableDiffusion.encode_image: {why or 'an empty batch'}")
+        if dev is None:
+            dev = DeviceArray.from_numpy(np.ascontiguousarray(images), np.uint8, "row")
+        x = DeviceArray.empty((b, 3, h, w), np.float16, "nhwc")          # NHWC: the (B,H,W,3) element order of the uint8 image
+        hip.tf_image_from_u8_f16(x.ptr, dev.ptr, x.size, _sh())
+        means = fsm.encode(x)                                            # (B,4,H/8,W/8) fp16 NHWC
+        x0 = DeviceArray.empty(means.shape, np.float32, "row")
+        hip.tf_means_to_latent_f32(x0.ptr, means.ptr, b, means.shape[2], means.shape[3], _sh())
+        x0._base = (dev, x, means)                                       # (referenced until the kernels have run)
+        return x0
+
+    @staticmethod
+    def latent_mask(mask):
+        """Host helper: an inpainting mask at image resolution (B,H,W) -- bool, uint8 or float, >= 0.5 (uint8: nonzero) means repaint -- to the
+        latent mask (B,1,H/8,W/8) fp32 the masked step reads, by the maximum over each 8x8 block (a latent pixel is repainted when any of its
+        image pixels is).  A float (B,1,h,w) array is a latent mask already: it passes through once its values are checked to lie in [0, 1]."""
+        m = np.asarray(mask)
+        if m.dtype != np.bool_ and m.dtype != np.uint8 and m.dtype.kind != "f":
+            raise TypeError(f"StableDiffusion.latent_mask: bool, uint8 or float masks, got {m.dtype}")
+        if m.dtype.kind == "f" and not (np.isfinite(m).all() and (m >= 0).all() and (m <= 1).all()):
+            raise ValueError("StableDiffusion.latent_mask: float mask values must lie in [0, 1]")
+        if m.ndim == 4:
+            if m.shape[1] != 1 or m.dtype.kind != "f":
+                raise ValueError(f"StableDiffusion.latent_mask: a latent-size mask is float (B,1,h,w), got {m.dtype} {m.shape}")
+            return np.ascontiguousarray(m, dtype=np.float32)
+        if m.ndim != 3 or m.shape[0] < 1 or m.shape[1] < 8 or m.shape[2] < 8 or m.shape[1] % 8 or m.shape[2] % 8:
+            raise ValueError(f"StableDiffusion.latent_mask: takes (B,H,W) with H and W multiples of 8 (or a float (B,1,h,w) latent mask), got {m.shape}")
+        b, h, w = m.shape
+        rep = (m != 0) if m.dtype == np.uint8 else (m >= 0.5)
+        return rep.reshape(b, 1, h // 8, 8, w // 8, 8).any(axis=(3, 5)).astype(np.float32)
+
     # -- helpers ---------------------------------------------------------------------------------
     def _step_params(self):
         if self._params is None:
@@ -141,7 +204,7 @@ class StableDiffusion:
         return out
 
     # -- whole-step HIP graph ------------------------------------------------------------------------
-    def compile(self, unconditional_context, context, latent, stream=None, warmup=2, timesteps=None, sampler=None):
+    def compile(self, unconditional_context, context, latent, stream=None, warmup=2, timesteps=None, sampler=None, inpaint=False):
         """Capture one denoising step for these (static) buffers into a HIP graph.  Afterwards
         ``step(timestep, a_t, a_prev, guidance)`` updates ``latent`` in place with one graph launch.
 
@@ -157,9 +220,15 @@ class StableDiffusion:
 
         ``sampler``: a ``Schedule`` (variants/samplers.py, e.g. ``DPMSolverPP2M().schedule(20)``).  The captured step then ends in the fused
         sampler update (tf_cfg_sampler_step_*) instead of the DDIM one, its coefficient table is uploaded once, the model owns an fp32 x0 history,
-        and the sampler is driven by ``start`` / ``run`` / ``step_sampler``; ``step`` is refused.  Without one, nothing changes."""
+        and the sampler is driven by ``start`` / ``run`` / ``step_sampler``; ``step`` is refused.  Without one, nothing changes.
+
+        ``inpaint=True`` (with a sampler only): the model owns private fp32 ``x0_init`` (the clean latent) and ``mask`` (B,1,H,W) buffers, the
+        mask all ones, and the captured step ends in the masked update (tf_cfg_sampler_step_masked_*), which keeps the region where the mask is
+        0 on the noised trajectory of x0_init.  ``start(init_image= / init_latent=, mask=)`` fills them."""
         if config.is_bf16() and (config.parallel_branches or config.cfg_parallel):
             raise RuntimeError("StableDiffusion.compile: the bfloat16 step has no parallel-branch / two-chain CFG form (TF_PARALLEL_BRANCHES / TF_CFG_PARALLEL are fp16-only experiments)")
+        if inpaint and sampler is None:
+            raise ValueError("StableDiffusion.compile: inpaint=True needs a sampler schedule (sampler=<Schedule>)")
         if sampler is not None:
             if not isinstance(sampler, Schedule):
                 raise TypeError("StableDiffusion.compile: sampler= takes a Schedule (e.g. DPMSolverPP2M().schedule(20))")
@@ -168,13 +237,17 @@ class StableDiffusion:
             timesteps = sampler.timesteps
         self._stream = stream or Stream()
         self._latent, self._unc, self._ctx = latent, unconditional_context, context
-        self._sched = sampler
+        self._sched, self._inpaint = sampler, bool(inpaint)
         if sampler is not None:
             with use_stream(self._stream):
                 self._params = StepParams.__new__(StepParams)          # the sampler block: the 4 step scalars + row, seed, image offset
                 self._params.dev = DeviceArray.zeros((8,), np.float32, "row")
                 self._coeffs = DeviceArray.from_numpy(np.asarray(sampler.coeffs, np.float32), np.float32, "row")
                 self._x0_hist = DeviceArray.zeros(latent.shape, np.float32, "row")
+                if inpaint:
+                    b, _, h, w = latent.shape
+                    self._x0_init = DeviceArray.zeros(latent.shape, np.float32, "row")
+                    self._mask = DeviceArray.from_numpy(np.ones((b, 1, h, w), np.float32), np.float32, "row")
             self._seed, self._image_offset, self._cursor = (0, 0), 0, 0
         sp = self._step_params()
         unet = self.model.diffusion_model
@@ -244,7 +317,11 @@ class StableDiffusion:
             out = unet(x2, sp, self._ctx2, shared=(None, self._emb_cur, self._kv_all))     # (step() has put this timestep's row into _emb_cur)
         else:
             out = unet(x2, sp, self._ctx2)
-        if getattr(self, "_sched", None) is not None:
+        if getattr(self, "_inpaint", False):
+            (hip.tf_cfg_sampler_step_masked_bf16 if config.is_bf16() else hip.tf_cfg_sampler_step_masked_f32)(
+                self._latent.ptr, out.ptr, self._x0_hist.ptr, sp.dev.ptr, self._coeffs.ptr, len(self._sched.timesteps), self._x0_init.ptr, self._mask.ptr,
+                b, c, h, w, _sh())
+        elif getattr(self, "_sched", None) is not None:
             (hip.tf_cfg_sampler_step_bf16 if config.is_bf16() else hip.tf_cfg_sampler_step_f32)(
                 self._latent.ptr, out.ptr, self._x0_hist.ptr, sp.dev.ptr, self._coeffs.ptr, len(self._sched.timesteps), b, c, h, w, _sh())
         else:
@@ -285,24 +362,91 @@ class StableDiffusion:
             raise UnsupportedSamplerConfig(f"StableDiffusion.{what}: compile(..., sampler=<Schedule>) first (this model runs the DDIM step())")
         return self._sched
 
-    def start(self, seed=None, noise=None, image_offset=0):
+    def start(self, seed=None, noise=None, image_offset=0, init_image=None, init_latent=None, mask=None):
         """A new image batch for the compiled sampler: sets the latent in place and rewinds the schedule.  ``seed``: the initial latent is
         drawn on the device (tag 0; image b is global image image_offset + b), and the ancestral noise of every step comes from the same seed
         (tag 1); ``noise``: a host (B,C,H,W) array for the initial latent instead (the ancestral noise then uses ``seed``, default 0).
-        Ordered after every step already queued."""
+        Ordered after every step already queued.
+
+        Image-to-image: ``init_image`` (uint8 (B,H,W,3), encoded by ``encode_image``) or ``init_latent`` (x0, fp32 (B,C,H,W), host or device)
+        sets latent = sqrt(a) x0 + sqrt(1 - a) z at the schedule's start level a = alphas[0] (Sampler.schedule(..., strength=)), z the tag-0
+        noise of ``seed`` -- the noise a text-to-image start from that seed draws.  Inpainting (a model compiled with inpaint=True, which
+        requires an init): ``mask`` -- a latent_mask() input, or a device fp32 (B,1,h,w) array; 1 = repaint -- is written into the model's mask
+        buffer (all ones without one) and x0 into its x0_init buffer."""
         self._require_sampler("start")
+        init = init_image if init_image is not None else init_latent
+        if init_image is not None and init_latent is not None:
+            raise ValueError("StableDiffusion.start: pass init_image= or init_latent=, not both")
+        if init is not None and (noise is not None or seed is None):
+            raise ValueError("StableDiffusion.start: an image-to-image start takes its noise from seed= (and no noise= array)")
         if seed is None and noise is None:
             raise ValueError("StableDiffusion.start: pass seed= (device noise) or noise= (a host array)")
         if int(image_offset) < 0:
             raise ValueError(f"StableDiffusion.start: image_offset must be >= 0, got {image_offset}")
+        inpaint = getattr(self, "_inpaint", False)
+        if mask is not None and not inpaint:
+            raise ValueError("StableDiffusion.start: mask= needs a model compiled with inpaint=True")
+        if inpaint and init is None:
+            raise ValueError("StableDiffusion.start: an inpainting model starts from init_image= or init_latent=")
         self._seed, self._image_offset, self._cursor = _seed_words(0 if seed is None else seed), int(image_offset), 0
-        if noise is not None:
-            return self.set_latent(noise)
-        self.synchronize()
+        if init is None:
+            if noise is not None:
+                return self.set_latent(noise)
+            self.synchronize()
+            b = self._latent.shape[0]
+            with use_stream(self._stream):
+                hip.tf_randn_f32(self._latent.ptr, b, self._latent.size // b, self._seed[0], self._seed[1], self._image_offset, 0, 0, _sh())
+            return self._latent
         b = self._latent.shape[0]
+        lat_mask = None
+        if inpaint:
+            lat_mask = self._mask_for_start(mask)
+        if init_latent is not None and isinstance(init_latent, DeviceArray):
+            if init_latent.shape != self._latent.shape or init_latent.dtype != np.float32 or init_latent.layout != "row":
+                raise ValueError(f"StableDiffusion.start: init_latent must be an fp32 NCHW {self._latent.shape} array, got {init_latent}")
+            hip.tf_stream_sync(_sh())                                  # (made on the caller's stream)
+        elif init_latent is not None:
+            x0h = np.asarray(init_latent)
+            if x0h.shape != self._latent.shape:
+                raise ValueError(f"StableDiffusion.start: init_latent must have the latent's shape {self._latent.shape}, got {x0h.shape}")
+        else:
+            init_image = init_image if isinstance(init_image, DeviceArray) else np.asarray(init_image)
+            ish = tuple(int(v) for v in init_image.shape)
+            if len(ish) != 4 or (ish[0], 4, ish[1] // 8, ish[2] // 8) != self._latent.shape:
+                raise ValueError(f"StableDiffusion.start: init_image {ish} does not encode to the compiled latent {self._latent.shape}")
+        self.synchronize()
         with use_stream(self._stream):
-            hip.tf_randn_f32(self._latent.ptr, b, self._latent.size // b, self._seed[0], self._seed[1], self._image_offset, 0, 0, _sh())
+            if init_image is not None:
+                x0 = self.encode_image(init_image)
+            elif isinstance(init_latent, DeviceArray):
+                x0 = init_latent
+            else:
+                x0 = DeviceArray.from_numpy(np.ascontiguousarray(x0h, dtype=np.float32), np.float32, "row")
+            if inpaint:
+                hip.tf_memcpy_async(self._x0_init.ptr, x0.ptr, x0.nbytes, 3, _sh())
+                if isinstance(lat_mask, DeviceArray):
+                    hip.tf_memcpy_async(self._mask.ptr, lat_mask.ptr, lat_mask.nbytes, 3, _sh())
+                else:
+                    self._mask.copy_from_numpy(lat_mask)
+            hip.tf_noise_to_level_f32(self._latent.ptr, x0.ptr, b, self._latent.size // b, float(self._sched.alphas[0]), self._seed[0], self._seed[1],
+                                      self._image_offset, _sh())
+            self._start_keep = x0                                       # (referenced until the kernels have run)
         return self._latent
+
+    def _mask_for_start(self, mask):
+        """The inpainting mask start() writes: all ones without one; a device fp32 (B,1,h,w) array as it is; anything else through latent_mask."""
+        shape = self._mask.shape
+        if mask is None:
+            return np.ones(shape, np.float32)
+        if isinstance(mask, DeviceArray):
+            if mask.shape != shape or mask.dtype != np.float32 or mask.layout != "row":
+                raise ValueError(f"StableDiffusion.start: a device mask must be fp32 {shape}, got {mask}")
+            hip.tf_stream_sync(_sh())                                  # (made on the caller's stream)
+            return mask
+        m = self.latent_mask(mask)
+        if m.shape != shape:
+            raise ValueError(f"StableDiffusion.start: the mask is {m.shape} at latent size, the compiled latent needs {shape}")
+        return m
 
     def step_sampler(self, i, guidance, eager=False):
         """Step i of the compiled schedule (asynchronous, on the sampler stream): one parameter launch (timestep scalars, schedule row, seed and

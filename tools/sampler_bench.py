@@ -3,7 +3,9 @@
 tf_cfg_sampler_step_f32) against the DDIM step (tf_cfg_ddim_step_f32), 100 graph replays each, alternated over several rounds; and the
 config-3 end-to-end img/s (CLIP x2 -> steps -> VAE decode, batch 1) at 20 DPM++2M steps against 50 DDIM steps.
 
-    python tools/sampler_bench.py [--replays 100] [--rounds 5] [--images 3] [--dpm-steps 20]
+    python tools/sampler_bench.py [--replays 100] [--rounds 5] [--images 3] [--dpm-steps 20] [--inpaint]
+--inpaint adds the masked DPM++2M step (tf_cfg_sampler_step_masked_f32, a model compiled with inpaint=True on the same shape, half the
+latent repainted) to the alternation, and the VAE encoder's time for a 512^2 image (StableDiffusion.encode_image).
 Prints one JSON line."""
 import argparse
 import contextlib
@@ -25,6 +27,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--images", type=int, default=3)
     ap.add_argument("--dpm-steps", type=int, default=20)
+    ap.add_argument("--inpaint", action="store_true", help="also time the masked step against the unmasked one, and the VAE encoder")
     args = ap.parse_args()
 
     import torch  # noqa: F401  (the weight arena is a torch allocation)
@@ -56,6 +59,13 @@ def main():
     lat_a, lat_b = ddim_m.latent_from_numpy(noise), dpm_m.latent_from_numpy(noise)
     ddim_m.compile(unc, ctx, lat_a, timesteps=ddim_sched.timesteps)                 # the DDIM step() path, exactly as bench.py captures it
     dpm_m.compile(unc, ctx, lat_b, sampler=dpm_sched)
+    if args.inpaint:
+        inp_m = StableDiffusion()
+        update_state(inp_m.model.diffusion_model, state, "")
+        lat_c = inp_m.latent_from_numpy(noise)
+        inp_m.compile(unc, ctx, lat_c, sampler=dpm_sched, inpaint=True)
+        half = np.zeros((1, 1, 64, 64), np.float32); half[..., :32] = 1.0
+        inp_m.start(seed=1234, init_latent=0.5 * noise, mask=half)
     lat0 = T.DeviceArray.from_numpy(noise, np.float32, "row")
     ts, al, ap_ = ddim_sched.timesteps, ddim_sched.alphas, ddim_sched.alphas_prev
 
@@ -74,6 +84,14 @@ def main():
                 hip.tf_memcpy_async(lat_b.ptr, lat0.ptr, lat_b.nbytes, 3, dpm_m._stream.handle)
             dpm_m.step_sampler(i, 7.5)
 
+    def inp_replays(n):
+        k = len(dpm_sched.timesteps)
+        for s in range(n):
+            i = s % k
+            if i == 0:
+                hip.tf_memcpy_async(lat_c.ptr, lat0.ptr, lat_c.nbytes, 3, inp_m._stream.handle)
+            inp_m.step_sampler(i, 7.5)
+
     def timed(model, fn, n):
         ev0, ev1, ms = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_float()
         hip.tf_event_create(ctypes.byref(ev0)); hip.tf_event_create(ctypes.byref(ev1))
@@ -88,10 +106,27 @@ def main():
 
     ddim_replays(20); dpm_replays(20)
     step_ms = {"ddim": [], "dpmpp2m": []}
+    if args.inpaint:
+        inp_replays(20)
+        step_ms["dpmpp2m_masked"] = []
     for _ in range(args.rounds):
         step_ms["ddim"].append(timed(ddim_m, ddim_replays, args.replays))
         step_ms["dpmpp2m"].append(timed(dpm_m, dpm_replays, args.replays))
+        if args.inpaint:
+            step_ms["dpmpp2m_masked"].append(timed(inp_m, inp_replays, args.replays))
     med = {k: float(np.median(v)) for k, v in step_ms.items()}
+    extra = {}
+    if args.inpaint:
+        img = np.random.default_rng(0).integers(0, 256, (1, 512, 512, 3), dtype=np.uint8)
+        enc = []
+        with T.use_stream(ddim_m._stream):                                 # (the model whose first_stage_model holds weights)
+            for r in range(args.rounds + 1):
+                t0 = time.perf_counter()
+                ddim_m.encode_image(img)
+                ddim_m.synchronize()
+                enc.append(time.perf_counter() - t0)                     # (includes the 0.75 MB host -> device upload of the image)
+        extra = {"dpmpp2m_masked_step_ms": round(med["dpmpp2m_masked"], 4), "masked_over_unmasked": round(med["dpmpp2m_masked"] / med["dpmpp2m"], 4),
+                 "encode_512_ms": round(1e3 * float(np.median(enc[1:])), 3)}
 
     def e2e(model, steps, sample):
         recs = []
@@ -122,7 +157,7 @@ def main():
         dpm_m.run(7.5)
 
     out = {"metric": "sd15_sampler_step_ms", "ddim_step_ms": round(med["ddim"], 4), "dpmpp2m_step_ms": round(med["dpmpp2m"], 4),
-           "dpmpp2m_over_ddim": round(med["dpmpp2m"] / med["ddim"], 4), "replays": args.replays, "rounds": args.rounds,
+           "dpmpp2m_over_ddim": round(med["dpmpp2m"] / med["ddim"], 4), **extra, "replays": args.replays, "rounds": args.rounds,
            "step_ms_per_round": {k: [round(x, 4) for x in v] for k, v in step_ms.items()},
            "e2e_ddim50": e2e(ddim_m, 50, ddim_sample), "e2e_dpmpp2m": e2e(dpm_m, len(dpm_sched.timesteps), dpm_sample)}
     out["e2e_speedup"] = round(out["e2e_dpmpp2m"]["img_per_s"] / out["e2e_ddim50"]["img_per_s"], 3)
