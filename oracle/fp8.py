@@ -79,7 +79,7 @@ MIN_K = 640            # tinyfusers_amd/ff/fp8.py::MIN_K
 
 
 def mx_gemm_supported(M, N, K, act=0, out_mx=False, howo=None, c_parts=None):
-    """Restatement of the host rule (csrc/gemm.hip: mx_shape_ok / pp_ok): the block-scaled GEMM is the 192- / 256-row ping-pong kernel and is
+    """Restatement of the host rule (csrc/gemm.hip: mx_shape_ok; csrc/gemm_family.h: pp_ok): the block-scaled GEMM is the 192- / 256-row ping-pong kernel and is
     offered where one of its tiles gives the launch at least 128 blocks.  N = output width (GEGLU: the width AFTER the gate), howo = pixels
     per image of a convolution that carries a time-embedding bias (its tile must not span more than two images), c_parts = channel counts of
     the sources (a count off the 128 grid excludes the 256 x 160 tile)."""
