@@ -368,7 +368,7 @@ int tf_group_norm_bf16(void* y, const void* x, const void* x2, const void* gamma
 int tf_layer_norm_bf16(void* y, const void* x, const void* gamma, const void* beta, int rows, int C, float eps, tfStream_t s);
 /* y(M,N) = x(M,K) . w(N,K)^T + bias(N) + residual(M,N)   (ff/linear.py:112-121) */
 int tf_linear_bf16(void* y, const void* x, const void* w, const void* bias, const void* residual, int M, int N, int K, tfStream_t s);
-/* tf_conv2d_f16's arguments without the workspace (vision/conv2d.py:9-28): NHWC x (+ concat x2), w (Cout, R, S, C1 + C2) */
+/* tf_conv2d_bf16 (its prototype closes this block): tf_conv2d_f16's arguments without the workspace (vision/conv2d.py:9-28): NHWC x (+ concat x2), w (Cout, R, S, C1 + C2) */
 /* the bfloat16 STEP (round 4: config.set_dtype("bf16"), bench.py --dtype bf16): the sampler on bfloat16 tensors throughout -- conv / linear /
  * GEGLU on the bf16 MFMA (tf_conv2d_bf16, tf_linear_act_bf16), GroupNorm / LayerNorm / SiLU in bfloat16, the time-embedding chain, CFG duplicate
  * and the CFG + DDIM update reading bfloat16 (vision/unet.py:51-97, variants/sd.py:14-46); since round 5 the step runs on the dtype-tagged fused

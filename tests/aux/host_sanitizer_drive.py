@@ -141,6 +141,18 @@ if nogpu:
     ok(rc != 0, "conv without a GPU")
     ok(lib.tf_sdpa_f16(P, P, P, P, 2, 8, 4096, 4096, 40, *([40 * 4096 * 8, 40 * 4096, 40] * 4), 0, None) != 0, "sdpa without a GPU")
     ok(lib.tf_layer_norm_f16(P, P, P, P, 64, 320, 1e-5, None) != 0, "layer norm without a GPU")
+# ---- the corpus of conv / linear entry calls that tests/test_abi.py compares with the golden answers: here only through the sanitizers (the
+# well-formed ones carry placeholder pointers: without a device only)
+import json
+ok(lib.tf_gemm_autotune(2) == 0, "table only: a shape without a row is a status, not a tuning run")
+for case in json.load(open(os.path.join(ROOT, "tests", "golden", "gemm_entry_trace.json")))["cases"]:
+    if case["device"] and not nogpu:
+        continue
+    outs = [ctypes.c_int(0) for a in case["args"] if a == "I"]
+    it = iter(outs)
+    ret = getattr(lib, case["fn"])(*[P if a == "P" else ctypes.byref(next(it)) if a == "I" else a for a in case["args"]])
+    ok(ret == case["expect"]["ret"], f"{case['fn']}{case['args']} -> {ret}")
+ok(lib.tf_gemm_autotune(1) == 0, "back to the default mode")
 # ---- run-time compilation and the communicator: argument handling (the libraries are opened on first use)
 fn = ctypes.c_void_p()
 ok(lib.tf_rtc_load(None, b"x", b"f") != 0 and lib.tf_rtc_load(ctypes.byref(fn), None, b"f") != 0 and lib.tf_rtc_load(ctypes.byref(fn), b"x", None) != 0, "rtc nulls")

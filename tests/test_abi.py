@@ -1,6 +1,7 @@
 """CPU checks of the drop-in boundary: the C-ABI library loads without a GPU and exports every symbol that
 include/tinyfusers_hip.h declares; argument validation and the status -> RuntimeError convention work."""
 import ctypes
+import json
 import os
 import re
 
@@ -48,6 +49,60 @@ def test_status_convention_without_gpu(native):
     assert b"null tensor" in native.lib.tf_last_error()
     assert native.lib.tf_sdpa_f16(*([ctypes.c_void_p(8)] * 4), 1, 1, 4, 4, 12, *([8] * 12), 0, None) == 10001   # HS % 8
     assert native.lib.tf_version() >= 100
+
+
+GEMM_ENTRY_TRACE = os.path.join(ROOT, "tests", "golden", "gemm_entry_trace.json")
+
+
+def _replay_gemm_entry(lib, case, trace_path):
+    """One call of the corpus: "P" is a non-null placeholder pointer (nothing dereferences it on the host), None is NULL, "I" an int the entry may
+    write.  What the call shows without a device: its return value, the shape key it looked up (none when it returned first), the values left in
+    its int out-arguments and, for TF_E_INVALID_VALUE, the entry name its message begins with."""
+    outs = []
+
+    def arg(a):
+        if a == "P":
+            return ctypes.c_void_p(4096)
+        if a == "I":
+            outs.append(ctypes.c_int(-7))
+            return ctypes.byref(outs[-1])
+        return a
+    args = [arg(a) for a in case["args"]]
+    assert lib.tf_gemm_tune_trace(1) == 0                  # (switching the trace on forgets the keys of the call before)
+    ret = getattr(lib, case["fn"])(*args)
+    assert lib.tf_gemm_tune_trace_dump(trace_path.encode()) == 0
+    keys = [[int(v) for v in line.split()[:10]] for line in open(trace_path)]
+    assert len(keys) <= 1, keys
+    return {"ret": ret, "key": keys[0] if keys else None, "who": lib.tf_last_error().decode().split(":")[0] if ret == 10001 else None,
+            "outs": [o.value for o in outs]}
+
+
+def _replay_gemm_entries(native, cases, trace_path, with_placeholders):
+    import sys
+    mode = sys.modules["tinyfusers_amd.native.hip"]._mode
+    try:
+        assert native.lib.tf_gemm_autotune(2) == 0         # table only: a launch looks its key up and never tunes
+        return [_replay_gemm_entry(native.lib, c, trace_path) if with_placeholders or not c["device"] else None for c in cases]
+    finally:
+        native.lib.tf_gemm_tune_trace(0)
+        native.lib.tf_gemm_autotune(int(mode) if mode else 1)
+
+
+def test_entries_describe_the_same_gemm_problems(native, tmp_path):
+    """Which problem each conv / linear entry describes to the dispatcher: tests/golden/gemm_entry_trace.json holds a corpus of entry calls and,
+    per call, what the library of the commit before the launch descriptors got their builders answered (python tests/test_abi.py records it).
+    resolve() looks the shape key up before anything touches a device, so a well-formed call with placeholder pointers leaves its key in the
+    trace and returns a status (not in the table, or no device); those calls ("device": true) run only where no GPU is visible.  The rejected
+    calls and the host-only predicates return before any device work and run everywhere."""
+    n = ctypes.c_int(-1)
+    have_gpu = native.lib.tf_device_count(ctypes.byref(n)) == 0 and n.value > 0
+    cases = json.load(open(GEMM_ENTRY_TRACE))["cases"]
+    assert all(c["device"] or c["expect"]["key"] is None for c in cases)      # what runs next to a GPU never got as far as a launch
+    got = _replay_gemm_entries(native, cases, str(tmp_path / "trace.txt"), not have_gpu)
+    for i, (c, g) in enumerate(zip(cases, got)):
+        assert g is None or g == c["expect"], (i, c["fn"], c["args"], g, c["expect"])
+    if have_gpu:
+        pytest.skip("a GPU is visible: the placeholder-pointer calls were not replayed (the rejected calls and predicates passed)")
 
 
 def test_no_cpu_fallback(native, monkeypatch):
@@ -104,3 +159,20 @@ def test_host_code_is_clean_under_asan_ubsan():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "aux", "host_sanitizer_drive.py")], env=b.sanitizer_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "HOST_SANITIZER_OK" in r.stdout, (r.stdout[-1500:], r.stderr[-4000:])
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error:" not in r.stderr, r.stderr[-4000:]
+
+
+if __name__ == "__main__":       # record mode: answer every call of the corpus with the library in the tree and write the answers back
+    import sys
+    import tempfile
+    sys.path.insert(0, ROOT)
+    import __graft_entry__
+    __graft_entry__.build()
+    import tinyfusers_amd.native as _native
+    _n = ctypes.c_int(-1)
+    assert not (_native.lib.tf_device_count(ctypes.byref(_n)) == 0 and _n.value > 0), "record where no GPU is visible"
+    _fx = json.load(open(GEMM_ENTRY_TRACE))
+    with tempfile.TemporaryDirectory() as _d:
+        for _c, _g in zip(_fx["cases"], _replay_gemm_entries(_native, _fx["cases"], os.path.join(_d, "trace.txt"), True)):
+            _c["expect"] = _g
+    with open(GEMM_ENTRY_TRACE, "w") as _f:
+        _f.write('{"cases": [\n' + ",\n".join(json.dumps(_c) for _c in _fx["cases"]) + "\n]}\n")

@@ -12,7 +12,7 @@ import numpy as np
 from .. import config
 from ..ff.group_norm import GroupNorm
 from ..ff.layer_norm import LayerNorm
-from ..ff.linear import Linear, fold_layer_norm, linear_any, linear_f16, linear_ln_f16
+from ..ff.linear import Linear, fold_layer_norm, linear_f16, linear_ln_f16
 from ..ff.nn import FeedForward
 from ..native import hip
 from ..storage.tensor import DeviceArray, _sh, is_bfloat16
@@ -96,7 +96,7 @@ class CrossAttention:
 
     def project_kv(self, context):
         """(b, tk, 2C) fused K|V projection of the context (computed once per UNet call by the model)."""
-        return linear_any(context, self._fused_weights(False))
+        return linear_f16(context, self._fused_weights(False))
 
     def __call__(self, x, context=None, residual=None, kv=None, ln=None):
         """ln: a LayerNorm to apply to x first, folded into the q (or q|k|v) projection (x is then the RAW input)."""
@@ -118,7 +118,7 @@ class CrossAttention:
             elif ln is not None:
                 qkv = linear_ln_f16(x, self._folded(ln, True), ln.eps)
             else:
-                qkv = linear_any(x, self._fused_weights(True))        # (b, t, 3C): q | k | v
+                qkv = linear_f16(x, self._fused_weights(True))        # (b, t, 3C): q | k | v
             q, k, v = qkv, qkv.view((b, t, 3 * c), "row", c), qkv.view((b, t, 3 * c), "row", 2 * c)
             tk, qs, ks = t, (t * 3 * c, hs, 3 * c), (t * 3 * c, hs, 3 * c)
         else:
@@ -126,7 +126,7 @@ class CrossAttention:
                 w8, wsc = fp8.pack_weight(self.to_q.weight, self._cache8["q"])
                 q = fp8.linear_mx(x8, w8, wsc, None)
             else:
-                q = linear_ln_f16(x, self._folded(ln, False), ln.eps) if ln is not None else linear_any(x, self.to_q.weight)
+                q = linear_ln_f16(x, self._folded(ln, False), ln.eps) if ln is not None else linear_f16(x, self.to_q.weight)
             if kv is None:
                 kv = self.project_kv(context)
             if hasattr(kv, "ld"):                          # column slice of the UNet's step-level K|V GEMM

@@ -297,79 +297,133 @@ int tf_gemm_splitk_partials(int bits) {
 }
 int tf_gemm_force_config(int bm, int bn, int splitk) { g_force_bm = bm; g_force_bn = bn; g_force_split = splitk; return TF_OK; }
 
-static int conv_geometry(int H, int W, int R, int S, int stride, int pad, int ups, int* Ho, int* Wo) {
-  int Hl = H << ups, Wl = W << ups;
-  *Ho = (Hl + 2 * pad - R) / stride + 1;
-  *Wo = (Wl + 2 * pad - S) / stride + 1;
-  return (*Ho > 0 && *Wo > 0) ? 0 : 1;
+// ---- launch descriptors: a conv / linear entry gets its GemmP from one of the two builders below (linear_problem, conv_problem) and then sets
+// the fields that are its own.  The host-only predicates and the *_workspace sizes go through the same geometry (linear_shape, conv_shape).
+enum Elem { EL_16, EL_E4M3, EL_MX };   // what x / x2 / w hold: 16-bit elements (GemmP::bf16 says which), e4m3 with one scale per weight row, e4m3 with block-scaled activations
+static long long elem_bytes(Elem e, long long n) { return e == EL_16 ? 2 * n : n; }
+static bool under_2gib(Elem e, long long bytes) { return bytes + (e == EL_MX ? bytes / 32 : 0) < (1LL << 31); }   // (a block-scaled tensor carries its scale bytes behind its codes)
+
+// a Linear is a 1x1 conv over an M x 1 image; N = the output width (the weight has twice as many rows for GEGLU)
+static void linear_shape(GemmP& p, Elem e, int M, int N, int K, int act) {
+  p = {};
+  p.fp8 = e != EL_16; p.mx = e == EL_MX;
+  p.M = M; p.N = act == 1 ? 2 * N : N; p.K = K; p.Kc = K; p.C1 = K; p.C2 = 0; p.C = K;
+  p.H = 1; p.W = M; p.Ho = 1; p.Wo = M; p.HoWo = M; p.S = 1; p.stride = 1; p.pad = 0; p.ups = 0; p.act = act;
+}
+// The checks every linear entry makes, under the name `fn` it makes them with, and its descriptor.  M == 0 is TF_OK with nothing to launch: the
+// caller returns `if (rc || M == 0)`.  K is a multiple of 8 for 16-bit operands and of 64 for e4m3.
+static int linear_problem(GemmP& p, const char* fn, Elem e, void* y, const void* x, const void* w, const void* bias, const void* residual, int M, int N, int K, int act) {
+  const int kq = e == EL_16 ? 8 : 64;
+  TF_REQUIRE(y && x && w, "%s: null tensor", fn);
+  TF_REQUIRE(M >= 0 && N >= 1 && K >= kq && K % kq == 0, "%s: K=%d must be a positive multiple of %d", fn, K, kq);
+  TF_REQUIRE(act == 0 || act == 1, "%s: act=%d", fn, act);
+  TF_REQUIRE(act == 0 || (bias && N % 16 == 0), "%s: GEGLU needs a bias and N %% 16 == 0 (N=%d)", fn, N);
+  if (M == 0) return TF_OK;
+  linear_shape(p, e, M, N, K, act);
+  p.x = (const half_t*)x; p.w = (const half_t*)w; p.y = (half_t*)y; p.bias = (const half_t*)bias; p.residual = (const half_t*)residual;
+  const long long xb = elem_bytes(e, (long long)M * K), wb = elem_bytes(e, (long long)p.N * K);
+  TF_REQUIRE(under_2gib(e, xb) && wb < (1LL << 31), "%s: tensors must be < 2 GiB each", fn);
+  p.x_bytes = p.x2_bytes = p.x3_bytes = p.x4_bytes = (unsigned)xb; p.w_bytes = (unsigned)wb;   // (a source that is not there has the size of x)
+  return TF_OK;
+}
+
+struct ConvShape { int N, H, W, C1, C2, Cout, R, S, stride, pad, upsample, C3, C4; };
+// the implicit GEMM of a conv: M = output pixels, K = the R*S taps of the concat (x | x2), then the channels of the extra 1x1 sources x3 | x4.
+// 0 = filled, 1 = no output pixel (or no stride), 2 = M or K beyond 32-bit indexing
+static int conv_shape(GemmP& p, Elem e, const ConvShape& g) {
+  p = {};
+  if (g.stride < 1) return 1;
+  const int ups = g.upsample ? 1 : 0;
+  const int Ho = ((g.H << ups) + 2 * g.pad - g.R) / g.stride + 1, Wo = ((g.W << ups) + 2 * g.pad - g.S) / g.stride + 1;
+  if (Ho <= 0 || Wo <= 0) return 1;
+  if ((long long)g.N * Ho * Wo >= (1LL << 31) || (long long)g.R * g.S * (g.C1 + g.C2) >= (1LL << 31)) return 2;
+  p.fp8 = e != EL_16; p.mx = e == EL_MX;
+  p.M = g.N * Ho * Wo; p.N = g.Cout; p.C1 = g.C1; p.C2 = g.C2; p.C = g.C1 + g.C2; p.Kc = g.R * g.S * p.C; p.K = p.Kc + g.C3 + g.C4; p.C3 = g.C3; p.C4 = g.C4;
+  p.H = g.H; p.W = g.W; p.Ho = Ho; p.Wo = Wo; p.HoWo = Ho * Wo; p.S = g.S; p.stride = g.stride; p.pad = g.pad; p.ups = ups; p.act = 0;
+  return 0;
+}
+// The checks every conv entry makes and its descriptor; N == 0 is TF_OK with nothing to launch: the caller returns `if (rc || N == 0)`.  `fn` is
+// tf_conv2d_f16 for every 16-bit entry (the messages about the extra sources say tf_conv2d_fused_f16, the entry that introduced them); channel
+// counts are multiples of 8 for 16-bit operands and of 64 for e4m3.
+static int conv_problem(GemmP& p, const char* fn, Elem e, const ConvShape& g, void* y, const void* x, const void* x2, const void* x3, const void* x4, const void* w,
+                        const void* bias, const void* bias_nc, long long bias_nc_stride, const void* residual) {
+  const int cq = e == EL_16 ? 8 : 64;
+  TF_REQUIRE(g.C3 >= 0 && g.C4 >= 0 && (g.C3 == 0 || x3) && (g.C4 == 0 || (x4 && g.C3 > 0)) && g.C3 % 8 == 0 && g.C4 % 8 == 0,
+             "tf_conv2d_fused_f16: extra sources C3=%d C4=%d must be multiples of 8 with their tensors given (x4 needs x3)", g.C3, g.C4);
+  TF_REQUIRE(g.C3 == 0 || g.upsample == 0, "tf_conv2d_fused_f16: the extra 1x1 sources cannot be combined with upsample");
+  TF_REQUIRE(y && x && w, "%s: null tensor", fn);
+  TF_REQUIRE(g.C1 > 0 && g.C2 >= 0 && (g.C2 == 0 || x2), "%s: C1=%d C2=%d x2=%p", fn, g.C1, g.C2, x2);
+  TF_REQUIRE(g.C1 % cq == 0 && g.C2 % cq == 0, "%s: channel counts must be multiples of %d (C1=%d C2=%d)%s", fn, cq, g.C1, g.C2, e == EL_16 ? "; use tf_im2col_nhwc_f16 for tiny C" : "");
+  TF_REQUIRE(g.R >= 1 && g.S >= 1 && g.stride >= 1 && g.pad >= 0 && g.Cout >= 1 && g.N >= 0, "%s: bad geometry R=%d S=%d stride=%d pad=%d", fn, g.R, g.S, g.stride, g.pad);
+  const int bad = conv_shape(p, e, g);
+  TF_REQUIRE(bad != 1, "%s: empty output for H=%d W=%d", fn, g.H, g.W);
+  if (g.N == 0) return TF_OK;
+  TF_REQUIRE(bad != 2, "%s: problem too large for 32-bit indexing", fn);
+  TF_REQUIRE(bias_nc_stride % 4 == 0 || g.Cout % 4 != 0, "%s: bias_nc_stride must be a multiple of 4", fn);
+  p.x = (const half_t*)x; p.x2 = (const half_t*)x2; p.x3 = (const half_t*)x3; p.x4 = (const half_t*)x4; p.w = (const half_t*)w; p.y = (half_t*)y;
+  p.bias = (const half_t*)bias; p.bias_nc = (const half_t*)bias_nc; p.residual = (const half_t*)residual; p.bias_nc_stride = bias_nc_stride;
+  const long long px = (long long)g.N * g.H * g.W, xb = elem_bytes(e, px * g.C1), x2b = elem_bytes(e, px * g.C2), wb = elem_bytes(e, (long long)g.Cout * p.K);
+  const long long x3b = elem_bytes(e, px * g.C3), x4b = elem_bytes(e, px * g.C4);
+  TF_REQUIRE(under_2gib(e, xb) && under_2gib(e, x2b) && wb < (1LL << 31), "%s: tensors must be < 2 GiB each", fn);
+  TF_REQUIRE(x3b < (1LL << 31) && x4b < (1LL << 31), "tf_conv2d_fused_f16: tensors must be < 2 GiB each");
+  p.x_bytes = (unsigned)xb; p.w_bytes = (unsigned)wb;                                          // (of a block-scaled tensor: the codes; the scale bytes sit behind them)
+  // a source that is not there has the size of x
+  p.x2_bytes = g.C2 ? (unsigned)x2b : (unsigned)xb; p.x3_bytes = g.C3 ? (unsigned)x3b : (unsigned)xb; p.x4_bytes = g.C4 ? (unsigned)x4b : (unsigned)xb;
+  return TF_OK;
+}
+// GroupNorm statistics of the output, where the caller gave a buffer for them: requested only for a group width the epilogue can fold (a group
+// spans at most two n-tiles, one lane per group of a tile); anything else simply reports chunks = 0 and the caller runs tf_group_norm_f16 as usual
+static int conv_output_stats(GemmP& p, const char* fn, int N, void* gn_partial, size_t gn_partial_bytes, int gn_groups) {
+  if (!gn_partial) return TF_OK;
+  TF_REQUIRE(gn_groups >= 1 && p.N % gn_groups == 0, "%s: Cout=%d not divisible by groups=%d", fn, p.N, gn_groups);
+  TF_REQUIRE(gn_partial_bytes >= tf_conv2d_gn_partial_bytes(N, gn_groups), "%s: statistics buffer too small (%zu bytes)", fn, gn_partial_bytes);
+  const int cpg = p.N / gn_groups;
+  if (cpg >= 4 && cpg <= 64 && p.N % 8 == 0 && p.N <= 4096 && gn_groups <= 256) { p.gn_part = (float*)gn_partial; p.gn_G = gn_groups; p.gn_cpg = cpg; }
+  return TF_OK;
+}
+static int run_forced(const GemmP& p, void* workspace, size_t workspace_bytes, tfStream_t s, int* gn_chunks = nullptr) {   // run_gemm under tf_gemm_force_config
+  return run_gemm(p, workspace, workspace_bytes, g_force_bm, g_force_bn, g_force_split, tf_hs(s), gn_chunks);
 }
 
 size_t tf_conv2d_gn_partial_bytes(int N, int groups) { return (size_t)(N > 0 ? N : 0) * TF_GN_MAX_CHUNKS * (groups > 0 ? groups : 0) * 2 * sizeof(float); }
 
-size_t tf_conv2d_workspace(int N, int H, int W, int C1, int C2, int Cout, int R, int S, int stride, int pad, int upsample) {
-  int Ho, Wo;
-  if (stride < 1 || conv_geometry(H, W, R, S, stride, pad, upsample ? 1 : 0, &Ho, &Wo)) return 0;
-  return gemm_workspace(N * Ho * Wo, Cout, R * S * (C1 + C2), 0);
+size_t tf_conv2d_fused_workspace(int N, int H, int W, int C1, int C2, int Cout, int R, int S, int stride, int pad, int upsample, int C3, int C4) {
+  GemmP p;
+  return conv_shape(p, EL_16, {N, H, W, C1, C2, Cout, R, S, stride, pad, upsample, C3, C4}) ? 0 : gemm_workspace(p.M, p.N, p.K, 0);
 }
-
-static int conv2d_impl(void* y, const void* x, const void* x2, const void* w, const void* bias, const void* bias_nc, long long bias_nc_stride,
-                       const void* residual, int N, int H, int W, int C1, int C2, int Cout, int R, int S, int stride, int pad, int upsample,
-                       void* workspace, size_t workspace_bytes, float* gn_partial, size_t gn_partial_bytes, int gn_groups, int* gn_chunks,
-                       const void* x3, const void* x4, int C3, int C4, tfStream_t s, const GemmP* gi = nullptr) {
-  if (gn_chunks) *gn_chunks = 0;
-  TF_REQUIRE(C3 >= 0 && C4 >= 0 && (C3 == 0 || x3) && (C4 == 0 || (x4 && C3 > 0)) && C3 % 8 == 0 && C4 % 8 == 0,
-             "tf_conv2d_fused_f16: extra sources C3=%d C4=%d must be multiples of 8 with their tensors given (x4 needs x3)", C3, C4);
-  TF_REQUIRE(C3 == 0 || upsample == 0, "tf_conv2d_fused_f16: the extra 1x1 sources cannot be combined with upsample");
-  TF_REQUIRE(y && x && w, "tf_conv2d_f16: null tensor");
-  TF_REQUIRE(C1 > 0 && C2 >= 0 && (C2 == 0 || x2), "tf_conv2d_f16: C1=%d C2=%d x2=%p", C1, C2, x2);
-  TF_REQUIRE(C1 % 8 == 0 && C2 % 8 == 0, "tf_conv2d_f16: channel counts must be multiples of 8 (C1=%d C2=%d); use tf_im2col_nhwc_f16 for tiny C", C1, C2);
-  TF_REQUIRE(R >= 1 && S >= 1 && stride >= 1 && pad >= 0 && Cout >= 1 && N >= 0, "tf_conv2d_f16: bad geometry R=%d S=%d stride=%d pad=%d", R, S, stride, pad);
-  int ups = upsample ? 1 : 0, Ho, Wo;
-  TF_REQUIRE(!conv_geometry(H, W, R, S, stride, pad, ups, &Ho, &Wo), "tf_conv2d_f16: empty output for H=%d W=%d", H, W);
-  if (N == 0) return TF_OK;
-  TF_REQUIRE((long long)N * Ho * Wo < (1LL << 31) && (long long)R * S * (C1 + C2) < (1LL << 31), "tf_conv2d_f16: problem too large for 32-bit indexing");
-  GemmP p = {};
-  p.x = (const half_t*)x; p.x2 = (const half_t*)x2; p.w = (const half_t*)w; p.y = (half_t*)y;
-  p.bias = (const half_t*)bias; p.bias_nc = (const half_t*)bias_nc; p.residual = (const half_t*)residual;
-  p.bias_nc_stride = bias_nc_stride;
-  TF_REQUIRE(bias_nc_stride % 4 == 0 || Cout % 4 != 0, "tf_conv2d_f16: bias_nc_stride must be a multiple of 4");
-  p.M = N * Ho * Wo; p.N = Cout; p.C1 = C1; p.C2 = C2; p.C = C1 + C2; p.Kc = R * S * p.C; p.K = p.Kc + C3 + C4;
-  p.x3 = (const half_t*)x3; p.x4 = (const half_t*)x4; p.C3 = C3; p.C4 = C4;
-  p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo; p.HoWo = Ho * Wo; p.S = S; p.stride = stride; p.pad = pad; p.ups = ups; p.act = 0;
-  {
-    long long xb = (long long)N * H * W * C1 * 2, x2b = (long long)N * H * W * C2 * 2, wb = (long long)Cout * p.K * 2;
-    TF_REQUIRE(xb < (1LL << 31) && x2b < (1LL << 31) && wb < (1LL << 31), "tf_conv2d_f16: tensors must be < 2 GiB each");
-    p.x_bytes = (unsigned)xb; p.x2_bytes = C2 ? (unsigned)x2b : (unsigned)xb; p.w_bytes = (unsigned)wb;
-    long long x3b = (long long)N * H * W * C3 * 2, x4b = (long long)N * H * W * C4 * 2;
-    TF_REQUIRE(x3b < (1LL << 31) && x4b < (1LL << 31), "tf_conv2d_fused_f16: tensors must be < 2 GiB each");
-    p.x3_bytes = C3 ? (unsigned)x3b : (unsigned)xb; p.x4_bytes = C4 ? (unsigned)x4b : (unsigned)xb;
-  }
-  if (gn_partial) {
-    TF_REQUIRE(gn_chunks, "tf_conv2d_fused_f16: gn_chunks must not be NULL");
-    TF_REQUIRE(gn_groups >= 1 && Cout % gn_groups == 0, "tf_conv2d_fused_f16: Cout=%d not divisible by groups=%d", Cout, gn_groups);
-    TF_REQUIRE(gn_partial_bytes >= tf_conv2d_gn_partial_bytes(N, gn_groups), "tf_conv2d_fused_f16: statistics buffer too small (%zu bytes)", gn_partial_bytes);
-    int cpg = Cout / gn_groups;
-    // group width the epilogue can fold (a group spans at most two n-tiles, one lane per group of a tile); anything else
-    // simply reports chunks = 0 and the caller runs tf_group_norm_f16 as usual
-    if (cpg >= 4 && cpg <= 64 && Cout % 8 == 0 && Cout <= 4096 && gn_groups <= 256) {
-      p.gn_part = gn_partial; p.gn_G = gn_groups; p.gn_cpg = cpg;
-    }
-  }
-  if (gi && gi->bf16) p.bf16 = 1;
-  if (gi && gi->on_z && p.gn_part) {                       // (groups the epilogue cannot fold: no statistics, no apply -- *z_written stays 0)
-    p.on_z = gi->on_z; p.on_gamma = gi->on_gamma; p.on_beta = gi->on_beta; p.on_eps = gi->on_eps; p.on_silu = gi->on_silu; p.on_applied = gi->on_applied;
-  }
-  if (gi && gi->gi_part) {
-    p.gi_part = gi->gi_part; p.gi_part2 = gi->gi_part2; p.gi_gamma = gi->gi_gamma; p.gi_beta = gi->gi_beta;
-    p.gi_chunks = gi->gi_chunks; p.gi_chunks2 = gi->gi_chunks2; p.gi_G = gi->gi_G; p.gi_G1 = gi->gi_G1; p.gi_G2 = gi->gi_G2; p.gi_mr = gi->gi_mr;
-    p.gi_silu = gi->gi_silu; p.gi_eps = gi->gi_eps;
-    p.ktiles = (p.K + 63) / 64;
-    if (!gi_any_ok(p)) { tf_set_error("tf_conv2d_gn_f16: this geometry cannot carry the input GroupNorm (ask tf_conv2d_gn_supported first)"); return TF_E_UNSUPPORTED; }
-  }
-  return run_gemm(p, workspace, workspace_bytes, g_force_bm, g_force_bn, g_force_split, tf_hs(s), gn_chunks);
+size_t tf_conv2d_workspace(int N, int H, int W, int C1, int C2, int Cout, int R, int S, int stride, int pad, int upsample) {
+  return tf_conv2d_fused_workspace(N, H, W, C1, C2, Cout, R, S, stride, pad, upsample, 0, 0);
 }
 
 #define TF_REQUIRE_DTYPE(fn) TF_REQUIRE(dtype == TF_DTYPE_F16 || dtype == TF_DTYPE_BF16, fn ": dtype=%d (0 = float16, 1 = bfloat16)", dtype)
+int tf_conv2d_fused_16(int dtype, void* y, const void* x, const void* x2, const void* w, const void* bias, const void* bias_nc, long long bias_nc_stride,
+                       const void* residual, int N, int H, int W, int C1, int C2, int Cout, int R, int S, int stride, int pad, int upsample,
+                       void* workspace, size_t workspace_bytes, const void* x3, const void* x4, int C3, int C4, void* gn_partial,
+                       size_t gn_partial_bytes, int gn_groups, int* gn_chunks, tfStream_t s) {
+  TF_REQUIRE_DTYPE("tf_conv2d_fused_16");
+  TF_REQUIRE(!gn_partial || gn_chunks, "tf_conv2d_fused_f16: gn_chunks must be given with gn_partial");
+  if (gn_chunks) *gn_chunks = 0;
+  GemmP p;
+  int rc = conv_problem(p, "tf_conv2d_f16", EL_16, {N, H, W, C1, C2, Cout, R, S, stride, pad, upsample, C3, C4}, y, x, x2, x3, x4, w, bias, bias_nc, bias_nc_stride, residual);
+  if (rc || N == 0) return rc;
+  p.bf16 = dtype == TF_DTYPE_BF16;
+  if ((rc = conv_output_stats(p, "tf_conv2d_fused_f16", N, gn_partial, gn_partial_bytes, gn_groups))) return rc;
+  return run_forced(p, workspace, workspace_bytes, s, gn_chunks);
+}
+int tf_conv2d_fused_f16(void* y, const void* x, const void* x2, const void* w, const void* bias, const void* bias_nc, long long bias_nc_stride,
+                        const void* residual, int N, int H, int W, int C1, int C2, int Cout, int R, int S, int stride, int pad, int upsample,
+                        void* workspace, size_t workspace_bytes, const void* x3, const void* x4, int C3, int C4, void* gn_partial,
+                        size_t gn_partial_bytes, int gn_groups, int* gn_chunks, tfStream_t s) {
+  return tf_conv2d_fused_16(TF_DTYPE_F16, y, x, x2, w, bias, bias_nc, bias_nc_stride, residual, N, H, W, C1, C2, Cout, R, S, stride, pad, upsample, workspace, workspace_bytes, x3, x4, C3, C4,
+                            gn_partial, gn_partial_bytes, gn_groups, gn_chunks, s);
+}
+int tf_conv2d_f16(void* y, const void* x, const void* x2, const void* w, const void* bias, const void* bias_nc, long long bias_nc_stride,
+                  const void* residual, int N, int H, int W, int C1, int C2, int Cout, int R, int S, int stride, int pad, int upsample,
+                  void* workspace, size_t workspace_bytes, tfStream_t s) {
+  return tf_conv2d_fused_16(TF_DTYPE_F16, y, x, x2, w, bias, bias_nc, bias_nc_stride, residual, N, H, W, C1, C2, Cout, R, S, stride, pad, upsample, workspace, workspace_bytes,
+                            nullptr, nullptr, 0, 0, nullptr, 0, 0, nullptr, s);
+}
+
 int tf_conv2d_fused_norm_16(int dtype, void* y, const void* x, const void* x2, const void* w, const void* bias, const void* bias_nc, long long bias_nc_stride,
                             const void* residual, int N, int H, int W, int C1, int C2, int Cout, int R, int S, int stride, int pad, int upsample,
                             void* workspace, size_t workspace_bytes, const void* x3, const void* x4, int C3, int C4, void* gn_partial,
@@ -378,13 +432,16 @@ int tf_conv2d_fused_norm_16(int dtype, void* y, const void* x, const void* x2, c
   TF_REQUIRE_DTYPE("tf_conv2d_fused_norm_16");
   TF_REQUIRE(gn_partial && gn_chunks && z && z_written, "tf_conv2d_fused_norm_f16: gn_partial, gn_chunks, z and z_written must be given");
   TF_REQUIRE((z_gamma == nullptr) == (z_beta == nullptr), "tf_conv2d_fused_norm_f16: gamma and beta must both be given or both NULL");
-  *z_written = 0;
-  GemmP ex = {};
-  ex.bf16 = dtype == TF_DTYPE_BF16;
-  ex.on_z = (half_t*)z; ex.on_gamma = (const half_t*)z_gamma; ex.on_beta = (const half_t*)z_beta; ex.on_eps = z_eps; ex.on_silu = z_silu ? 1 : 0;
-  ex.on_applied = z_written;
-  return conv2d_impl(y, x, x2, w, bias, bias_nc, bias_nc_stride, residual, N, H, W, C1, C2, Cout, R, S, stride, pad, upsample, workspace,
-                     workspace_bytes, (float*)gn_partial, gn_partial_bytes, gn_groups, gn_chunks, x3, x4, C3, C4, s, &ex);
+  *z_written = 0; *gn_chunks = 0;
+  GemmP p;
+  int rc = conv_problem(p, "tf_conv2d_f16", EL_16, {N, H, W, C1, C2, Cout, R, S, stride, pad, upsample, C3, C4}, y, x, x2, x3, x4, w, bias, bias_nc, bias_nc_stride, residual);
+  if (rc || N == 0) return rc;
+  p.bf16 = dtype == TF_DTYPE_BF16;
+  if ((rc = conv_output_stats(p, "tf_conv2d_fused_f16", N, gn_partial, gn_partial_bytes, gn_groups))) return rc;
+  if (p.gn_part) {                                          // (groups the epilogue cannot fold: no statistics, no apply -- *z_written stays 0)
+    p.on_z = (half_t*)z; p.on_gamma = (const half_t*)z_gamma; p.on_beta = (const half_t*)z_beta; p.on_eps = z_eps; p.on_silu = z_silu ? 1 : 0; p.on_applied = z_written;
+  }
+  return run_forced(p, workspace, workspace_bytes, s, gn_chunks);
 }
 int tf_conv2d_fused_norm_f16(void* y, const void* x, const void* x2, const void* w, const void* bias, const void* bias_nc, long long bias_nc_stride,
                              const void* residual, int N, int H, int W, int C1, int C2, int Cout, int R, int S, int stride, int pad, int upsample,
@@ -396,13 +453,10 @@ int tf_conv2d_fused_norm_f16(void* y, const void* x, const void* x2, const void*
 }
 
 int tf_conv2d_gn_supported(int N, int H, int W, int C1, int C2, int Cout, int R, int S, int stride, int pad, int upsample, int C3, int C4, int in_groups) {
-  int Ho, Wo;
   if (N < 1 || C1 < 1 || C2 < 0 || Cout < 1 || R != S || stride < 1 || in_groups < 1 || (C1 + C2) % in_groups) return 0;
-  if (conv_geometry(H, W, R, S, stride, pad, upsample ? 1 : 0, &Ho, &Wo)) return 0;
+  GemmP p;
+  if (conv_shape(p, EL_16, {N, H, W, C1, C2, Cout, R, S, stride, pad, upsample, C3, C4})) return 0;
   static float dummy;
-  GemmP p = {};
-  p.M = N * Ho * Wo; p.N = Cout; p.C1 = C1; p.C2 = C2; p.C = C1 + C2; p.Kc = R * S * p.C; p.K = p.Kc + C3 + C4; p.C3 = C3; p.C4 = C4;
-  p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo; p.HoWo = Ho * Wo; p.S = S; p.stride = stride; p.pad = pad; p.ups = upsample ? 1 : 0;
   p.gi_part = &dummy; p.gi_G = in_groups;
   return gi_any_ok(p) ? 1 : 0;
 }
@@ -417,10 +471,7 @@ int tf_conv2d_gn_16(int dtype, void* y, const void* x, const void* x2, const voi
   TF_REQUIRE(!gn_partial || gn_chunks, "tf_conv2d_gn_f16: gn_chunks must be given with gn_partial");
   TF_REQUIRE(in_partial && in_chunks >= 1 && in_chunks <= 4096 && in_groups >= 1 && (C1 + C2) % in_groups == 0, "tf_conv2d_gn_f16: input statistics missing (chunks=%d groups=%d)", in_chunks, in_groups);
   TF_REQUIRE((in_gamma == nullptr) == (in_beta == nullptr), "tf_conv2d_gn_f16: gamma and beta must both be given or both NULL");
-  GemmP gi = {};
-  gi.bf16 = dtype == TF_DTYPE_BF16;
-  gi.gi_part = (const float*)in_partial; gi.gi_gamma = (const half_t*)in_gamma; gi.gi_beta = (const half_t*)in_beta;
-  gi.gi_chunks = in_chunks; gi.gi_G = in_groups; gi.gi_G1 = in_groups; gi.gi_mr = 1; gi.gi_eps = in_eps; gi.gi_silu = in_silu ? 1 : 0;
+  int mr = 1;
   if (in_partial2) {
     // concat (x, x2) whose statistics came with its two sources: partials of G1 sub-groups of x and G2 of x2, all of one width,
     // mr adjacent sub-groups of the list [x's | x2's] form a group of the concat (tf_group_norm_apply_cat_f16's contract)
@@ -428,10 +479,20 @@ int tf_conv2d_gn_16(int dtype, void* y, const void* x, const void* x2, const voi
                "tf_conv2d_gn_f16: C1=%d C2=%d groups1=%d groups2=%d chunks2=%d", C1, C2, in_groups1, in_groups2, in_chunks2);
     const int sub = C1 / in_groups1, cpg = (C1 + C2) / in_groups;
     TF_REQUIRE(C2 / in_groups2 == sub && cpg % sub == 0 && cpg / sub <= 8, "tf_conv2d_gn_f16: the partials' sub-groups (%d and %d channels) do not tile the %d-channel groups", sub, C2 / in_groups2, cpg);
-    gi.gi_part2 = (const float*)in_partial2; gi.gi_chunks2 = in_chunks2; gi.gi_G1 = in_groups1; gi.gi_G2 = in_groups2; gi.gi_mr = cpg / sub;
+    mr = cpg / sub;
   }
-  return conv2d_impl(y, x, x2, w, bias, bias_nc, bias_nc_stride, residual, N, H, W, C1, C2, Cout, R, S, stride, pad, upsample, workspace,
-                     workspace_bytes, (float*)gn_partial, gn_partial_bytes, gn_groups, gn_chunks, x3, x4, C3, C4, s, &gi);
+  if (gn_chunks) *gn_chunks = 0;
+  GemmP p;
+  int rc = conv_problem(p, "tf_conv2d_f16", EL_16, {N, H, W, C1, C2, Cout, R, S, stride, pad, upsample, C3, C4}, y, x, x2, x3, x4, w, bias, bias_nc, bias_nc_stride, residual);
+  if (rc || N == 0) return rc;
+  p.bf16 = dtype == TF_DTYPE_BF16;
+  if ((rc = conv_output_stats(p, "tf_conv2d_fused_f16", N, gn_partial, gn_partial_bytes, gn_groups))) return rc;
+  p.gi_part = (const float*)in_partial; p.gi_gamma = (const half_t*)in_gamma; p.gi_beta = (const half_t*)in_beta;
+  p.gi_chunks = in_chunks; p.gi_G = in_groups; p.gi_G1 = in_groups; p.gi_mr = mr; p.gi_eps = in_eps; p.gi_silu = in_silu ? 1 : 0;
+  if (in_partial2) { p.gi_part2 = (const float*)in_partial2; p.gi_chunks2 = in_chunks2; p.gi_G1 = in_groups1; p.gi_G2 = in_groups2; }
+  p.ktiles = (p.K + 63) / 64;
+  if (!gi_any_ok(p)) { tf_set_error("tf_conv2d_gn_f16: this geometry cannot carry the input GroupNorm (ask tf_conv2d_gn_supported first)"); return TF_E_UNSUPPORTED; }
+  return run_forced(p, workspace, workspace_bytes, s, gn_chunks);
 }
 int tf_conv2d_gn_f16(void* y, const void* x, const void* x2, const void* w, const void* bias, const void* bias_nc, long long bias_nc_stride,
                      const void* residual, int N, int H, int W, int C1, int C2, int Cout, int R, int S, int stride, int pad, int upsample,
@@ -444,123 +505,51 @@ int tf_conv2d_gn_f16(void* y, const void* x, const void* x2, const void* w, cons
                          in_silu, s);
 }
 
-int tf_conv2d_f16(void* y, const void* x, const void* x2, const void* w, const void* bias, const void* bias_nc, long long bias_nc_stride,
-                  const void* residual, int N, int H, int W, int C1, int C2, int Cout, int R, int S, int stride, int pad, int upsample,
-                  void* workspace, size_t workspace_bytes, tfStream_t s) {
-  return conv2d_impl(y, x, x2, w, bias, bias_nc, bias_nc_stride, residual, N, H, W, C1, C2, Cout, R, S, stride, pad, upsample, workspace,
-                     workspace_bytes, nullptr, 0, 0, nullptr, nullptr, nullptr, 0, 0, s);
-}
-
-int tf_conv2d_fused_16(int dtype, void* y, const void* x, const void* x2, const void* w, const void* bias, const void* bias_nc, long long bias_nc_stride,
-                       const void* residual, int N, int H, int W, int C1, int C2, int Cout, int R, int S, int stride, int pad, int upsample,
-                       void* workspace, size_t workspace_bytes, const void* x3, const void* x4, int C3, int C4, void* gn_partial,
-                       size_t gn_partial_bytes, int gn_groups, int* gn_chunks, tfStream_t s) {
-  TF_REQUIRE_DTYPE("tf_conv2d_fused_16");
-  TF_REQUIRE(!gn_partial || gn_chunks, "tf_conv2d_fused_f16: gn_chunks must be given with gn_partial");
-  GemmP ex = {};
-  ex.bf16 = dtype == TF_DTYPE_BF16;
-  return conv2d_impl(y, x, x2, w, bias, bias_nc, bias_nc_stride, residual, N, H, W, C1, C2, Cout, R, S, stride, pad, upsample, workspace,
-                     workspace_bytes, (float*)gn_partial, gn_partial_bytes, gn_groups, gn_chunks, x3, x4, C3, C4, s, &ex);
-}
-int tf_conv2d_fused_f16(void* y, const void* x, const void* x2, const void* w, const void* bias, const void* bias_nc, long long bias_nc_stride,
-                        const void* residual, int N, int H, int W, int C1, int C2, int Cout, int R, int S, int stride, int pad, int upsample,
-                        void* workspace, size_t workspace_bytes, const void* x3, const void* x4, int C3, int C4, void* gn_partial,
-                        size_t gn_partial_bytes, int gn_groups, int* gn_chunks, tfStream_t s) {
-  return tf_conv2d_fused_16(TF_DTYPE_F16, y, x, x2, w, bias, bias_nc, bias_nc_stride, residual, N, H, W, C1, C2, Cout, R, S, stride, pad, upsample, workspace, workspace_bytes, x3, x4, C3, C4,
-                            gn_partial, gn_partial_bytes, gn_groups, gn_chunks, s);
-}
-
-size_t tf_conv2d_fused_workspace(int N, int H, int W, int C1, int C2, int Cout, int R, int S, int stride, int pad, int upsample, int C3, int C4) {
-  int Ho, Wo;
-  if (stride < 1 || conv_geometry(H, W, R, S, stride, pad, upsample ? 1 : 0, &Ho, &Wo)) return 0;
-  return gemm_workspace(N * Ho * Wo, Cout, R * S * (C1 + C2) + C3 + C4, 0);
-}
-
 size_t tf_linear_workspace(int M, int N, int K, int act) { return gemm_workspace(M, act == 1 ? 2 * N : N, K, act); }
 
-int tf_linear_f16(void* y, const void* x, const void* w, const void* bias, const void* residual, int M, int N, int K, int act,
-                  void* workspace, size_t workspace_bytes, tfStream_t s) {
-  return tf_linear_16(TF_DTYPE_F16, y, x, w, bias, residual, M, N, K, act, workspace, workspace_bytes, s);
+// tf_linear_16 under the name its messages carry.  heed_force = false: tf_gemm_force_config does not reach this launch (the _bf16-only entries)
+static int linear_16(const char* fn, int dtype, void* y, const void* x, const void* w, const void* bias, const void* residual, int M, int N, int K, int act,
+                     void* workspace, size_t workspace_bytes, bool heed_force, tfStream_t s) {
+  GemmP p;
+  int rc = linear_problem(p, fn, EL_16, y, x, w, bias, residual, M, N, K, act);
+  if (rc || M == 0) return rc;
+  p.bf16 = dtype == TF_DTYPE_BF16;
+  return heed_force ? run_forced(p, workspace, workspace_bytes, s) : run_gemm(p, workspace, workspace_bytes, 0, 0, 0, tf_hs(s));
 }
 int tf_linear_16(int dtype, void* y, const void* x, const void* w, const void* bias, const void* residual, int M, int N, int K, int act,
                  void* workspace, size_t workspace_bytes, tfStream_t s) {
   TF_REQUIRE_DTYPE("tf_linear_16");
-  TF_REQUIRE(y && x && w, "tf_linear_f16: null tensor");
-  TF_REQUIRE(M >= 0 && N >= 1 && K >= 8 && K % 8 == 0, "tf_linear_f16: K=%d must be a positive multiple of 8", K);
-  TF_REQUIRE(act == 0 || act == 1, "tf_linear_f16: act=%d", act);
-  TF_REQUIRE(act == 0 || (bias && N % 16 == 0), "tf_linear_f16: GEGLU needs a bias and N %% 16 == 0 (N=%d)", N);
-  if (M == 0) return TF_OK;
-  GemmP p = {};
-  p.x = (const half_t*)x; p.w = (const half_t*)w; p.y = (half_t*)y; p.bias = (const half_t*)bias; p.residual = (const half_t*)residual;
-  p.M = M; p.N = act == 1 ? 2 * N : N; p.K = K; p.Kc = K; p.C1 = K; p.C2 = 0; p.C = K;
-  p.H = 1; p.W = M; p.Ho = 1; p.Wo = M; p.HoWo = M; p.S = 1; p.stride = 1; p.pad = 0; p.ups = 0; p.act = act;
-  p.bf16 = dtype == TF_DTYPE_BF16;
-  {
-    long long xb = (long long)M * K * 2, wb = (long long)p.N * K * 2;
-    TF_REQUIRE(xb < (1LL << 31) && wb < (1LL << 31), "tf_linear_f16: tensors must be < 2 GiB each");
-    p.x_bytes = (unsigned)xb; p.x2_bytes = (unsigned)xb; p.w_bytes = (unsigned)wb;
-  }
-  return run_gemm(p, workspace, workspace_bytes, g_force_bm, g_force_bn, g_force_split, tf_hs(s));
+  return linear_16("tf_linear_f16", dtype, y, x, w, bias, residual, M, N, K, act, workspace, workspace_bytes, true, s);
+}
+int tf_linear_f16(void* y, const void* x, const void* w, const void* bias, const void* residual, int M, int N, int K, int act,
+                  void* workspace, size_t workspace_bytes, tfStream_t s) {
+  return tf_linear_16(TF_DTYPE_F16, y, x, w, bias, residual, M, N, K, act, workspace, workspace_bytes, s);
 }
 
 // scores of the unfused attention path (attention/sdpa.py:66 of the reference: cp.matmul(q, k^T) in fp32): y32[m, n] = sum_k x[m, k] w[n, k],
 // fp16 operands, fp32 accumulators stored as they are
 int tf_linear_f32out_f16(void* y_f32, const void* x, const void* w, int M, int N, int K, tfStream_t s) {
-  TF_REQUIRE(y_f32 && x && w, "tf_linear_f32out_f16: null tensor");
-  TF_REQUIRE(M >= 0 && N >= 1 && K >= 8 && K % 8 == 0, "tf_linear_f32out_f16: K=%d must be a positive multiple of 8", K);
-  if (M == 0) return TF_OK;
-  GemmP p = {};
-  p.x = (const half_t*)x; p.w = (const half_t*)w; p.y = (half_t*)y_f32; p.out32 = (float*)y_f32;
-  p.M = M; p.N = N; p.K = K; p.Kc = K; p.C1 = K; p.C2 = 0; p.C = K;
-  p.H = 1; p.W = M; p.Ho = 1; p.Wo = M; p.HoWo = M; p.S = 1; p.stride = 1; p.pad = 0; p.ups = 0; p.act = 0;
-  {
-    long long xb = (long long)M * K * 2, wb = (long long)N * K * 2;
-    TF_REQUIRE(xb < (1LL << 31) && wb < (1LL << 31), "tf_linear_f32out_f16: tensors must be < 2 GiB each");
-    p.x_bytes = (unsigned)xb; p.x2_bytes = (unsigned)xb; p.w_bytes = (unsigned)wb; p.x3_bytes = p.x4_bytes = (unsigned)xb;
-  }
-  return run_gemm(p, nullptr, 0, g_force_bm, g_force_bn, g_force_split > 1 ? 1 : g_force_split, tf_hs(s));
+  GemmP p;
+  int rc = linear_problem(p, "tf_linear_f32out_f16", EL_16, y_f32, x, w, nullptr, nullptr, M, N, K, 0);
+  if (rc || M == 0) return rc;
+  p.out32 = (float*)y_f32;
+  return run_gemm(p, nullptr, 0, g_force_bm, g_force_bn, g_force_split > 1 ? 1 : g_force_split, tf_hs(s));   // no workspace: a forced split is clamped to 1
 }
 
 // ---- bfloat16 entries: the reference's op tests parametrise bfloat16 next to float16 (tests/linear.py:13, tests/layer_norm.py:13,
-// tests/group_norm.py:12) -- same tensors and semantics as the _f16 entries with every 16-bit tensor holding bfloat16 ----------------
+// tests/group_norm.py:12) -- the tagged entries with TF_DTYPE_BF16, without a workspace (so never split along K); the two linears are also out
+// of tf_gemm_force_config's reach ----------------
 int tf_linear_bf16(void* y, const void* x, const void* w, const void* bias, const void* residual, int M, int N, int K, tfStream_t s) {
-  TF_REQUIRE(y && x && w, "tf_linear_bf16: null tensor");
-  TF_REQUIRE(M >= 0 && N >= 1 && K >= 8 && K % 8 == 0, "tf_linear_bf16: K=%d must be a positive multiple of 8", K);
-  if (M == 0) return TF_OK;
-  GemmP p = {};
-  p.x = (const half_t*)x; p.w = (const half_t*)w; p.y = (half_t*)y; p.bias = (const half_t*)bias; p.residual = (const half_t*)residual;
-  p.M = M; p.N = N; p.K = K; p.Kc = K; p.C1 = K; p.C2 = 0; p.C = K;
-  p.H = 1; p.W = M; p.Ho = 1; p.Wo = M; p.HoWo = M; p.S = 1; p.stride = 1; p.pad = 0; p.ups = 0; p.act = 0; p.bf16 = 1;
-  {
-    long long xb = (long long)M * K * 2, wb = (long long)p.N * K * 2;
-    TF_REQUIRE(xb < (1LL << 31) && wb < (1LL << 31), "tf_linear_bf16: tensors must be < 2 GiB each");
-    p.x_bytes = (unsigned)xb; p.x2_bytes = (unsigned)xb; p.w_bytes = (unsigned)wb;
-  }
-  return run_gemm(p, nullptr, 0, 0, 0, 0, tf_hs(s));
+  return linear_16("tf_linear_bf16", TF_DTYPE_BF16, y, x, w, bias, residual, M, N, K, 0, nullptr, 0, false, s);
 }
 // ... with the GEGLU epilogue (act = 1: w / bias packed in 16-row value | gate blocks as for tf_linear_f16; N = the output width): ff/nn.py:5-12 on bfloat16
 int tf_linear_act_bf16(void* y, const void* x, const void* w, const void* bias, const void* residual, int M, int N, int K, int act, tfStream_t s) {
-  TF_REQUIRE(y && x && w, "tf_linear_act_bf16: null tensor");
-  TF_REQUIRE(M >= 0 && N >= 1 && K >= 8 && K % 8 == 0, "tf_linear_act_bf16: K=%d must be a positive multiple of 8", K);
-  TF_REQUIRE(act == 0 || (act == 1 && bias && N % 16 == 0), "tf_linear_act_bf16: act=%d (GEGLU needs a bias and N %% 16 == 0, N=%d)", act, N);
-  if (M == 0) return TF_OK;
-  GemmP p = {};
-  p.x = (const half_t*)x; p.w = (const half_t*)w; p.y = (half_t*)y; p.bias = (const half_t*)bias; p.residual = (const half_t*)residual;
-  p.M = M; p.N = act == 1 ? 2 * N : N; p.K = K; p.Kc = K; p.C1 = K; p.C2 = 0; p.C = K;
-  p.H = 1; p.W = M; p.Ho = 1; p.Wo = M; p.HoWo = M; p.S = 1; p.stride = 1; p.pad = 0; p.ups = 0; p.act = act; p.bf16 = 1;
-  {
-    long long xb = (long long)M * K * 2, wb = (long long)p.N * K * 2;
-    TF_REQUIRE(xb < (1LL << 31) && wb < (1LL << 31), "tf_linear_act_bf16: tensors must be < 2 GiB each");
-    p.x_bytes = (unsigned)xb; p.x2_bytes = (unsigned)xb; p.w_bytes = (unsigned)wb;
-  }
-  return run_gemm(p, nullptr, 0, 0, 0, 0, tf_hs(s));
+  return linear_16("tf_linear_act_bf16", TF_DTYPE_BF16, y, x, w, bias, residual, M, N, K, act, nullptr, 0, false, s);
 }
 int tf_conv2d_bf16(void* y, const void* x, const void* x2, const void* w, const void* bias, const void* bias_nc, long long bias_nc_stride,
                    const void* residual, int N, int H, int W, int C1, int C2, int Cout, int R, int S, int stride, int pad, int upsample, tfStream_t s) {
-  GemmP ex = {};
-  ex.bf16 = 1;
-  return conv2d_impl(y, x, x2, w, bias, bias_nc, bias_nc_stride, residual, N, H, W, C1, C2, Cout, R, S, stride, pad, upsample, nullptr, 0,
-                     nullptr, 0, 0, nullptr, nullptr, nullptr, 0, 0, s, &ex);
+  return tf_conv2d_fused_16(TF_DTYPE_BF16, y, x, x2, w, bias, bias_nc, bias_nc_stride, residual, N, H, W, C1, C2, Cout, R, S, stride, pad, upsample, nullptr, 0,
+                            nullptr, nullptr, 0, 0, nullptr, 0, 0, nullptr, s);
 }
 
 // ---- fp8 entries (config 5) ---------------------------------------------------------------------------------------------------
@@ -587,55 +576,26 @@ int tf_conv2d_fp8(void* y, const void* x8, const void* x28, const void* w8, cons
                   int upsample, void* workspace, size_t workspace_bytes, void* gn_partial, size_t gn_partial_bytes, int gn_groups, int* gn_chunks,
                   tfStream_t s) {
   if (gn_chunks) *gn_chunks = 0;
-  TF_REQUIRE(y && x8 && w8 && wscale, "tf_conv2d_fp8: null tensor");
-  TF_REQUIRE(C1 > 0 && C2 >= 0 && (C2 == 0 || x28) && C1 % 64 == 0 && C2 % 64 == 0, "tf_conv2d_fp8: channel counts must be multiples of 64 (C1=%d C2=%d)", C1, C2);
-  TF_REQUIRE(R >= 1 && R == S && stride >= 1 && pad >= 0 && Cout >= 1 && N >= 0, "tf_conv2d_fp8: bad geometry R=%d S=%d stride=%d pad=%d", R, S, stride, pad);
+  TF_REQUIRE(wscale, "tf_conv2d_fp8: null tensor");
+  TF_REQUIRE(R == S, "tf_conv2d_fp8: bad geometry R=%d S=%d stride=%d pad=%d", R, S, stride, pad);
   TF_REQUIRE(!gn_partial || gn_chunks, "tf_conv2d_fp8: gn_chunks must be given with gn_partial");
-  int ups = upsample ? 1 : 0, Ho, Wo;
-  TF_REQUIRE(!conv_geometry(H, W, R, S, stride, pad, ups, &Ho, &Wo), "tf_conv2d_fp8: empty output for H=%d W=%d", H, W);
-  if (N == 0) return TF_OK;
-  TF_REQUIRE((long long)N * Ho * Wo < (1LL << 31), "tf_conv2d_fp8: problem too large for 32-bit indexing");
-  GemmP p = {};
-  p.fp8 = 1; p.wscale = (const float*)wscale;
-  p.x = (const half_t*)x8; p.x2 = (const half_t*)x28; p.w = (const half_t*)w8; p.y = (half_t*)y;
-  p.bias = (const half_t*)bias; p.bias_nc = (const half_t*)bias_nc; p.residual = (const half_t*)residual; p.bias_nc_stride = bias_nc_stride;
-  TF_REQUIRE(bias_nc_stride % 4 == 0 || Cout % 4 != 0, "tf_conv2d_fp8: bias_nc_stride must be a multiple of 4");
-  p.M = N * Ho * Wo; p.N = Cout; p.C1 = C1; p.C2 = C2; p.C = C1 + C2; p.Kc = R * S * p.C; p.K = p.Kc;
-  p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo; p.HoWo = Ho * Wo; p.S = S; p.stride = stride; p.pad = pad; p.ups = ups;
-  {
-    long long xb = (long long)N * H * W * C1, x2b = (long long)N * H * W * C2, wb = (long long)Cout * p.K;
-    TF_REQUIRE(xb < (1LL << 31) && x2b < (1LL << 31) && wb < (1LL << 31), "tf_conv2d_fp8: tensors must be < 2 GiB each");
-    p.x_bytes = (unsigned)xb; p.x2_bytes = C2 ? (unsigned)x2b : (unsigned)xb; p.w_bytes = (unsigned)wb;
-    p.x3_bytes = p.x4_bytes = (unsigned)xb;
-  }
-  if (gn_partial) {
-    TF_REQUIRE(gn_groups >= 1 && Cout % gn_groups == 0, "tf_conv2d_fp8: Cout=%d not divisible by groups=%d", Cout, gn_groups);
-    TF_REQUIRE(gn_partial_bytes >= tf_conv2d_gn_partial_bytes(N, gn_groups), "tf_conv2d_fp8: statistics buffer too small (%zu bytes)", gn_partial_bytes);
-    int cpg = Cout / gn_groups;
-    if (cpg >= 4 && cpg <= 64 && Cout % 8 == 0 && Cout <= 4096 && gn_groups <= 256) { p.gn_part = (float*)gn_partial; p.gn_G = gn_groups; p.gn_cpg = cpg; }
-  }
-  return run_gemm(p, workspace, workspace_bytes, g_force_bm, g_force_bn, g_force_split, tf_hs(s), gn_chunks);
+  GemmP p;
+  int rc = conv_problem(p, "tf_conv2d_fp8", EL_E4M3, {N, H, W, C1, C2, Cout, R, S, stride, pad, upsample, 0, 0}, y, x8, x28, nullptr, nullptr, w8, bias, bias_nc, bias_nc_stride, residual);
+  if (rc || N == 0) return rc;
+  p.wscale = (const float*)wscale;
+  if ((rc = conv_output_stats(p, "tf_conv2d_fp8", N, gn_partial, gn_partial_bytes, gn_groups))) return rc;
+  return run_forced(p, workspace, workspace_bytes, s, gn_chunks);
 }
 int tf_linear_fp8(void* y, const void* x8, const void* w8, const void* wscale, const void* bias, const void* residual, int M, int N, int K, int act,
                   int out_fp8, void* workspace, size_t workspace_bytes, tfStream_t s) {
-  TF_REQUIRE(y && x8 && w8 && wscale, "tf_linear_fp8: null tensor");
-  TF_REQUIRE(M >= 0 && N >= 1 && K >= 64 && K % 64 == 0, "tf_linear_fp8: K=%d must be a positive multiple of 64", K);
-  TF_REQUIRE(act == 0 || act == 1, "tf_linear_fp8: act=%d", act);
-  TF_REQUIRE(act == 0 || (bias && N % 16 == 0), "tf_linear_fp8: GEGLU needs a bias and N %% 16 == 0 (N=%d)", N);
+  TF_REQUIRE(wscale, "tf_linear_fp8: null tensor");
   TF_REQUIRE(!out_fp8 || N % 8 == 0, "tf_linear_fp8: an e4m3 output needs N %% 8 == 0 (N=%d)", N);
-  if (M == 0) return TF_OK;
-  GemmP p = {};
-  p.fp8 = 1; p.wscale = (const float*)wscale; p.out8 = out_fp8 ? 1 : 0;
-  p.x = (const half_t*)x8; p.w = (const half_t*)w8; p.y = (half_t*)y; p.bias = (const half_t*)bias; p.residual = (const half_t*)residual;
-  p.M = M; p.N = act == 1 ? 2 * N : N; p.K = K; p.Kc = K; p.C1 = K; p.C2 = 0; p.C = K;
-  p.H = 1; p.W = M; p.Ho = 1; p.Wo = M; p.HoWo = M; p.S = 1; p.stride = 1; p.pad = 0; p.ups = 0; p.act = act;
-  {
-    long long xb = (long long)M * K, wb = (long long)p.N * K;
-    TF_REQUIRE(xb < (1LL << 31) && wb < (1LL << 31), "tf_linear_fp8: tensors must be < 2 GiB each");
-    p.x_bytes = (unsigned)xb; p.x2_bytes = (unsigned)xb; p.w_bytes = (unsigned)wb; p.x3_bytes = p.x4_bytes = (unsigned)xb;
-  }
+  GemmP p;
+  int rc = linear_problem(p, "tf_linear_fp8", EL_E4M3, y, x8, w8, bias, residual, M, N, K, act);
+  if (rc || M == 0) return rc;
+  p.wscale = (const float*)wscale; p.out8 = out_fp8 ? 1 : 0;
   if (p.out8) workspace = nullptr, workspace_bytes = 0;   // the split-K reduce writes fp16: an e4m3 output runs unsplit
-  return run_gemm(p, workspace, workspace_bytes, g_force_bm, g_force_bn, g_force_split, tf_hs(s));
+  return run_forced(p, workspace, workspace_bytes, s);
 }
 
 // ---- block-scaled e4m3 activations (round 4): one E8M0 scale per 32 consecutive channels of a pixel / token, fed to the scale operand of
@@ -663,18 +623,15 @@ static bool mx_shape_ok(const GemmP& p) {
 }
 int tf_mx8_gemm_supported(int M, int N, int K, int act, int out_mx) {
   if (M < 1 || N < 1 || K < 64) return 0;
-  GemmP p = {};
-  p.fp8 = 1; p.mx = 1; p.out8 = out_mx ? 1 : 0; p.act = act;
-  p.M = M; p.N = act == 1 ? 2 * N : N; p.K = K; p.Kc = K; p.C1 = K; p.C = K; p.H = 1; p.W = M; p.Ho = 1; p.Wo = M; p.HoWo = M; p.S = 1; p.stride = 1;
+  GemmP p;
+  linear_shape(p, EL_MX, M, N, K, act);
+  p.out8 = out_mx ? 1 : 0;
   return mx_shape_ok(p) ? 1 : 0;
 }
 int tf_mx8_conv_supported(int N, int H, int W, int C1, int C2, int Cout, int R, int S, int stride, int pad, int upsample) {
-  int Ho, Wo;
-  if (N < 1 || C1 < 64 || C2 < 0 || R != S || stride != 1 || upsample || (C1 % 64) || (C2 % 64) || conv_geometry(H, W, R, S, stride, pad, 0, &Ho, &Wo)) return 0;
-  GemmP p = {};
-  p.fp8 = 1; p.mx = 1;
-  p.M = N * Ho * Wo; p.N = Cout; p.C1 = C1; p.C2 = C2; p.C = C1 + C2; p.Kc = R * S * p.C; p.K = p.Kc;
-  p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo; p.HoWo = Ho * Wo; p.S = S; p.stride = 1; p.pad = pad;
+  if (N < 1 || C1 < 64 || C2 < 0 || R != S || stride != 1 || upsample || (C1 % 64) || (C2 % 64)) return 0;
+  GemmP p;
+  if (conv_shape(p, EL_MX, {N, H, W, C1, C2, Cout, R, S, 1, pad, 0, 0, 0})) return 0;
   p.bias_nc = (const half_t*)&p;                            // (the ResBlock convs carry a time-embedding bias: the stricter tile rule)
   return mx_shape_ok(p) ? 1 : 0;
 }
@@ -682,55 +639,26 @@ int tf_conv2d_mx8(void* y, const void* x_mx, const void* x2_mx, const void* w8, 
                   long long bias_nc_stride, const void* residual, int N, int H, int W, int C1, int C2, int Cout, int R, int S, int stride, int pad,
                   void* workspace, size_t workspace_bytes, void* gn_partial, size_t gn_partial_bytes, int gn_groups, int* gn_chunks, tfStream_t s) {
   if (gn_chunks) *gn_chunks = 0;
-  TF_REQUIRE(y && x_mx && w8 && wscale, "tf_conv2d_mx8: null tensor");
-  TF_REQUIRE(C1 > 0 && C2 >= 0 && (C2 == 0 || x2_mx) && C1 % 64 == 0 && C2 % 64 == 0, "tf_conv2d_mx8: channel counts must be multiples of 64 (C1=%d C2=%d)", C1, C2);
-  TF_REQUIRE(R >= 1 && R == S && stride == 1 && pad >= 0 && Cout >= 1 && N >= 0, "tf_conv2d_mx8: stride-1 square filters only (R=%d S=%d stride=%d pad=%d)", R, S, stride, pad);
+  TF_REQUIRE(wscale, "tf_conv2d_mx8: null tensor");
+  TF_REQUIRE(R == S && stride == 1, "tf_conv2d_mx8: stride-1 square filters only (R=%d S=%d stride=%d pad=%d)", R, S, stride, pad);
   TF_REQUIRE(!gn_partial || gn_chunks, "tf_conv2d_mx8: gn_chunks must be given with gn_partial");
-  int Ho, Wo;
-  TF_REQUIRE(!conv_geometry(H, W, R, S, stride, pad, 0, &Ho, &Wo), "tf_conv2d_mx8: empty output for H=%d W=%d", H, W);
-  if (N == 0) return TF_OK;
-  TF_REQUIRE((long long)N * Ho * Wo < (1LL << 31), "tf_conv2d_mx8: problem too large for 32-bit indexing");
-  GemmP p = {};
-  p.fp8 = 1; p.mx = 1; p.wscale = (const float*)wscale;
-  p.x = (const half_t*)x_mx; p.x2 = (const half_t*)x2_mx; p.w = (const half_t*)w8; p.y = (half_t*)y;
-  p.bias = (const half_t*)bias; p.bias_nc = (const half_t*)bias_nc; p.residual = (const half_t*)residual; p.bias_nc_stride = bias_nc_stride;
-  TF_REQUIRE(bias_nc_stride % 4 == 0 || Cout % 4 != 0, "tf_conv2d_mx8: bias_nc_stride must be a multiple of 4");
-  p.M = N * Ho * Wo; p.N = Cout; p.C1 = C1; p.C2 = C2; p.C = C1 + C2; p.Kc = R * S * p.C; p.K = p.Kc;
-  p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo; p.HoWo = Ho * Wo; p.S = S; p.stride = stride; p.pad = pad; p.ups = 0;
-  {
-    long long xb = (long long)N * H * W * C1, x2b = (long long)N * H * W * C2, wb = (long long)Cout * p.K;
-    TF_REQUIRE(xb + xb / 32 < (1LL << 31) && x2b + x2b / 32 < (1LL << 31) && wb < (1LL << 31), "tf_conv2d_mx8: tensors must be < 2 GiB each");
-    p.x_bytes = (unsigned)xb; p.x2_bytes = C2 ? (unsigned)x2b : (unsigned)xb; p.w_bytes = (unsigned)wb;     // (the codes; the scale bytes sit behind them)
-    p.x3_bytes = p.x4_bytes = (unsigned)xb;
-  }
-  if (gn_partial) {
-    TF_REQUIRE(gn_groups >= 1 && Cout % gn_groups == 0, "tf_conv2d_mx8: Cout=%d not divisible by groups=%d", Cout, gn_groups);
-    TF_REQUIRE(gn_partial_bytes >= tf_conv2d_gn_partial_bytes(N, gn_groups), "tf_conv2d_mx8: statistics buffer too small (%zu bytes)", gn_partial_bytes);
-    int cpg = Cout / gn_groups;
-    if (cpg >= 4 && cpg <= 64 && Cout % 8 == 0 && Cout <= 4096 && gn_groups <= 256) { p.gn_part = (float*)gn_partial; p.gn_G = gn_groups; p.gn_cpg = cpg; }
-  }
-  return run_gemm(p, workspace, workspace_bytes, g_force_bm, g_force_bn, g_force_split, tf_hs(s), gn_chunks);
+  GemmP p;
+  int rc = conv_problem(p, "tf_conv2d_mx8", EL_MX, {N, H, W, C1, C2, Cout, R, S, 1, pad, 0, 0, 0}, y, x_mx, x2_mx, nullptr, nullptr, w8, bias, bias_nc, bias_nc_stride, residual);
+  if (rc || N == 0) return rc;
+  p.wscale = (const float*)wscale;
+  if ((rc = conv_output_stats(p, "tf_conv2d_mx8", N, gn_partial, gn_partial_bytes, gn_groups))) return rc;
+  return run_forced(p, workspace, workspace_bytes, s, gn_chunks);
 }
 int tf_linear_mx8(void* y, const void* x_mx, const void* w8, const void* wscale, const void* bias, const void* residual, int M, int N, int K, int act,
                   int out_mx, void* workspace, size_t workspace_bytes, tfStream_t s) {
-  TF_REQUIRE(y && x_mx && w8 && wscale, "tf_linear_mx8: null tensor");
-  TF_REQUIRE(M >= 0 && N >= 1 && K >= 64 && K % 64 == 0, "tf_linear_mx8: K=%d must be a positive multiple of 64", K);
-  TF_REQUIRE(act == 0 || act == 1, "tf_linear_mx8: act=%d", act);
-  TF_REQUIRE(act == 0 || (bias && N % 16 == 0), "tf_linear_mx8: GEGLU needs a bias and N %% 16 == 0 (N=%d)", N);
+  TF_REQUIRE(wscale, "tf_linear_mx8: null tensor");
   TF_REQUIRE(!out_mx || (act == 1 && N % 32 == 0 && !residual), "tf_linear_mx8: a block-scaled output is the GEGLU epilogue's (act = 1, N %% 32 == 0, no residual; N=%d)", N);
-  if (M == 0) return TF_OK;
-  GemmP p = {};
-  p.fp8 = 1; p.mx = 1; p.wscale = (const float*)wscale; p.out8 = out_mx ? 1 : 0;
-  p.x = (const half_t*)x_mx; p.w = (const half_t*)w8; p.y = (half_t*)y; p.bias = (const half_t*)bias; p.residual = (const half_t*)residual;
-  p.M = M; p.N = act == 1 ? 2 * N : N; p.K = K; p.Kc = K; p.C1 = K; p.C2 = 0; p.C = K;
-  p.H = 1; p.W = M; p.Ho = 1; p.Wo = M; p.HoWo = M; p.S = 1; p.stride = 1; p.pad = 0; p.ups = 0; p.act = act;
-  {
-    long long xb = (long long)M * K, wb = (long long)p.N * K;
-    TF_REQUIRE(xb + xb / 32 < (1LL << 31) && wb < (1LL << 31), "tf_linear_mx8: tensors must be < 2 GiB each");
-    p.x_bytes = (unsigned)xb; p.x2_bytes = (unsigned)xb; p.w_bytes = (unsigned)wb; p.x3_bytes = p.x4_bytes = (unsigned)xb;
-  }
+  GemmP p;
+  int rc = linear_problem(p, "tf_linear_mx8", EL_MX, y, x_mx, w8, bias, residual, M, N, K, act);
+  if (rc || M == 0) return rc;
+  p.wscale = (const float*)wscale; p.out8 = out_mx ? 1 : 0;
   if (p.out8) workspace = nullptr, workspace_bytes = 0;   // the split-K reduce writes fp16: an e4m3 output runs unsplit
-  return run_gemm(p, workspace, workspace_bytes, g_force_bm, g_force_bn, g_force_split, tf_hs(s));
+  return run_forced(p, workspace, workspace_bytes, s);
 }
 
 int tf_ln_fold_weights_16(int dtype, void* w_out, void* bias_out, void* colsum_out, const void* w, const void* bias, const void* gamma, const void* beta,
@@ -749,30 +677,22 @@ int tf_ln_fold_weights_f16(void* w_out, void* bias_out, void* colsum_out, const 
   return tf_ln_fold_weights_16(TF_DTYPE_F16, w_out, bias_out, colsum_out, w, bias, gamma, beta, N, K, s);
 }
 
-int tf_linear_ln_f16(void* y, const void* x, const void* w_folded, const void* bias_folded, const void* colsum, const void* residual, int M, int N,
-                     int K, int act, float eps, tfStream_t s) {
-  return tf_linear_ln_16(TF_DTYPE_F16, y, x, w_folded, bias_folded, colsum, residual, M, N, K, act, eps, s);
-}
 int tf_linear_ln_16(int dtype, void* y, const void* x, const void* w_folded, const void* bias_folded, const void* colsum, const void* residual, int M, int N,
                     int K, int act, float eps, tfStream_t s) {
   TF_REQUIRE_DTYPE("tf_linear_ln_16");
-  TF_REQUIRE(y && x && w_folded && bias_folded && colsum, "tf_linear_ln_f16: null tensor");
-  TF_REQUIRE(M >= 0 && N >= 1 && K >= 64 && K % 64 == 0, "tf_linear_ln_f16: K=%d must be a positive multiple of 64", K);
-  TF_REQUIRE(act == 0 || act == 1, "tf_linear_ln_f16: act=%d", act);
+  TF_REQUIRE(bias_folded && colsum, "tf_linear_ln_f16: null tensor");
+  TF_REQUIRE(K >= 64 && K % 64 == 0, "tf_linear_ln_f16: K=%d must be a positive multiple of 64", K);
   TF_REQUIRE((act == 1 ? N % 16 == 0 : N % 4 == 0), "tf_linear_ln_f16: N=%d must be a multiple of 4 (16 for GEGLU)", N);
-  if (M == 0) return TF_OK;
-  GemmP p = {};
-  p.x = (const half_t*)x; p.w = (const half_t*)w_folded; p.y = (half_t*)y; p.bias = (const half_t*)bias_folded; p.residual = (const half_t*)residual;
+  GemmP p;
+  int rc = linear_problem(p, "tf_linear_ln_f16", EL_16, y, x, w_folded, bias_folded, residual, M, N, K, act);
+  if (rc || M == 0) return rc;
   p.ln_colsum = (const float*)colsum; p.ln_eps = eps;
   p.bf16 = dtype == TF_DTYPE_BF16;
-  p.M = M; p.N = act == 1 ? 2 * N : N; p.K = K; p.Kc = K; p.C1 = K; p.C2 = 0; p.C = K;
-  p.H = 1; p.W = M; p.Ho = 1; p.Wo = M; p.HoWo = M; p.S = 1; p.stride = 1; p.pad = 0; p.ups = 0; p.act = act;
-  {
-    long long xb = (long long)M * K * 2, wb = (long long)p.N * K * 2;
-    TF_REQUIRE(xb < (1LL << 31) && wb < (1LL << 31), "tf_linear_ln_f16: tensors must be < 2 GiB each");
-    p.x_bytes = (unsigned)xb; p.x2_bytes = (unsigned)xb; p.w_bytes = (unsigned)wb;
-  }
-  return run_gemm(p, nullptr, 0, g_force_bm, g_force_bn, g_force_split, tf_hs(s));
+  return run_forced(p, nullptr, 0, s);                    // (row statistics need the whole K range in one block: never split, no workspace)
+}
+int tf_linear_ln_f16(void* y, const void* x, const void* w_folded, const void* bias_folded, const void* colsum, const void* residual, int M, int N,
+                     int K, int act, float eps, tfStream_t s) {
+  return tf_linear_ln_16(TF_DTYPE_F16, y, x, w_folded, bias_folded, colsum, residual, M, N, K, act, eps, s);
 }
 
 int tf_gemv_16(int dtype, void* y, const void* x, const void* w, const void* bias, int M, int N, int K, int silu_input, tfStream_t s) {
@@ -788,4 +708,3 @@ int tf_gemv_f16(void* y, const void* x, const void* w, const void* bias, int M, 
 }
 
 }  // extern "C"
-

@@ -19,14 +19,12 @@ regime) or where the fp16 kernels are faster (K = 320: ``MIN_K``).
 The fixed-scale entries of round 2 (``quantize``, ``conv2d_fp8``, ``linear_fp8``, ``group_norm_fp8``, ``layer_norm_fp8``: scale 1, k_igemm8)
 remain as an op-level API; the model no longer uses them.
 """
-import ctypes
-
 import numpy as np
 
 from .. import config
 from ..native import hip, lib
-from ..storage.tensor import DeviceArray, _sh
-from .linear import workspace
+from ..storage.tensor import DeviceArray, _sh, concat_stats_tile
+from .linear import OutputStats, bias_nc_stride, workspace
 
 
 def enabled():
@@ -69,14 +67,11 @@ def group_norm_fp8(x, norm, silu):
         y = DeviceArray.empty((n, c1, h, w), np.uint8, "nhwc")
         hip.tf_group_norm_apply_fp8(y.ptr, x.ptr, None, gm, bt, x.gn[0].ptr, x.gn[1], G, None, 0, 0, n, h * w, c1, 0, G, float(norm.eps), 1 if silu else 0, _sh())
         return y
-    if x2 is not None and x.gn is not None and x2.gn is not None and config.concat_stats:
-        g1, g2 = x.gn[2], x2.gn[2]
-        cpg = (c1 + c2) // G
-        if c1 % g1 == 0 and c2 % g2 == 0 and c1 // g1 == c2 // g2 and cpg % (c1 // g1) == 0 and cpg // (c1 // g1) <= 8:
-            y = DeviceArray.empty((n, c1 + c2, h, w), np.uint8, "nhwc")
-            hip.tf_group_norm_apply_fp8(y.ptr, x.ptr, x2.ptr, gm, bt, x.gn[0].ptr, x.gn[1], g1, x2.gn[0].ptr, x2.gn[1], g2, n, h * w, c1, c2, G,
-                                        float(norm.eps), 1 if silu else 0, _sh())
-            return y
+    if x2 is not None and config.concat_stats and concat_stats_tile(x, x2, G):
+        y = DeviceArray.empty((n, c1 + c2, h, w), np.uint8, "nhwc")
+        hip.tf_group_norm_apply_fp8(y.ptr, x.ptr, x2.ptr, gm, bt, x.gn[0].ptr, x.gn[1], x.gn[2], x2.gn[0].ptr, x2.gn[1], x2.gn[2], n, h * w, c1, c2, G,
+                                    float(norm.eps), 1 if silu else 0, _sh())
+        return y
     return quantize(norm((x, x2) if x2 is not None else x, silu=silu))
 
 
@@ -100,19 +95,11 @@ def conv2d_fp8(x8, w8, wscale, bias, weight_shape, padding, stride, bias_nc=None
     y = DeviceArray.empty((n, k, ho, wo), np.float16, "nhwc")
     nb = hip.tf_conv2d_fp8_workspace(n, h, wd, c1, c2, k, r, s, stride[0], padding[0], up)
     ws = workspace(nb)
-    bnc_stride = 0
-    if bias_nc is not None:
-        bnc_stride = k if bias_nc.size // k > 1 else 0
-    part, pb, chunks = None, 0, ctypes.c_int(0)
-    if gn:
-        pb = hip.tf_conv2d_gn_partial_bytes(n, gn)
-        part = workspace(pb)
+    st = OutputStats(n, gn)
     hip.tf_conv2d_fp8(y.ptr, x8.ptr, x82.ptr if x82 is not None else None, w8.ptr, wscale.ptr, bias.ptr if bias is not None else None,
-                      bias_nc.ptr if bias_nc is not None else None, bnc_stride, residual.ptr if residual is not None else None,
-                      n, h, wd, c1, c2, k, r, s, stride[0], padding[0], up, ws.ptr if ws else None, nb,
-                      part.ptr if part is not None else None, pb, gn, ctypes.byref(chunks), _sh())
-    if chunks.value > 0:
-        y.gn = (part, chunks.value, gn)
+                      bias_nc.ptr if bias_nc is not None else None, bias_nc_stride(bias_nc, k), residual.ptr if residual is not None else None,
+                      n, h, wd, c1, c2, k, r, s, stride[0], padding[0], up, ws.ptr if ws else None, nb, *st.args, _sh())
+    st.attach(y)
     return y
 
 
@@ -202,14 +189,11 @@ def group_norm_mx(x, norm, silu):
         y = mx_empty((n, c1, h, w), "nhwc")
         hip.tf_group_norm_apply_mx8(y.ptr, x.ptr, None, gm, bt, x.gn[0].ptr, x.gn[1], G, None, 0, 0, n, h * w, c1, 0, G, float(norm.eps), 1 if silu else 0, _sh())
         return y
-    if x2 is not None and x.gn is not None and x2.gn is not None and config.concat_stats:
-        g1, g2 = x.gn[2], x2.gn[2]
-        cpg = (c1 + c2) // G
-        if c1 % g1 == 0 and c2 % g2 == 0 and c1 // g1 == c2 // g2 and cpg % (c1 // g1) == 0 and cpg // (c1 // g1) <= 8:
-            y = mx_empty((n, c1 + c2, h, w), "nhwc")
-            hip.tf_group_norm_apply_mx8(y.ptr, x.ptr, x2.ptr, gm, bt, x.gn[0].ptr, x.gn[1], g1, x2.gn[0].ptr, x2.gn[1], g2, n, h * w, c1, c2, G,
-                                        float(norm.eps), 1 if silu else 0, _sh())
-            return y
+    if x2 is not None and config.concat_stats and concat_stats_tile(x, x2, G):
+        y = mx_empty((n, c1 + c2, h, w), "nhwc")
+        hip.tf_group_norm_apply_mx8(y.ptr, x.ptr, x2.ptr, gm, bt, x.gn[0].ptr, x.gn[1], x.gn[2], x2.gn[0].ptr, x2.gn[1], x2.gn[2], n, h * w, c1, c2, G,
+                                    float(norm.eps), 1 if silu else 0, _sh())
+        return y
     return quantize_mx(norm((x, x2) if x2 is not None else x, silu=silu))
 
 
@@ -231,19 +215,11 @@ def conv2d_mx(x8, w8, wscale, bias, weight_shape, padding, bias_nc=None, residua
     y = DeviceArray.empty((n, k, ho, wo), np.float16, "nhwc")
     nb = hip.tf_conv2d_fp8_workspace(n, h, wd, c1, 0, k, r, s, 1, padding[0], 0)
     ws = workspace(nb)
-    bnc_stride = 0
-    if bias_nc is not None:
-        bnc_stride = k if bias_nc.size // k > 1 else 0
-    part, pb, chunks = None, 0, ctypes.c_int(0)
-    if gn:
-        pb = hip.tf_conv2d_gn_partial_bytes(n, gn)
-        part = workspace(pb)
+    st = OutputStats(n, gn)
     hip.tf_conv2d_mx8(y.ptr, x8.ptr, None, w8.ptr, wscale.ptr, bias.ptr if bias is not None else None,
-                      bias_nc.ptr if bias_nc is not None else None, bnc_stride, residual.ptr if residual is not None else None,
-                      n, h, wd, c1, 0, k, r, s, 1, padding[0], ws.ptr if ws else None, nb,
-                      part.ptr if part is not None else None, pb, gn, ctypes.byref(chunks), _sh())
-    if chunks.value > 0:
-        y.gn = (part, chunks.value, gn)
+                      bias_nc.ptr if bias_nc is not None else None, bias_nc_stride(bias_nc, k), residual.ptr if residual is not None else None,
+                      n, h, wd, c1, 0, k, r, s, 1, padding[0], ws.ptr if ws else None, nb, *st.args, _sh())
+    st.attach(y)
     return y
 
 

@@ -1,6 +1,8 @@
 """Linear -- mirrors tinyfusers/ff/linear.py:112-121 (live branch: cp.dot(x, W^T) + b, fp32 cuBLAS SGEMM via CuPy).
 Here: one MFMA implicit-GEMM launch (tf_linear_f16) with bias / residual fused, or the weight-streaming
 GEMV (tf_gemv_f16) for <= 8 rows (time-embedding MLP, ResBlock emb_layers)."""
+import ctypes
+
 import numpy as np
 
 from ..native import hip
@@ -9,6 +11,27 @@ from ..storage.tensor import DeviceArray, _sh, asarray, dtag, is_bfloat16
 
 def workspace(nbytes):
     return DeviceArray.empty((nbytes,), np.uint8, "row") if nbytes else None
+
+
+def bias_nc_stride(bias_nc, k):
+    """Elements between the rows of a per-image bias (n, k) of a conv with k outputs; 0: one row for every image (or no such bias)."""
+    return k if bias_nc is not None and bias_nc.size // k > 1 else 0
+
+
+class OutputStats:
+    """What a conv launch over n images needs to leave the GroupNorm(groups) statistics of its output behind: ``args`` are the entry's
+    (gn_partial, gn_partial_bytes, gn_groups, gn_chunks); groups = 0 asks for none."""
+
+    def __init__(self, n, groups):
+        self.groups = groups
+        nbytes = hip.tf_conv2d_gn_partial_bytes(n, groups) if groups else 0
+        self.part, self.chunks = workspace(nbytes), ctypes.c_int(0)
+        self.args = (self.part.ptr if self.part is not None else None, nbytes, groups, ctypes.byref(self.chunks) if groups else None)
+
+    def attach(self, y):
+        """After the launch: the statistics travel with y where the shape let the epilogue emit them (``y.gn``)."""
+        if self.chunks.value > 0:
+            y.gn = (self.part, self.chunks.value, self.groups)
 
 
 def linear_f16(x, w, b=None, residual=None, act=0, out_features=None):
@@ -35,21 +58,6 @@ def linear_bf16(x, w, b=None, residual=None):
     hip.tf_linear_bf16(y.ptr, x.ptr, w.ptr, b.ptr if b is not None else None, residual.ptr if residual is not None else None,
                        rows, w.shape[0], K, _sh())
     return y
-
-
-def linear_act_bf16(x, w, b=None, residual=None, act=0, out_features=None):
-    """bfloat16 form of linear_f16 (act = 1: GEGLU, w / b packed as for the fp16 kernel)."""
-    K = x.shape[-1]
-    rows = x.size // K
-    n_out = out_features if out_features is not None else w.shape[0]
-    y = DeviceArray.empty(x.shape[:-1] + (n_out,), x.dtype, "row")
-    hip.tf_linear_act_bf16(y.ptr, x.ptr, w.ptr, b.ptr if b is not None else None, residual.ptr if residual is not None else None, rows, n_out, K, act, _sh())
-    return y
-
-
-def linear_any(x, w, b=None, residual=None, act=0, out_features=None):
-    """(round 4 name) linear_f16 takes either element type since round 5."""
-    return linear_f16(x, w, b, residual, act, out_features)
 
 
 def to_f16(x):

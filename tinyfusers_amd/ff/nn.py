@@ -5,7 +5,7 @@ import numpy as np
 
 from ..native import hip
 from ..storage.tensor import DeviceArray, Tensor, _sh
-from .linear import Linear, fold_layer_norm, linear_any, linear_f16, linear_ln_f16
+from .linear import Linear, fold_layer_norm, linear_f16, linear_ln_f16
 
 
 def pack_geglu(weight, bias):
@@ -53,7 +53,7 @@ class GEGLU:
             return linear_ln_f16(x, self._pack_ln(ln), ln.eps, act=1, out_features=self.dim_out)
         if self.dim_out % 16 == 0 and self.proj.bias is not None:
             wp, bp = self._pack()
-            return linear_any(x, wp, bp, None, act=1, out_features=self.dim_out)
+            return linear_f16(x, wp, bp, None, act=1, out_features=self.dim_out)
         h = self.proj(x)                                   # unfused fallback shape (still HIP): split + a*gelu(gate)
         assert h.dtype == np.float16, "unfused GEGLU fallback: fp16 only"
         y = DeviceArray.empty(x.shape[:-1] + (self.dim_out,), np.float16, "row")

@@ -415,6 +415,17 @@ class DeviceArray:
         return f"DeviceArray(shape={self.shape}, dtype={self.dtype}, layout={self.layout}, ptr=0x{self.ptr:x})"
 
 
+def concat_stats_tile(x, x2, num_groups):
+    """Do the statistics that came with x and with x2 (``.gn``: partials of g1 sub-groups of x, of g2 of x2) tile the ``num_groups`` groups of the
+    concat (x | x2)?  tf_group_norm_apply_cat_f16's contract: sub-groups of one width, at most 8 adjacent ones of the list [x's | x2's] to a group
+    -- 32 + 32 sub-groups for an equal split, 64 + 32 for the 2:1 splits of the UNet's output path."""
+    if x.gn is None or x2.gn is None:
+        return False
+    c1, c2, g1, g2 = x.shape[1], x2.shape[1], x.gn[2], x2.gn[2]
+    cpg = (c1 + c2) // num_groups
+    return c1 % g1 == 0 and c2 % g2 == 0 and c1 // g1 == c2 // g2 and cpg % (c1 // g1) == 0 and cpg // (c1 // g1) <= 8
+
+
 def asarray(x, dtype=np.float16, layout=None):
     """numpy / torch-CPU / DeviceArray -> DeviceArray (cp.asarray in the reference, storage/state.py:20)."""
     if isinstance(x, DeviceArray):

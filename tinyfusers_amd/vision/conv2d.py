@@ -10,8 +10,8 @@ import numpy as np
 
 from .. import config
 from ..native import hip, lib
-from ..storage.tensor import DeviceArray, _sh, asarray, dtag, is_bfloat16
-from ..ff.linear import workspace, linear_f16
+from ..storage.tensor import DeviceArray, _sh, asarray, concat_stats_tile, dtag, is_bfloat16
+from ..ff.linear import OutputStats, bias_nc_stride, workspace
 
 
 _gi_support = {}
@@ -34,11 +34,9 @@ def _gn_in_args(x, x2, norm, k, r, s, stride, pad, up, c3, c4):
             return None
         stats = (x.gn[0].ptr, x.gn[1], G, None, 0, 0)
     else:
-        g1, g2 = x.gn[2], x2.gn[2]
-        cpg = (c1 + c2) // G
-        if not (config.concat_stats and c1 % g1 == 0 and c2 % g2 == 0 and c1 // g1 == c2 // g2 and cpg % (c1 // g1) == 0 and cpg // (c1 // g1) <= 8):
+        if not (config.concat_stats and concat_stats_tile(x, x2, G)):
             return None
-        stats = (x.gn[0].ptr, x.gn[1], g1, x2.gn[0].ptr, x2.gn[1], g2)
+        stats = (x.gn[0].ptr, x.gn[1], x.gn[2], x2.gn[0].ptr, x2.gn[1], x2.gn[2])
     key = (n, h, wd, c1, c2, k, r, s, stride, pad, up, c3, c4, G)
     ok = _gi_support.get(key)
     if ok is None:
@@ -98,43 +96,26 @@ def _conv(x, w, bias, padding, stride, dilation, bias_nc=None, residual=None, up
     assert y.shape == (n, k, ho, wo) and y.layout == "nhwc"
     nb = hip.tf_conv2d_fused_workspace(n, h, wd, c1, c2, k, r, s, stride[0], padding[0], up, c3, c4)
     ws = workspace(nb)
-    bnc_stride = 0
-    if bias_nc is not None:
-        bnc_stride = k if bias_nc.size // k > 1 else 0
     args = (y.ptr, x.ptr, x2.ptr if x2 is not None else None, w.ptr, bias.ptr if bias is not None else None,
-            bias_nc.ptr if bias_nc is not None else None, bnc_stride, residual.ptr if residual is not None else None,
-            n, h, wd, c1, c2, k, r, s, stride[0], padding[0], up, ws.ptr if ws else None, nb)
-    ex = (x3.ptr if x3 is not None else None, x4.ptr if x4 is not None else None, c3, c4)
+            bias_nc.ptr if bias_nc is not None else None, bias_nc_stride(bias_nc, k), residual.ptr if residual is not None else None,
+            n, h, wd, c1, c2, k, r, s, stride[0], padding[0], up, ws.ptr if ws else None, nb,
+            x3.ptr if x3 is not None else None, x4.ptr if x4 is not None else None, c3, c4)
+    # gn: the GroupNorm(gn) that consumes y next gets its statistics from this conv's epilogue (when the shape allows).  The three entries take
+    # the same arguments up to here; each adds its own behind them
+    st = OutputStats(n, gn)
     if gi is not None:
-        pb, part, chunks = 0, None, ctypes.c_int(0)
-        if gn:
-            pb = hip.tf_conv2d_gn_partial_bytes(n, gn)
-            part = workspace(pb)
-        hip.tf_conv2d_gn_16(dt, *args, *ex, part.ptr if part is not None else None, pb, gn, ctypes.byref(chunks), *gi, 1 if gn_in[1] else 0, _sh())
-        if chunks.value > 0:
-            y.gn = (part, chunks.value, gn)
+        hip.tf_conv2d_gn_16(dt, *args, *st.args, *gi, 1 if gn_in[1] else 0, _sh())
         y._base = (y._base, x.gn[0], x2.gn[0] if x2 is not None else None)   # the statistics stay referenced while the launch is queued
     elif gn and out_norm is not None and config.fuse_reduce_norm and out_norm[0].num_groups == gn and out is None:
         # ... and, behind a split-K shape, is applied by the reduce kernel as well: z rides along with y
-        pb = hip.tf_conv2d_gn_partial_bytes(n, gn)
-        part, chunks, zw = workspace(pb), ctypes.c_int(0), ctypes.c_int(0)
-        z = DeviceArray.empty((n, k, ho, wo), x.dtype, "nhwc")
-        nm = out_norm[0]
-        hip.tf_conv2d_fused_norm_16(dt, *args, *ex, part.ptr, pb, gn, ctypes.byref(chunks), z.ptr, nm.weight.ptr if nm.weight is not None else None,
+        nm, z, zw = out_norm[0], DeviceArray.empty((n, k, ho, wo), x.dtype, "nhwc"), ctypes.c_int(0)
+        hip.tf_conv2d_fused_norm_16(dt, *args, *st.args, z.ptr, nm.weight.ptr if nm.weight is not None else None,
                                      nm.bias.ptr if nm.bias is not None else None, float(nm.eps), 1 if out_norm[1] else 0, ctypes.byref(zw), _sh())
-        if chunks.value > 0:
-            y.gn = (part, chunks.value, gn)
         if zw.value:
             y.normed = (nm, bool(out_norm[1]), z)
-    elif gn:
-        # the GroupNorm(gn) that consumes y next gets its statistics from this conv's epilogue (when the shape allows)
-        pb = hip.tf_conv2d_gn_partial_bytes(n, gn)
-        part, chunks = workspace(pb), ctypes.c_int(0)
-        hip.tf_conv2d_fused_16(dt, *args, *ex, part.ptr, pb, gn, ctypes.byref(chunks), _sh())
-        if chunks.value > 0:
-            y.gn = (part, chunks.value, gn)
     else:
-        hip.tf_conv2d_fused_16(dt, *args, *ex, None, 0, 0, None, _sh())
+        hip.tf_conv2d_fused_16(dt, *args, *st.args, _sh())
+    st.attach(y)
     return y
 
 
@@ -198,32 +179,10 @@ def conv2d_bf16(x, w, bias, padding, stride, dilation, residual=None, bias_nc=No
     ho = ((h << up) + 2 * padding[0] - r) // stride[0] + 1
     wo = ((wd << up) + 2 * padding[1] - s_) // stride[1] + 1
     y = DeviceArray.empty((n, k, ho, wo), x.dtype, "nhwc")
-    bnc_stride = 0
-    if bias_nc is not None:
-        bnc_stride = k if bias_nc.size // k > 1 else 0
     hip.tf_conv2d_bf16(y.ptr, x.ptr, x2.ptr if x2 is not None else None, w.ptr, bias.ptr if bias is not None else None,
-                       bias_nc.ptr if bias_nc is not None else None, bnc_stride,
+                       bias_nc.ptr if bias_nc is not None else None, bias_nc_stride(bias_nc, k),
                        residual.ptr if residual is not None else None, n, h, wd, c, c2, k, r, s_, stride[0], padding[0], up, _sh())
     return y
-
-
-def _conv_small_c_bf16(x, w, bias, padding, stride, cache):
-    """Cin % 8 != 0 on bfloat16 (the 4-channel conv_in of the bfloat16 step): im2col (a 2-byte copy: the same kernel) to K padded to 64, then a
-    1x1 bfloat16 conv over the patch image."""
-    n, c, h, wd = x.shape
-    k, _, r, s = w.shape
-    kk = r * s * c
-    kpad = (kk + 63) // 64 * 64
-    ho = (h + 2 * padding[0] - r) // stride[0] + 1
-    wo = (wd + 2 * padding[1] - s) // stride[1] + 1
-    key = (w.wkey, kpad, "bf16")
-    if cache.get("key") != key:
-        wp = DeviceArray.zeros((k, kpad), w.dtype, "row")
-        hip.tf_memcpy_2d_async(wp.ptr, kpad * 2, w.ptr, kk * 2, kk * 2, k, _sh())
-        cache["key"], cache["w"] = key, wp
-    col = DeviceArray.empty((n * ho * wo, kpad), x.dtype, "row")
-    hip.tf_im2col_nhwc_f16(col.ptr, x.ptr, n, h, wd, c, r, s, stride[0], padding[0], kpad, _sh())
-    return conv2d_bf16(col.view((n, kpad, ho, wo), "nhwc"), cache["w"].view((k, kpad, 1, 1), "nhwc"), bias, [0, 0], [1, 1], [1, 1])
 
 
 def pad_image(x, left, right, top, bottom):

@@ -19,7 +19,7 @@ import numpy as np
 
 from ..attention.attention import SpatialTransformer, _concat_rows
 from ..ff.group_norm import GroupNorm
-from ..ff.linear import Linear, gemv_f16, linear_any, linear_bf16, linear_f16, to_f16
+from ..ff.linear import Linear, gemv_f16, linear_f16
 from ..native import hip
 from .. import config
 from ..storage.tensor import Branch, DeviceArray, Tensor, _sh, asarray, bfloat16, is_bfloat16
@@ -174,7 +174,7 @@ class UNetModel:
         """Every cross-attention's K|V projection of the (stacked) context as ONE GEMM (attention/attention.py:35-36 for all 16 blocks):
         depends on the context alone, so a sampler computes it when the context changes, not once per step."""
         bt = self._prepare()
-        return linear_any(context, bt["kv_w"]) if bt["kv_w"] is not None else None
+        return linear_f16(context, bt["kv_w"]) if bt["kv_w"] is not None else None
 
     def weights_key(self):
         """Identity of everything time_embedding_all / context_kv depend on: a cached row is stale once any of these weights is replaced."""
