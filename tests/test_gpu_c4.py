@@ -110,6 +110,36 @@ def test_c4_linear_with_folded_layer_norm(tf, kern, m, n, k, act):
     close(got, want)
 
 
+@pytest.mark.parametrize("m,act", [(27600, 0), (55200, 1)])
+def test_c4_layer_norm_fold_with_chunked_walk(tf, kern, m, act):
+    """The LayerNorm fold on a chunked tile walk: with the n-fastest order the launchers give a block chunks of 2 or 4 consecutive tiles while that
+    still leaves 8 (c4) or 4 (c8) chunks per CU, and the kernel reuses a row block's statistics for the following tiles of the
+    chunk.  K = 64, packed N = 2432: 19 column tiles, an odd count, so chunks straddle row blocks and the statistics are recomputed mid-chunk.
+    Both M are ragged for both tile heights."""
+    from oracle import ops as O
+    from tinyfusers_amd.ff.layer_norm import LayerNorm
+    from tinyfusers_amd.ff.linear import fold_layer_norm, linear_ln_f16
+    from tinyfusers_amd.ff.nn import GEGLU
+    # tile counts on a chip of 256 CUs (the chunk thresholds scale with the CU count): m = 27600: 216 x 19 = 4104 (c4) / 108 x 19 = 2052 (c8) -> chunk 2;
+    # m = 55200: 432 x 19 = 8208 (c4) / 216 x 19 = 4104 (c8) -> chunk 4
+    k, n_packed = 64, 2432
+    x = rnd("cck.x", (m, k), 1.5) + 0.7
+    g, b = 1 + rnd("cck.g", (k,), 0.1), rnd("cck.b", (k,), 0.1)
+    ln = LayerNorm(k); ln.weight = dev(tf, g); ln.bias = dev(tf, b)
+    xn = O.layer_norm(x, g, b)
+    w, bias = rnd("cck.w", (n_packed, k), k ** -0.5), rnd("cck.bias", (n_packed,), 0.1)
+    with forced(kern):
+        if act == 0:
+            r = rnd("cck.r", (m, n_packed))
+            got = linear_ln_f16(dev(tf, x), fold_layer_norm(dev(tf, w), dev(tf, bias), ln), ln.eps, residual=dev(tf, r)).numpy()
+            want = (O.linear(xn, w, bias) + torch.from_numpy(r)).numpy()
+        else:
+            ge = GEGLU(k, n_packed // 2, init=False); ge.proj.weight = dev(tf, w); ge.proj.bias = dev(tf, bias)
+            got = ge(dev(tf, x), ln=ln).numpy()
+            want = O.geglu(xn, w, bias).numpy()
+    close(got, want)
+
+
 @pytest.mark.parametrize("n,c1,c2,hw,cout", [(2, 128, 64, 32, 320), (2, 320, 0, 32, 320), (3, 128, 0, 24, 128), (2, 64, 64, 32, 192)])
 def test_c4_conv1x1(tf, kern, n, c1, c2, hw, cout):
     """A 1x1 / stride 1 convolution is the same GEMM; the concat input is a second K segment with its own row pitch."""

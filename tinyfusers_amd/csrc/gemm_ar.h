@@ -1,7 +1,7 @@
 // Part of the implicit-GEMM family of csrc/gemm.hip (see its head comment); split into translation units so that the
 // instances compile in parallel.
 #pragma once
-#include "gemm_common.h"
+#include "gemm_shortk.h"
 
 // =====================================================================================================================
 // ACTIVATION-RESIDENT short-K kernel (round 5, variant 8): Linear / 1x1 convolution with K = 256 or 320 and no residual -- at SD's first level the GEGLU projection,
@@ -24,6 +24,9 @@
 //     panel's K tile k replaces the old one right behind the last step that read it (ring depth 4 <= K tiles 4 / 5) -- no drain at the seam;
 //   * the row statistics of the LayerNorm fold come from the fragments of the panel's first tile, each wave for its own 64 rows (no exchange).
 // LDS: panel 80 KiB + ring 64 KiB + patches 16 KiB = all 160 KiB.  Launches: k_gemm_c4's (c4_ok) with K = 256 / 320 and no residual.
+// This file: the loader / consumer split, the ring protocol across tiles and panels, the pipelined quarter store and the contiguous-run arithmetic.  From gemm_shortk.h
+// (shared with k_gemm_c4 / k_gemm_c8): the n-fastest decode, the staging rows and LDS-DMA of a K tile (SkStager: the loaders are the four staging waves), the half-step
+// reads / MFMAs / row sums, the bias request, the LayerNorm fold and the rounding of a quarter.
 //
 // Diagnostic build 3 (python -m tinyfusers_amd.build --tag stamp3 -DTF_IGEMM_STAMP=3; tools/ar_stamp.py): cycle sums (s_memtime) of consumer wave 0 and loader wave 4.
 #ifndef TF_AR_EXP
@@ -51,7 +54,8 @@ __global__ void __launch_bounds__(512, 1) k_gemm_ar(const GemmP p) {
   if (t0 >= ntiles) return;
   const int t1 = t0 + p.c4_chunk < ntiles ? t0 + p.c4_chunk : ntiles;
   const int G = (t1 - t0) * nt;                           // K steps of the run: step g = K tile g % nt of tile t0 + g / nt, weights in ring slot g % NS
-  const int tm0 = t0 / ntn, tn0 = t0 - tm0 * ntn;
+  int tm0, tn0;
+  sk_decode(t0, 0, p.ntm, ntn, tm0, tn0);                 // (launched with the n-fastest order only)
   auto barrier = [&]() {
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
@@ -67,45 +71,20 @@ __global__ void __launch_bounds__(512, 1) k_gemm_ar(const GemmP p) {
   if (wid >= 4) {
     // =========================== loader waves: the weight stream, the panel images where the run enters a panel, and the stores ===========================
     const int lw = wid - 4;
-    const int sub = lane >> 3;
-    const int cs = (lane & 7) ^ ((4 * (lw & 1) + (sub >> 1)) & 7);        // source chunk of this lane's 16 bytes (the LDS image is lane-linear; pieces of a wave are 4 apart)
-    const i4v rs_x1 = raw_rsrc(p.x, p.x_bytes), rs_x2 = raw_rsrc(p.x2 ? p.x2 : p.x, p.x2_bytes), rs_w = raw_rsrc(p.w, p.w_bytes);
-    const int C1_ = p.C1, C2_ = p.C2;
-    int am[4];
-    unsigned gw[4];
-    auto rows_a = [&](int m0) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { const int m = m0 + 8 * (lw + 4 * i) + sub; am[i] = m < M_ ? m : -1; }
-    };
-    auto rows_w = [&](int n0) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { const int n = n0 + 8 * (lw + 4 * i) + sub; gw[i] = n < N_ ? (unsigned)(n * K_ + cs * 8) * 2u : TF_OOB; }
-    };
+    SkStager<4, 4, 4> sg(p, lw, lane);                    // four staging waves: 4 weight pieces per wave and K step, 4 activation pieces where a panel image is due
     int l_tm = tm0, l_tn = tn0, l_kt = 0, l_g = 0;
     bool l_new = true;                                    // the cursor's tile is the first one of its panel in this run: its stages carry the panel images
-    rows_a(l_tm * BM); rows_w(l_tn * BN);
+    sg.rows_a(l_tm * BM); sg.rows_w(l_tn * BN);
     auto issue = [&]() -> int {                           // stage l_g (if the run has one); returns the pieces this wave issued
       if (l_g >= G || (TF_AR_EXP & 8)) return 0;
-      const unsigned wbase = lds0 + RING + (unsigned)(l_g & (NS - 1)) * IMG + (unsigned)lw * 1024u;
       int q = 4;
-      if (l_new) {
-        const int c = l_kt * 64;
-        const bool second = c >= C1_;
-        const int ld = second ? C2_ : C1_;
-        const int cc = (second ? c - C1_ : c) + cs * 8;
-        const i4v rs = second ? rs_x2 : rs_x1;
-        const unsigned abase = lds0 + (unsigned)l_kt * IMG + (unsigned)lw * 1024u;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) dma16(rs, am[i] >= 0 ? (unsigned)(am[i] * ld + cc) * 2u : TF_OOB, abase + (unsigned)i * 4096u);
-        q = 8;
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) dma16_w(rs_w, gw[i] != TF_OOB ? gw[i] + (unsigned)l_kt * 128u : TF_OOB, wbase + (unsigned)i * 4096u);
+      if (l_new) { sg.stage_a(l_kt, lds0 + (unsigned)l_kt * IMG); q = 8; }
+      sg.stage_w(l_kt, lds0 + RING + (unsigned)(l_g & (NS - 1)) * IMG);
       ++l_g;
       if (++l_kt == nt) {
         l_kt = 0;
-        if (++l_tn == ntn) { l_tn = 0; ++l_tm; rows_a(l_tm * BM); l_new = true; } else l_new = false;
-        rows_w(l_tn * BN);
+        if (++l_tn == ntn) { l_tn = 0; ++l_tm; sg.rows_a(l_tm * BM); l_new = true; } else l_new = false;
+        sg.rows_w(l_tn * BN);
       }
       return q;
     };
@@ -195,7 +174,7 @@ __global__ void __launch_bounds__(512, 1) k_gemm_ar(const GemmP p) {
   // =========================== consumer waves ===========================
   const int wm = wid & 1, wn = wid >> 1;
   const int lr = lane & 15, lg = lane >> 4;
-  const int fo = lr * 128 + ((lg ^ ((lr >> 1) & 7)) << 4);
+  const int fo = sk_frag_off(lane);
   const int xo = wm * 64 * 128 + fo, wo_ = RING + wn * 64 * 128 + fo;
   // this lane's 8 bytes of a patch row: row lr, logical 16-byte chunk 2 i + (lg >> 1) (GEGLU: 2 (i >> 1) + (lg >> 1)) -> physical chunk ^ ((lr >> 1) & 7)
   const unsigned pw0 = lds0 + PATCH0 + (unsigned)wid * 2u * PATCH + (unsigned)(lr * 128 + (lg & 1) * 8);
@@ -227,15 +206,7 @@ __global__ void __launch_bounds__(512, 1) k_gemm_ar(const GemmP p) {
     need_stats = LNF && c_tm != stat_tm;
     // bias (and LayerNorm column sums) of this lane's columns: requested now, consumed behind the K loop -- the only vector-memory instructions of these waves
     // (through the scalar cache instead -- s_load into SGPRs, v_cndmask per lane -- the tile end took 1000 cycles longer: measured, profiles/r05_ar_stamps.txt)
-    const int nb = c_tn * BN + wn * 64;
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      braw[i] = (h4){(half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f}; cq[i] = (f4){0.f, 0.f, 0.f, 0.f};
-      int n = nb + i * 16 + lg * 4;
-      n = n + 3 < N_ ? n : 0;                              // columns beyond N are never stored: any readable address will do
-      if (p.bias) braw[i] = *reinterpret_cast<const h4*>(p.bias + n);
-      if constexpr (LNF) cq[i] = *reinterpret_cast<const f4*>(p.ln_colsum + n);
-    }
+    sk_request<LNF>(p, c_tn * BN + wn * 64, lg, braw, cq);
   };
   // one 32-deep half (f) of a K step's fragments: the two halves are the software pipeline -- half f = 1 of step g is read while half 0 multiplies, half 0 of
   // step g + 1 while half 1 multiplies (64 fragment registers; whole steps double-buffered would be 128 next to the 64 accumulators: scratch)
@@ -245,27 +216,17 @@ __global__ void __launch_bounds__(512, 1) k_gemm_ar(const GemmP p) {
       for (int i = 0; i < NI; ++i) { asm volatile("" : "+v"(wf[i])); asm volatile("" : "+v"(xf[i])); }
       return;
     }
-    const char* sa = smem + kt * IMG;
-    const char* sw = smem + slot * IMG;
-#pragma unroll
-    for (int i = 0; i < NI; ++i) wf[i] = *reinterpret_cast<const h8*>(sw + ((wo_ + i * 2048) ^ (f * 64)));
-#pragma unroll
-    for (int j = 0; j < MJ; ++j) xf[j] = *reinterpret_cast<const h8*>(sa + ((xo + j * 2048) ^ (f * 64)));
+    sk_read_half(wf, smem + slot * IMG, wo_, f);
+    sk_read_half(xf, smem + kt * IMG, xo, f);
   };
-  auto stats_half = [&](h8 (&xf)[MJ]) {                   // row statistics of the panel from the fragments of its first tile: this wave's own 64 rows
-#pragma unroll
-    for (int j = 0; j < MJ; ++j) dot2_stats<BF>(xf[j], ls[j], lq[j]);
-  };
+  auto stats_half = [&](h8 (&xf)[MJ]) { sk_stats_half<BF>(xf, ls, lq); };   // row statistics of the panel from the fragments of its first tile: this wave's own 64 rows
   auto mma_half = [&](h8 (&wf)[NI], h8 (&xf)[MJ]) {
     if (TF_AR_EXP & 2) {
 #pragma unroll
       for (int i = 0; i < NI; ++i) { asm volatile("" ::"v"(wf[i])); asm volatile("" ::"v"(xf[i])); }
       return;
     }
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-#pragma unroll
-      for (int j = 0; j < MJ; ++j) acc[i][j] = mfma16<BF>(wf[i], xf[j], acc[i][j]);
+    sk_mma_half<BF>(wf, xf, acc);
   };
   // one half step = 16 MFMAs on one fragment half + the 8 ds_read_b128 of the other, interleaved (the reads in the shadow of the first eight MFMAs)
 #define AR_INTERLEAVE() do { \
@@ -286,52 +247,25 @@ __global__ void __launch_bounds__(512, 1) k_gemm_ar(const GemmP p) {
   };
   // the end of a tile: LayerNorm fold / bias / GEGLU on the accumulators, rounded into pend
   auto tile_end = [&](bool more) {
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      asm volatile("" : "+v"(braw[i]));                    // (the values are used from here on: nothing of this moves in front of the K loop)
-      if constexpr (LNF) asm volatile("" : "+v"(cq[i]));
-    }
+    sk_request_pin<LNF>(braw, cq);
     if constexpr (LNF) {
-      if (need_stats) {
+      if (need_stats) {                                    // each wave for its own 64 rows: no exchange
         const float invK = 1.0f / (float)K_;
 #pragma unroll
         for (int j = 0; j < MJ; ++j) {
-          float s_ = ls[j], q_ = lq[j];
-          s_ += __shfl_xor(s_, 16, 64); q_ += __shfl_xor(q_, 16, 64);
-          s_ += __shfl_xor(s_, 32, 64); q_ += __shfl_xor(q_, 32, 64);
-          ln_mean[j] = s_ * invK;
-          ln_rstd[j] = rsqrtf(fmaxf(q_ * invK - ln_mean[j] * ln_mean[j], 0.f) + p.ln_eps);
+          sk_row_reduce(ls[j], lq[j]);
+          sk_mean_rstd(ls[j], lq[j], invK, p.ln_eps, ln_mean[j], ln_rstd[j]);
         }
         stat_tm = c_tm;
       }
-#pragma unroll
-      for (int j = 0; j < MJ; ++j)
-#pragma unroll
-        for (int i = 0; i < NI; ++i) acc[i][j] = ln_rstd[j] * (acc[i][j] - ln_mean[j] * cq[i]);
     }
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-#pragma unroll
-      for (int j = 0; j < MJ; ++j) acc[i][j] += (f4){e2f<BF>(braw[i][0]), e2f<BF>(braw[i][1]), e2f<BF>(braw[i][2]), e2f<BF>(braw[i][3])};
+    sk_fold<LNF, BF>(acc, ln_mean, ln_rstd, cq, braw);
 #pragma unroll
     for (int j = 0; j < MJ; ++j) {
-      if constexpr (geglu) {
+      h4 o[NP];
+      sk_round_quarter<geglu, BF>(acc, j, o);
 #pragma unroll
-        for (int i = 0; i < NI; i += 2) {
-          h4 o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = f2e<BF>(acc[i][j][e] * gelu_f(acc[i + 1][j][e]));
-          pend[i >> 1][j] = o;
-        }
-      } else {
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-          h4 o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = f2e<BF>(acc[i][j][e]);
-          pend[i][j] = o;
-        }
-      }
+      for (int i = 0; i < NP; ++i) pend[i][j] = o[i];
     }
     have_pend = true;
     if (more) { if (++c_tn == ntn) { c_tn = 0; ++c_tm; } tile_begin(); }
