@@ -58,7 +58,7 @@ def sanitizer_env(base=None):
 
 def build(force=False, verbose=False, ablation=False, tag=None, defs=(), asan_host=False):
     """tag / defs: an EXPERIMENTAL build for same-box A/B runs (tools/ab_lib.sh, TF_LIB_PATH): the sources compiled with extra -D definitions into
-    lib/<tag>/ and lib/libtinyfusers_hip_<tag>.so (`python -m tinyfusers_amd.build --tag prio1 -DTF_PP_PRIO=1`); never loaded by default."""
+    lib/<tag>/ and lib/libtinyfusers_hip_<tag>.so (`python -m tinyfusers_amd.build --tag wnt -DTF_W_NT=1`); never loaded by default."""
     objdir = os.path.join(LIBDIR, "asan") if asan_host else os.path.join(LIBDIR, "ablation") if ablation else os.path.join(LIBDIR, tag) if tag else LIBDIR
     lib = LIB_ASAN if asan_host else LIB_ABLATION if ablation else os.path.join(LIBDIR, f"libtinyfusers_hip_{tag}.so") if tag else LIB
     os.makedirs(objdir, exist_ok=True)

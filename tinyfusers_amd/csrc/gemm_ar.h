@@ -54,8 +54,8 @@ __global__ void __launch_bounds__(512, 1) k_gemm_ar(const GemmP p) {
   if (t0 >= ntiles) return;
   const int t1 = t0 + p.c4_chunk < ntiles ? t0 + p.c4_chunk : ntiles;
   const int G = (t1 - t0) * nt;                           // K steps of the run: step g = K tile g % nt of tile t0 + g / nt, weights in ring slot g % NS
-  int tm0, tn0;
-  sk_decode(t0, 0, p.ntm, ntn, tm0, tn0);                 // (launched with the n-fastest order only)
+  const TileMN tmn0 = tile_decode(t0, 0, p.ntm, ntn);      // (launched with the n-fastest order only)
+  const int tm0 = tmn0.m, tn0 = tmn0.n;
   auto barrier = [&]() {
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");

@@ -46,9 +46,8 @@ __global__ void __launch_bounds__(256, 2) k_gemm_c4(const GemmP p) {
   // all four waves stage: activation pieces wid + 4 i (i < 4), weight pieces likewise -- 8 LDS-DMA pieces per wave and K tile
   SkStager<4, 4, 4> sg(p, wid, lane);
   auto setup = [&](int tile, int& m0, int& n0) {
-    int tm, tn;
-    sk_decode(tile, p.order, ntm, ntn, tm, tn);
-    m0 = tm * BM; n0 = tn * BN;
+    const TileMN t = tile_decode(tile, p.order, ntm, ntn);
+    m0 = t.m * BM; n0 = t.n * BN;
     sg.rows_a(m0); sg.rows_w(n0);
   };
   auto stage = [&](int slot, int kt) {                    // K tile kt of the tile whose rows are in sg

@@ -44,9 +44,8 @@ __global__ void __launch_bounds__(512, 2) k_gemm_c8(const GemmP p) {
   // all eight waves stage: activation pieces wid + 8 i (i < 4), weight pieces wid + 8 i (i < 2) -- LPT pieces per wave and K tile
   SkStager<8, 4, 2> sg(p, wid, lane);
   auto setup = [&](int tile, int& m0, int& n0) {
-    int tm, tn;
-    sk_decode(tile, p.order, ntm, ntn, tm, tn);
-    m0 = tm * BM; n0 = tn * BN;
+    const TileMN t = tile_decode(tile, p.order, ntm, ntn);
+    m0 = t.m * BM; n0 = t.n * BN;
     sg.rows_a(m0); sg.rows_w(n0);
   };
   auto stage = [&](int slot, int kt) {                    // K tile kt of the tile whose rows are in sg

@@ -117,6 +117,21 @@ static void fast_div_magic(unsigned d, unsigned* mul, unsigned* shr) {
   *mul = (unsigned)((((1ull << l) - d) << 32) / d + 1);
   *shr = l;
 }
+// ---- block -> work item ------------------------------------------------------------------------------------------------------
+// XCD-aware work order: blocks b and b+8 share an XCD (and its L2), so every XCD gets a contiguous run of the nblk work items
+// (bijective remap).  Speed only: any order is correct.
+__device__ __forceinline__ int xcd_order(int bid, int nblk) {
+  int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+// tile index -> (m, n) tile coordinates (returned, not written through references: that form compiles the callers to another instruction stream).  order 0 = n fastest (neighbours re-use the same activation rows and sweep the weight tiles), 1 = m fastest
+// (neighbours share one weight tile: each weight byte leaves HBM / Infinity Cache once); the host picks it per shape (an autotuned knob).
+struct TileMN { int m, n; };
+__device__ __forceinline__ TileMN tile_decode(int tile, int order, int ntm, int ntn) {
+  TileMN t;
+  if (order == 0) { t.m = tile / ntn; t.n = tile - t.m * ntn; } else { t.n = tile / ntm; t.m = tile - t.n * ntm; }
+  return t;
+}
 #define TF_OOB 0x80000000u   // voffset beyond every tensor: the buffer range check returns 0 -> zero padding in LDS
 
 // LDS-DMA: 16 B per lane, LDS destination = wave-uniform base + lane*16; out-of-range lanes write zeros
@@ -677,6 +692,13 @@ __device__ __forceinline__ void dma16_w(i4v rsrc, unsigned voffset_bytes, unsign
 __device__ __forceinline__ void dma16(i4v rsrc, unsigned voffset_bytes, unsigned lds_base) {
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
                :: "s"(__builtin_amdgcn_readfirstlane((int)lds_base)), "v"(voffset_bytes), "s"(rsrc) : "memory");   // M0 has no other user in this kernel
+}
+// 4 / 2 bytes per lane, 4 bytes of LDS per lane (the E8M0 scale bytes of the block-scaled e4m3 kernels: one lane per row)
+__device__ __forceinline__ void dma4(i4v rsrc, unsigned voffset_bytes, unsigned lds_base) {
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dword %1, %2, 0 offen lds" :: "s"(__builtin_amdgcn_readfirstlane((int)lds_base)), "v"(voffset_bytes), "s"(rsrc) : "memory");
+}
+__device__ __forceinline__ void dma2(i4v rsrc, unsigned voffset_bytes, unsigned lds_base) {
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_ushort %1, %2, 0 offen lds" :: "s"(__builtin_amdgcn_readfirstlane((int)lds_base)), "v"(voffset_bytes), "s"(rsrc) : "memory");
 }
 
 

@@ -40,23 +40,12 @@ __global__ void __launch_bounds__(512, WIDE ? 4 : 2) k_igemm(const GemmP p) {
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const bool loader = wid >= 4;
   const int w4 = wid & 3;
-  // XCD-aware work order: blocks b and b+8 share an XCD (and its L2), so every XCD gets a contiguous run of work items
-  // (bijective remap).  Inside a run either n is fastest (neighbours re-use the same activation rows and sweep the
-  // weight tiles) or m is fastest (neighbours share one weight tile: each weight byte leaves HBM / Infinity Cache once);
-  // the host picks the order per shape (it is one of the autotuned knobs).  Speed only: any order is correct.
   const int ntiles = p.ntm * p.ntn;
   const int nblk = ntiles * p.splitk;
-  int bid = blockIdx.x;
-  {
-    int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int bid = xcd_order(blockIdx.x, nblk);
   const int split = bid / ntiles;
-  const int tid_ = bid - split * ntiles;
-  int tile_m, tile_n;
-  if (p.order == 0) { tile_m = tid_ / p.ntn; tile_n = tid_ - tile_m * p.ntn; }
-  else { tile_n = tid_ / p.ntm; tile_m = tid_ - tile_n * p.ntm; }
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
+  const TileMN tmn = tile_decode(bid - split * ntiles, p.order, p.ntm, p.ntn);
+  const int m0 = tmn.m * BM, n0 = tmn.n * BN;
   const int kt_begin = split * p.ktiles_per_split;
   const int kt_end = min(p.ktiles, kt_begin + p.ktiles_per_split);
 #if TF_IGEMM_STAMP

@@ -40,17 +40,10 @@ __global__ void __launch_bounds__(512, 2) k_igemm8(const GemmP p) {
   const int w4 = wid & 3;
   const int ntiles = p.ntm * p.ntn;
   const int nblk = ntiles * p.splitk;
-  int bid = blockIdx.x;
-  {
-    int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;      // XCD-aware order, as in k_igemm
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int bid = xcd_order(blockIdx.x, nblk);
   const int split = bid / ntiles;
-  const int tid_ = bid - split * ntiles;
-  int tile_m, tile_n;
-  if (p.order == 0) { tile_m = tid_ / p.ntn; tile_n = tid_ - tile_m * p.ntn; }
-  else { tile_n = tid_ / p.ntm; tile_m = tid_ - tile_n * p.ntm; }
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
+  const TileMN tmn = tile_decode(bid - split * ntiles, p.order, p.ntm, p.ntn);
+  const int m0 = tmn.m * BM, n0 = tmn.n * BN;
   const int kt_begin = split * p.ktiles_per_split;
   const int kt_end = min(p.ktiles, kt_begin + p.ktiles_per_split);
   const int nt = kt_end - kt_begin;

@@ -3,9 +3,7 @@
 
 template <int BN, int NP, bool FASTA, bool F8 = false, bool H2 = false, int BM = 256, bool LNF = false>
 static int launch_pp2(const GemmP& p, hipStream_t st) {
-  constexpr int STAGE = (BM + BN) * 128, NS = (163840 / STAGE) >= 3 ? 3 : 2;
-  constexpr int ring = NS * STAGE + (F8 ? NS * (H2 ? 2 : 1) * 1024 : 0), scratch = 4 * (BM / 4) * (BN / 2 + 4) * 4, tail = (BM / 2) * 8 + 4 * BN * 8 + 3 * BN * 4;   // (+ the bias / time-embedding table)
-  constexpr int smem = ring > scratch + tail ? ring : scratch + tail;
+  constexpr int smem = PpLds<BM, BN, F8, H2>::total;        // the layout the kernel reads (gemm_pingpong.h)
   static_assert(smem <= 163840, "LDS budget");
 #ifdef TF_ABLATION
   if constexpr (!F8 && FASTA && BM == 256 && !LNF) {       // ablation build (tools/pp_dbg.py): the lean-addressing fp16 instances only

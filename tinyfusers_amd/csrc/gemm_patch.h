@@ -32,17 +32,10 @@ __global__ void __launch_bounds__(512, 2) k_igemm_patch(const GemmP p) {
   const int w4 = wid & 3;
   const int ntiles = p.ntm * p.ntn;
   const int nblk = ntiles * p.splitk;
-  int bid = blockIdx.x;
-  {
-    int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;      // XCD-aware order, as in k_igemm
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int bid = xcd_order(blockIdx.x, nblk);
   const int split = bid / ntiles;
-  const int tid_ = bid - split * ntiles;
-  int tile_m, tile_n;
-  if (p.order == 0) { tile_m = tid_ / p.ntn; tile_n = tid_ - tile_m * p.ntn; }
-  else { tile_n = tid_ / p.ntm; tile_m = tid_ - tile_n * p.ntm; }
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
+  const TileMN tmn = tile_decode(bid - split * ntiles, p.order, p.ntm, p.ntn);
+  const int m0 = tmn.m * BM, n0 = tmn.n * BN;
   const int kt_begin = split * p.ktiles_per_split;
   const int kt_end = min(p.ktiles, kt_begin + p.ktiles_per_split);
   const int nt = kt_end - kt_begin;
@@ -58,7 +51,7 @@ __global__ void __launch_bounds__(512, 2) k_igemm_patch(const GemmP p) {
     // =============================== LOADER WAVES ===============================================
     const rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
     const int sub = lane >> 3;
-    const int cs = (lane & 7) ^ ((4 * (w4 & 1) + (sub >> 1)) & 7);      // source chunk of this lane (see k_igemm)
+    const int cs = (lane & 7) ^ ((4 * (w4 & 1) + (sub >> 1)) & 7);      // source chunk of this lane (gemm_common.h's head comment)
     unsigned gw[BNP];
     int ga[AXP], pp[TF_PATCH_PPW];
 #pragma unroll

@@ -1,7 +1,8 @@
 // Part of the implicit-GEMM family of csrc/gemm.hip (see its head comment); split into translation units so that the
-// instances compile in parallel.
+// instances compile in parallel.  What this kernel shares with its patch form k_igemm_pp3 (gemm_pp3.h) -- the LDS layout, weight staging, source
+// descriptors, the MFMA block, the weight scales, the bias prefetch and the epilogue -- is gemm_pingpong.h; here are the ring protocol and the gather.
 #pragma once
-#include "gemm_common.h"
+#include "gemm_pingpong.h"
 
 // =====================================================================================================================
 // PING-PONG variant for problems that fill the chip with 256-row tiles (more images per GPU, 96 x 96 latents: BASELINE config 5):
@@ -21,8 +22,8 @@
 //     the earliest place a DMA into that slot is issued.
 //   LDS-DMA is issued from inline asm (M0 + buffer_load ... lds): the compiler does not see an LDS write and therefore puts no
 //     s_waitcnt vmcnt(0) in front of the fragment reads; all vmcnt bookkeeping is the counted waits above.
-// Epilogue: the accumulators go through the 2 x 2-wave-tile scratch of k_igemm in two passes of BM / 2 rows (igemm_epilogue<BM / 2, BN>), so
-// bias / time embedding / residual / GEGLU / split-K partials / GroupNorm statistics are the shared code, chunked as a 128-row tile.
+// Epilogue: pp_epilogue -- two passes of BM / 2 rows through the 2 x 2-wave-tile scratch of k_igemm, so bias / time embedding / residual / GEGLU /
+// split-K partials / GroupNorm statistics are the shared code.
 // Channel counts on the 64 grid (taps and concat sources advance as wave-uniform scalars), no LayerNorm fold, no input GroupNorm.
 // NP = half-phases per K tile and wave group: 2 = one per 32-deep k-step (fragments of one k-step in registers), 1 = the whole K tile per
 //   phase (both k-steps' fragments in registers, half the barriers; needs the 3-slot ring: with two slots the second half would issue a
@@ -37,7 +38,7 @@
 //   k = 16 lg .. 16 lg + 15, registers 4-7 hold k = 64 + 16 lg ..; tools/probe_mx.hip).  ACTIVATIONS are block scaled ("MX", common.h: mx_quant8):
 //   every 32 consecutive channels of a pixel share one E8M0 byte, stored behind the tensor's codes; the instruction takes the scale of K block b
 //   (k = 32 b .. 32 b + 31 of the 128) from lane group b, byte 0 of the scale operand (the same probe).  The four bytes of a (row, K tile) travel
-//   with the tile: waves 4-7 DMA them (buffer_load_dword / _ushort ... lds, one lane per row, 4 bytes of LDS per lane) into a small table
+//   with the tile: waves 4-7 DMA them (dma4 / dma2: buffer_load_dword / _ushort ... lds, one lane per row, 4 bytes of LDS per lane) into a small table
 //   behind the ring, slot by slot like the tile itself, and a lane reads the byte of (its row, block lg) with one ds_read_u8 per fragment.
 //   WEIGHTS carry one fp32 scale per output channel (tf_pack_weight_fp8), applied to the accumulators in front of the shared epilogue; their
 //   hardware scale is 2^0.  A K tile is two 64-channel HALVES that may lie in different taps / source tensors (320 channels = 2.5 tiles): H2 =
@@ -50,15 +51,6 @@
 //   the activation FRAGMENTS the wave multiplies anyway -- lane (lr, lg) holds the 8 k-values k = 8 lg .. of row lr of every fragment, so
 //   8 v_dot2_f32_f16 per fragment (in the MFMA block's spare issue slots) keep (sum, sum of squares) of that row's share, two lane
 //   shuffles at the end complete the row -- and they end up in exactly the lanes whose accumulators belong to that row.
-#ifndef TF_PP_V2
-#define TF_PP_V2 0        // experiment switch (tagged build): 1 = one barrier per K tile, loads issued between MFMA chunks (see the tile loop)
-#endif
-#ifndef TF_PP_H2_MERGE
-#define TF_PP_H2_MERGE 1  // e4m3, channel counts off the 128 grid: one full-width load where the two slabs of a K tile are contiguous (0: always two half-masked loads)
-#endif
-#ifndef TF_PP_PRIO
-#define TF_PP_PRIO 0      // experiment switch of tools' tagged builds: 0 = s_setprio 1 around every MFMA block (shipped), 1 = static priority for waves 4-7, 2 = none
-#endif
 template <int BN, int NP, bool FASTA, bool DBG = false, bool F8 = false, bool H2 = false, int BM = 256, bool LNF = false, bool BF = false>   // BF: bfloat16 operands / outputs (gemm_k_pp16_bf16.hip)
 __global__ void __launch_bounds__(512, 2) k_igemm_pp(const GemmP p) {
   static_assert(!(BF && F8), "the e4m3 form has fp16 bias / residual / outputs");
@@ -71,11 +63,9 @@ __global__ void __launch_bounds__(512, 2) k_igemm_pp(const GemmP p) {
   static_assert(!F8 || NP == 1, "the 128-deep MFMA takes both 64-byte halves of a row at once");
   static_assert(F8 || !H2, "half-masked activation loads are the fp8 kernel's");
   static_assert(!F8 || FASTA, "the e4m3 instances use the lean addressing");
-  constexpr int SCL = F8 ? (H2 ? 2 : 1) : 0;              // scale loads per K tile of a wave that stages scales (waves 4-7)
-  constexpr int SCS = SCL * 1024;                         // bytes of a ring slot's scale table: one dword per row and half, 4 waves x 64 rows (the 192-row tile leaves the last 64 unused)
+  using L = PpLds<BM, BN, F8, H2>;                        // the LDS layout: ring slots, scale tables, the epilogue's share
+  constexpr int SCL = L::SCL, SCS = L::SCS, STAGE = L::STAGE, NS = L::NS;
   constexpr int NWG = BN / 8;                             // weight pieces (8 rows x 128 B) of a stage
-  constexpr int STAGE = (BM + BN) * 128;
-  constexpr int NS = (163840 / STAGE) >= 3 ? 3 : 2;
   constexpr int D = NS - 1;                               // K tiles in flight ahead of the one being multiplied
   constexpr int WPW = (NWG + 7) / 8;                      // weight pieces per wave (the last one only on waves < NWG % 8 where that is not 0)
   constexpr int WREM = NWG % 8;
@@ -91,17 +81,10 @@ __global__ void __launch_bounds__(512, 2) k_igemm_pp(const GemmP p) {
   const int wm = wid & 3, wn = wid >> 2;                  // wave tile: pixels 64 wm .., channels TN wn ..
   const int ntiles = p.ntm * p.ntn;
   const int nblk = ntiles * p.splitk;
-  int bid = blockIdx.x;
-  {
-    int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;      // XCD-aware order, as in k_igemm
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int bid = xcd_order(blockIdx.x, nblk);
   const int split = bid / ntiles;
-  const int tid_ = bid - split * ntiles;
-  int tile_m, tile_n;
-  if (p.order == 0) { tile_m = tid_ / p.ntn; tile_n = tid_ - tile_m * p.ntn; }
-  else { tile_n = tid_ / p.ntm; tile_m = tid_ - tile_n * p.ntm; }
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
+  const TileMN tmn = tile_decode(bid - split * ntiles, p.order, p.ntm, p.ntn);
+  const int m0 = tmn.m * BM, n0 = tmn.n * BN;
   const int kt_begin = split * p.ktiles_per_split;
   const int kt_end = min(p.ktiles, kt_begin + p.ktiles_per_split);
   const int nt = kt_end - kt_begin;
@@ -109,7 +92,7 @@ __global__ void __launch_bounds__(512, 2) k_igemm_pp(const GemmP p) {
   // ---- staging state: wave w owns activation pieces w + 8 i (i < 4) and weight pieces w + 8 i (i < WPW, below NWG)
   const i4v rs_w = raw_rsrc(p.w, p.w_bytes);
   const int sub = lane >> 3;
-  const int cs = (lane & 7) ^ ((4 * (wid & 1) + (sub >> 1)) & 7);       // source chunk of this lane: XOR swizzle on the SOURCE side (see k_igemm)
+  const int cs = (lane & 7) ^ ((4 * (wid & 1) + (sub >> 1)) & 7);       // source chunk of this lane: XOR swizzle on the SOURCE side (gemm_common.h's head comment)
   // general gather: (hi0, wi0, first pixel of the image) per piece; FASTA: (pixel index of the output position, tap-validity mask, -)
   int g_a[APW], g_b[APW], g_c[APW];
   unsigned gw[WPW];
@@ -118,43 +101,22 @@ __global__ void __launch_bounds__(512, 2) k_igemm_pp(const GemmP p) {
     const int m = m0 + 8 * (wid + 8 * i) + sub;
     g_a[i] = FASTA ? 0 : -(1 << 28); g_b[i] = 0; g_c[i] = 0;
     if (m < p.M) {
-      int img = fast_div(m, p.dv_howo_mul, p.dv_howo_shr), rem = m - img * p.HoWo;
-      int ho = fast_div(rem, p.dv_wo_mul, p.dv_wo_shr), wo = rem - ho * p.Wo;
-      if constexpr (FASTA) {
-        // stride 1, no up-sampling: input pixel of tap (r, s) = output position + (r - pad) W + (s - pad); bit r S + s of the mask tells
-        // whether it lies inside the image, bit 31 marks a live row (the extra 1x1 segment and 1x1 convolutions read the position itself)
-        g_a[i] = img * p.H * p.W + ho * p.W + wo;
-        unsigned mask = 0x80000000u;
-        for (int r = 0; r < p.S; ++r)
-          for (int s_ = 0; s_ < p.S; ++s_)
-            if ((unsigned)(ho - p.pad + r) < (unsigned)p.H && (unsigned)(wo - p.pad + s_) < (unsigned)p.W) mask |= 1u << (r * p.S + s_);
-        g_b[i] = (int)mask;
-      } else {
+      if constexpr (FASTA) pp_fast_pixel(m, p, g_a[i], g_b[i]);
+      else {
+        int img = fast_div(m, p.dv_howo_mul, p.dv_howo_shr), rem = m - img * p.HoWo;
+        int ho = fast_div(rem, p.dv_wo_mul, p.dv_wo_shr), wo = rem - ho * p.Wo;
         g_a[i] = ho * p.stride - p.pad;
         g_b[i] = wo * p.stride - p.pad;
         g_c[i] = img * p.H * p.W;
       }
     }
   }
-#pragma unroll
-  for (int i = 0; i < WPW; ++i) {
-    const int g = wid + 8 * i, n = n0 + 8 * g + sub;
-    gw[i] = (g < NWG && n < p.N) ? (unsigned)(n * p.K) * ES + cs * 16u : TF_OOB;
-  }
+  pp_weight_rows<BN, ES>(p, n0, wid, sub, cs, gw);
   // F8: lane L of wave 4 + w stages the scale bytes of tile row 64 w + L: (pixel index of the output position, tap-validity mask) as g_a / g_b
   int s_pix = 0, s_mask = 0;
   if constexpr (F8) {
     const int m = m0 + 64 * (wid - 4) + lane;
-    if (wid >= 4 && 64 * (wid - 4) + lane < BM && m < p.M) {
-      int img = fast_div(m, p.dv_howo_mul, p.dv_howo_shr), rem = m - img * p.HoWo;
-      int ho = fast_div(rem, p.dv_wo_mul, p.dv_wo_shr), wo = rem - ho * p.Wo;
-      s_pix = img * p.H * p.W + ho * p.W + wo;
-      unsigned mask = 0x80000000u;
-      for (int r = 0; r < p.S; ++r)
-        for (int s_ = 0; s_ < p.S; ++s_)
-          if ((unsigned)(ho - p.pad + r) < (unsigned)p.H && (unsigned)(wo - p.pad + s_) < (unsigned)p.W) mask |= 1u << (r * p.S + s_);
-      s_mask = (int)mask;
-    }
+    if (wid >= 4 && 64 * (wid - 4) + lane < BM && m < p.M) pp_fast_pixel(m, p, s_pix, s_mask);
   }
   const int klim = p.K * ES - cs * 16;                     // this lane's 16 bytes of K tile kt lie inside the row iff kt * 128 < klim (fp8: K need not be a multiple of 128)
   const int Hl = p.H << p.ups, Wl = p.W << p.ups;
@@ -235,24 +197,19 @@ __global__ void __launch_bounds__(512, 2) k_igemm_pp(const GemmP p) {
       prep_act();
     }
   };
-  // pieces [i0, i1) of this wave's APL activation loads of a tile (H2: the first APW are the first slab's half-masked loads, the next APW the second's)
-  auto stage_act = [&](int slot, int i0 = 0, int i1 = 64) {
+  // this wave's APL activation loads of a tile (H2: the first APW are the first slab's half-masked loads, the next APW the second's)
+  auto stage_act = [&](int slot) {
     const unsigned base = lds0 + (unsigned)slot * STAGE + (unsigned)wid * 1024u;
-    // (the scalars are wave-uniform by construction; the readfirstlanes are no-ops that keep them in SGPRs whatever the compiler's
-    // divergence analysis makes of the bookkeeping's control flow)
-    auto one = [&](int lo, int hi, int nb, int r_, int s_, int c0_, int ld_, int cq, int hsel, int j0, int j1) {
-      // cq: this lane's 16-byte chunk inside the slab; hsel < 0: every lane issues, else only the lanes of half hsel; pieces [j0, j1) of APW
-      if (j0 >= j1) return;
-      i4v rs;
-      rs[0] = __builtin_amdgcn_readfirstlane(lo); rs[1] = __builtin_amdgcn_readfirstlane(hi);
-      rs[2] = __builtin_amdgcn_readfirstlane(nb); rs[3] = 0x00020000;
+    // (the scalars are wave-uniform by construction: the readfirstlanes are no-ops, see pp_src_rsrc)
+    auto one = [&](int lo, int hi, int nb, int r_, int s_, int c0_, int ld_, int cq, int hsel) {
+      // cq: this lane's 16-byte chunk inside the slab; hsel < 0: every lane issues, else only the lanes of half hsel
+      const i4v rs = pp_src_rsrc(lo, hi, nb);
       const int s_r = __builtin_amdgcn_readfirstlane(r_), s_c0 = __builtin_amdgcn_readfirstlane(c0_), s_ld = __builtin_amdgcn_readfirstlane(ld_);
       const bool mine = hsel < 0 || (cs >> 2) == hsel;
       if constexpr (FASTA) {
         const int vc = s_c0 + cq * 16;
 #pragma unroll
         for (int i = 0; i < APW; ++i) {
-          if (i < j0 || i >= j1) continue;
           unsigned off = __umul24((unsigned)g_a[i], (unsigned)s_ld) + (unsigned)vc;
           if (mine) dma16(rs, (g_b[i] & s_r) ? off : TF_OOB, base + (unsigned)i * 8192u);
         }
@@ -261,7 +218,6 @@ __global__ void __launch_bounds__(512, 2) k_igemm_pp(const GemmP p) {
         const int cc = s_c0 + cq * (16 / ES);
 #pragma unroll
         for (int i = 0; i < APW; ++i) {
-          if (i < j0 || i >= j1) continue;
           int hi_ = g_a[i] + s_r, wi = g_b[i] + s_s;
           bool ok = (unsigned)hi_ < (unsigned)Hl && (unsigned)wi < (unsigned)Wl;
           int pix = g_c[i] + (hi_ >> ups) * Wd + (wi >> ups);
@@ -269,50 +225,41 @@ __global__ void __launch_bounds__(512, 2) k_igemm_pp(const GemmP p) {
         }
       }
     };
-    const auto lim = [](int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; };
-    if constexpr (!F8) one(a_lo, a_hi, a_nb, a_r, a_s, a_c0, a_ld, cs, -1, i0, i1);
+    if constexpr (!F8) one(a_lo, a_hi, a_nb, a_r, a_s, a_c0, a_ld, cs, -1);
     else if constexpr (H2) {
       // the two 64-channel slabs of this K tile are usually 128 CONTIGUOUS bytes of one (tap, tensor) -- with 320 channels 4 tiles of 5 -- and then
       // one full-width load does it: the load instructions of the load half, not bytes, set this kernel's pace (13 per wave and tile against 9).
       // (wave-uniform test on the prepared scalars; the counted waits assume the smaller number of loads: see wait_landed)
-      const bool contig = TF_PP_H2_MERGE && FASTA && __builtin_amdgcn_readfirstlane((b_lo == a_lo) & (b_hi == a_hi) & (b_nb == a_nb) & (a_r == b_r) & (a_c0 == b_c0 + 64) & (a_ld == b_ld));
-      if (contig) one(b_lo, b_hi, b_nb, b_r, b_s, b_c0, b_ld, cs, -1, lim(i0, 0, APW), lim(i1, 0, APW));
+      const bool contig = FASTA && __builtin_amdgcn_readfirstlane((b_lo == a_lo) & (b_hi == a_hi) & (b_nb == a_nb) & (a_r == b_r) & (a_c0 == b_c0 + 64) & (a_ld == b_ld));
+      if (contig) one(b_lo, b_hi, b_nb, b_r, b_s, b_c0, b_ld, cs, -1);
       else {
-        one(b_lo, b_hi, b_nb, b_r, b_s, b_c0, b_ld, cs & 3, 0, lim(i0, 0, APW), lim(i1, 0, APW));
-        one(a_lo, a_hi, a_nb, a_r, a_s, a_c0, a_ld, cs & 3, 1, lim(i0 - APW, 0, APW), lim(i1 - APW, 0, APW));
+        one(b_lo, b_hi, b_nb, b_r, b_s, b_c0, b_ld, cs & 3, 0);
+        one(a_lo, a_hi, a_nb, a_r, a_s, a_c0, a_ld, cs & 3, 1);
       }
-    } else one(b_lo, b_hi, b_nb, b_r, b_s, b_c0, b_ld, cs, -1, i0, i1);       // channel counts on the 128 grid: the two slabs of a tile are 128 contiguous bytes
+    } else one(b_lo, b_hi, b_nb, b_r, b_s, b_c0, b_ld, cs, -1);       // channel counts on the 128 grid: the two slabs of a tile are 128 contiguous bytes
   };
-  auto stage_w = [&](int slot, int kt, int i0 = 0, int i1 = 64) {
-    const unsigned base = lds0 + (unsigned)slot * STAGE + (unsigned)(BM / 8 + wid) * 1024u;
+  auto stage_w = [&](int slot, int kt) {
     const unsigned kb = (unsigned)kt * 128u;
-#pragma unroll
-    for (int i = 0; i < WPW; ++i)
-      if (i >= i0 && i < i1 && (WREM == 0 || i < WPW - 1 || wid < WREM)) dma16_w(rs_w, (gw[i] != TF_OOB && (!F8 || (int)kb < klim)) ? gw[i] + kb : TF_OOB, base + (unsigned)i * 8192u);
+    pp_stage_weights<BN>(rs_w, gw, wid, lds0 + (unsigned)slot * STAGE + (unsigned)(BM / 8 + wid) * 1024u, kb, !F8 || (int)kb < klim);
   };
   // F8: the E8M0 bytes of the tile's activation rows (waves 4-7; every one of them issues SCL loads so that the counts stay uniform -- the
   // rows beyond BM of the 192-row tile fetch out of range).  A source tensor holds its scale bytes behind its codes (offset = the codes'
   // byte count `nb`), C / 32 per pixel; a 64-channel slab starting at byte offset c0 of a pixel's codes has its 2 bytes at c0 / 32.
-  auto stage_sc = [&](int slot, int i0 = 0, int i1 = 2) {
+  auto stage_sc = [&](int slot) {
     if constexpr (F8) {
       if (wid < 4) return;
-      const unsigned base = lds0 + (unsigned)NS * STAGE + (unsigned)slot * SCS + (unsigned)(wid - 4) * 256u;
+      const unsigned base = lds0 + (unsigned)L::scales + (unsigned)slot * SCS + (unsigned)(wid - 4) * 256u;
       auto one = [&](int lo, int hi, int nb, int r_, int c0_, int ld_, unsigned ldsb, auto wide) {
-        i4v rs;
         const int s_nb = __builtin_amdgcn_readfirstlane(nb);
-        rs[0] = __builtin_amdgcn_readfirstlane(lo); rs[1] = __builtin_amdgcn_readfirstlane(hi);
-        rs[2] = s_nb + (s_nb >> 5); rs[3] = 0x00020000;
+        const i4v rs = pp_scale_rsrc(lo, hi, nb);
         const int s_r = __builtin_amdgcn_readfirstlane(r_), s_c0 = __builtin_amdgcn_readfirstlane(c0_) >> 5, s_ld = __builtin_amdgcn_readfirstlane(ld_) >> 5;
         const unsigned off = (s_mask & s_r) ? (unsigned)s_nb + __umul24((unsigned)s_pix, (unsigned)s_ld) + (unsigned)s_c0 : TF_OOB;
-        if constexpr (decltype(wide)::value)
-          asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dword %1, %2, 0 offen lds" :: "s"(__builtin_amdgcn_readfirstlane((int)ldsb)), "v"(off), "s"(rs) : "memory");
-        else
-          asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_ushort %1, %2, 0 offen lds" :: "s"(__builtin_amdgcn_readfirstlane((int)ldsb)), "v"(off), "s"(rs) : "memory");
+        if constexpr (decltype(wide)::value) dma4(rs, off, ldsb); else dma2(rs, off, ldsb);
       };
       if constexpr (H2) {
-        if (i0 <= 0 && i1 > 0) one(b_lo, b_hi, b_nb, b_r, b_c0, b_ld, base, std::false_type{});
-        if (i0 <= 1 && i1 > 1) one(a_lo, a_hi, a_nb, a_r, a_c0, a_ld, base + 1024u, std::false_type{});
-      } else if (i0 <= 0 && i1 > 0) one(b_lo, b_hi, b_nb, b_r, b_c0, b_ld, base, std::true_type{});
+        one(b_lo, b_hi, b_nb, b_r, b_c0, b_ld, base, std::false_type{});
+        one(a_lo, a_hi, a_nb, a_r, a_c0, a_ld, base + 1024u, std::false_type{});
+      } else one(b_lo, b_hi, b_nb, b_r, b_c0, b_ld, base, std::true_type{});
     }
   };
   // "this wave's pieces of every tile but the newest one (NEWEST) / of every tile (!NEWEST) have landed"
@@ -322,7 +269,7 @@ __global__ void __launch_bounds__(512, 2) k_igemm_pp(const GemmP p) {
       static_assert(WREM == 0 || WREM == 4, "the wave classes below");
       // (H2 with merging: a tile issues APW or 2 APW activation loads; the wait assumes APW -- with the newest tile's loads at least that many in
       // flight, "at most that many outstanding" still means every older load has landed; a split tile's extra loads are waited for a little early)
-      constexpr int APLW = (F8 && H2 && TF_PP_H2_MERGE) ? APW : APL;
+      constexpr int APLW = (F8 && H2) ? APW : APL;
       if (wid < 4) wait_vm<APLW + WPW>(); else wait_vm<APLW + WPW - (WREM ? 1 : 0) + SCL>();
     } else wait_vm<0>();
   };
@@ -358,7 +305,7 @@ __global__ void __launch_bounds__(512, 2) k_igemm_pp(const GemmP p) {
   int sx[MJ];
 #pragma unroll
   for (int j = 0; j < MJ; ++j) sx[j] = 0x7F;
-  const int sc_lane = NS * STAGE + (H2 ? (lg >> 1) * 1024 + (lg & 1) : lg) + (wm * (BM / 4) + lr) * 4;
+  const int sc_lane = L::scales + (H2 ? (lg >> 1) * 1024 + (lg & 1) : lg) + (wm * (BM / 4) + lr) * 4;
   auto read_sc = [&](int slot) {
     if constexpr (F8) {
       const unsigned char* sc = reinterpret_cast<const unsigned char*>(smem) + sc_lane + slot * SCS;
@@ -370,8 +317,8 @@ __global__ void __launch_bounds__(512, 2) k_igemm_pp(const GemmP p) {
 #pragma unroll
   for (int j = 0; j < MJ; ++j) { ls[j] = 0.f; lq[j] = 0.f; }
   auto mma = [&]() {                                       // the MFMAs of every k-step held in registers
-    __builtin_amdgcn_sched_barrier(0);
     if constexpr (LNF) {
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int f = 0; f < KF; ++f)
 #pragma unroll
@@ -389,87 +336,20 @@ __global__ void __launch_bounds__(512, 2) k_igemm_pp(const GemmP p) {
         return;
       }
     }
-    if (TF_PP_PRIO == 0) __builtin_amdgcn_s_setprio(1);
-    if constexpr (F8) {
-      typedef int v8i __attribute__((ext_vector_type(8)));
-      typedef int v4i __attribute__((ext_vector_type(4)));
-      v8i xv[MJ];
-#pragma unroll
-      for (int j = 0; j < MJ; ++j) {
-        v4i lo = __builtin_bit_cast(v4i, xf[0][j]), hi = __builtin_bit_cast(v4i, xf[KF - 1][j]);
-        xv[j] = (v8i){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      }
-#pragma unroll
-      for (int i = 0; i < NI; ++i) {
-        v4i lo = __builtin_bit_cast(v4i, wf[0][i]), hi = __builtin_bit_cast(v4i, wf[KF - 1][i]);
-        const v8i wv = (v8i){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-#pragma unroll
-        for (int j = 0; j < MJ; ++j)      // e4m3 x e4m3; weights at 2^0 (their per-channel scale multiplies the accumulators later), activations with their block scales
-          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wv, xv[j], acc[i][j], 0, 0, 0, 0x7F7F7F7F, 0, sx[j]);
-      }
-    } else {
-#pragma unroll
-      for (int f = 0; f < KF; ++f)
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-#pragma unroll
-          for (int j = 0; j < MJ; ++j) acc[i][j] = mfma16<BF>(wf[f][i], xf[f][j], acc[i][j]);
-    }
-    if (TF_PP_PRIO == 0) __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  // chunk c of the MFMA block of a K tile (the experiment's form): the MJ instructions of (k-step c / NI, channel tile c % NI)
-  auto mma_chunk = [&](int c) {
-    const int f = c / NI, i = c % NI;
-    if constexpr (F8) {
-      typedef int v8i __attribute__((ext_vector_type(8)));
-      typedef int v4i __attribute__((ext_vector_type(4)));
-      v4i lo = __builtin_bit_cast(v4i, wf[0][i]), hi = __builtin_bit_cast(v4i, wf[KF - 1][i]);
-      const v8i wv = (v8i){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      if (f == 0) {
-#pragma unroll
-        for (int j = 0; j < MJ; ++j) {
-          v4i xl = __builtin_bit_cast(v4i, xf[0][j]), xh = __builtin_bit_cast(v4i, xf[KF - 1][j]);
-          const v8i xv = (v8i){xl[0], xl[1], xl[2], xl[3], xh[0], xh[1], xh[2], xh[3]};
-          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wv, xv, acc[i][j], 0, 0, 0, 0x7F7F7F7F, 0, sx[j]);
-        }
-      }
-    } else {
-      if constexpr (LNF) {
-        if (i == 0) {
-#pragma unroll
-          for (int j = 0; j < MJ; ++j) dot2_stats<BF>(xf[f][j], ls[j], lq[j]);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < MJ; ++j) acc[i][j] = mfma16<BF>(wf[f][i], xf[f][j], acc[i][j]);
-    }
-  };
-  auto barrier = [&]() {
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    pp_mma<F8, BF, KF, NI, MJ>(wf, xf, acc, sx);
   };
 
-  // bias and time-embedding values of this tile's columns, fetched now (latency under the K loop) and handed to the epilogue through an
-  // LDS table: thread t < BN holds column n0 + t; a tile spans at most two images (the host admits the kernel only where HoWo >= BM)
+  // bias and time-embedding values of this tile's columns, fetched now (latency under the K loop); a tile spans at most two images
   const int lb_img0 = m0 / p.HoWo;
-  float lb_b = 0.f, lb_c0 = 0.f, lb_c1 = 0.f;
-  if (tid < BN && n0 + tid < p.N && p.splitk <= 1) {
-    if (p.bias) lb_b = e2f<BF>(p.bias[n0 + tid]);
-    if (p.bias_nc) {
-      lb_c0 = e2f<BF>(p.bias_nc[(long long)lb_img0 * p.bias_nc_stride + n0 + tid]);
-      if ((lb_img0 + 1) * p.HoWo < p.M) lb_c1 = e2f<BF>(p.bias_nc[(long long)(lb_img0 + 1) * p.bias_nc_stride + n0 + tid]);
-    }
-  }
+  const PpBias lb = pp_bias_prefetch<BN, BF, true>(p, n0, tid, lb_img0, p.splitk <= 1);
   // ---- prologue: the first D tiles, whole
 #pragma unroll
   for (int s_ = 0; s_ < D; ++s_)
     if (s_ < nt) { prep_tile(); stage_act(s_); stage_w(s_, kt_begin + s_); stage_sc(s_); }
   if (D < nt) prep_tile();                                 // the scalars of tile D: its pieces ride on tile 0
   if (D >= 2 && nt >= 2) wait_landed(std::true_type{}); else wait_landed(std::false_type{});     // tile 0 landed
-  barrier();                                               // P: tile 0 is visible to every wave
-  if (grp == 1 && !(NP == 1 && TF_PP_V2 != 0)) barrier();  // the second half falls one barrier behind
-  if (TF_PP_PRIO == 1 && grp == 1) __builtin_amdgcn_s_setprio(1);      // (experiment: static priority for the later-dispatched half, no per-segment flips)
+  pp_barrier();                                            // P: tile 0 is visible to every wave
+  if (grp == 1) pp_barrier();                              // the second half falls one barrier behind
   int rs = 0, ws = D % NS;                                 // ring slot of tile t / of tile t + D
   int ktw = kt_begin + D;                                  // K tile whose weight pieces are staged next
   // one K tile.  MORE: tile t + D exists (its pieces are issued during this tile, and the wait for tile t + 1 leaves them in flight);
@@ -479,59 +359,34 @@ __global__ void __launch_bounds__(512, 2) k_igemm_pp(const GemmP p) {
     const char* sb = smem + rs * STAGE;
     bool more = MORE;
     if constexpr (DBG) { if (p.dbg & 4) more = false; }
-    if constexpr (NP == 1 && TF_PP_V2 != 0) {
-      // EXPERIMENT (tagged build -DTF_PP_V2=1): no ping-pong -- every wave runs the same phase, ONE barrier per K tile; a wave's loads of tile
-      // t + D are issued piece by piece between the chunks of its MFMA block (an LDS-DMA issue costs ~60 cycles among bare MFMAs against
-      // 100-185 inside a load segment that also carries the fragment reads: MI355X_MICROARCH.md), the partner wave of the SIMD covers the stalls
-      read_k(sb, 0, 0);
-      read_k(sb, 1, 1);
-      read_sc(rs);
-      constexpr int CH = F8 ? NI : KF * NI, PT = APL + WPW + SCL;      // MFMA chunks (MJ instructions each) and load instructions of a tile
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int c = 0; c < CH; ++c) {
-        mma_chunk(c);
-        __builtin_amdgcn_sched_barrier(0);
-        if (more) {
-          const int q0 = c * PT / CH, q1 = (c + 1) * PT / CH;                 // pieces issued behind this chunk
-          stage_act(ws, q0, q1 < APL ? q1 : APL);
-          stage_w(ws, ktw, q0 - APL, q1 - APL);
-          stage_sc(ws, q0 - APL - WPW, q1 - APL - WPW);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      if constexpr (MORE) prep_tile();
-      if constexpr (NEXT) wait_landed(more_c);
-      wait_lds_reads();
-      barrier();
-    } else if constexpr (NP == 1) {
+    if constexpr (NP == 1) {
       read_k(sb, 0, 0);
       read_k(sb, 1, 1);
       read_sc(rs);
       if (more) { stage_act(ws); stage_w(ws, ktw); stage_sc(ws); }
       if constexpr (NEXT) { if (grp == 1) wait_landed(more_c); }
       wait_lds_reads();
-      barrier();
+      pp_barrier();
       mma();
       if constexpr (MORE) prep_tile();                     // scalars of tile t + 1 + D (harmless past the end: arguments only)
       if constexpr (NEXT) { if (grp == 0) wait_landed(more_c); }
-      barrier();
+      pp_barrier();
     } else {
       read_k(sb, 0, 0);
       if (more) stage_act(ws);
       wait_lds_reads();
-      barrier();
+      pp_barrier();
       mma();
-      barrier();
+      pp_barrier();
       read_k(sb, 1, 0);
       if (more) stage_w(ws, ktw);
       if constexpr (NEXT) { if (grp == 1) wait_landed(more_c); }
       wait_lds_reads();
-      barrier();
+      pp_barrier();
       mma();
       if constexpr (MORE) prep_tile();
       if constexpr (NEXT) { if (grp == 0) wait_landed(more_c); }
-      barrier();
+      pp_barrier();
     }
     if (++rs == NS) rs = 0;
     if (++ws == NS) ws = 0;
@@ -543,7 +398,7 @@ __global__ void __launch_bounds__(512, 2) k_igemm_pp(const GemmP p) {
     for (; t + 1 < nt; ++t) tile(std::false_type{}, std::true_type{});         // drain: nothing left to stage
     tile(std::false_type{}, std::false_type{});                                // last tile
   }
-  if (grp == 0 && !(NP == 1 && TF_PP_V2 != 0)) barrier();  // the first half waits for the second: every wave is done with the ring
+  if (grp == 0) pp_barrier();                              // the first half waits for the second: every wave is done with the ring
 
   if constexpr (DBG) {
     if (p.dbg & 1) {
@@ -554,19 +409,8 @@ __global__ void __launch_bounds__(512, 2) k_igemm_pp(const GemmP p) {
       return;
     }
   }
-  if constexpr (F8) {                                      // per-output-channel weight scales (this lane's 4 consecutive channels of every n-tile)
-    if (p.wscale) {
-#pragma unroll
-      for (int i = 0; i < NI; ++i) {
-        const int n = n0 + wn * TN + i * 16 + lg * 4;
-        f4 w = {1.f, 1.f, 1.f, 1.f};
-        for (int e = 0; e < 4; ++e) if (n + e < p.N) w[e] = p.wscale[n + e];
-#pragma unroll
-        for (int j = 0; j < MJ; ++j) acc[i][j] *= w;
-      }
-    }
-  }
-  // ---- epilogue: two passes of 128 rows through the shared scratch (wave (wm, wn) is quadrant (wm & 1, wn) of sub-block wm >> 1)
+  if constexpr (F8) pp_apply_wscale(p, acc, n0 + wn * TN, lg);
+  // ---- epilogue: two passes of BM / 2 rows through the shared scratch (pp_epilogue)
   f4 csum[NI];
 #pragma unroll
   for (int i = 0; i < NI; ++i) csum[i] = (f4){0.f, 0.f, 0.f, 0.f};
@@ -587,32 +431,16 @@ __global__ void __launch_bounds__(512, 2) k_igemm_pp(const GemmP p) {
       if (n + 3 < p.N) csum[i] = *reinterpret_cast<const f4*>(p.ln_colsum + n);
     }
   }
-  constexpr int BS = BM / 2;                              // rows of an epilogue pass
-  float* const lbt = reinterpret_cast<float*>(smem + 4 * (BS / 2) * (TN + 4) * 4 + BS * 8 + 4 * BN * 8);    // behind the scratch, the LayerNorm table and the statistics table
-  if (tid < BN) { lbt[tid] = lb_b; lbt[BN + tid] = lb_c0; lbt[2 * BN + tid] = lb_c1; }                     // (visible behind the first pass's barrier)
-  const int lb_m1 = (lb_img0 + 1) * p.HoWo;
+  pp_epilogue<BM, BN, BF, (F8 && BN == 128) ? 2 : 0>(p, smem, acc, csum, lb, m0, n0, split, lb_img0, tid, [&]() {   // (block-scaled GEGLU output: the host admits it for act = 1 and 128-wide tiles only)
+    if constexpr (LNF) {
+      // (mean, rstd) of this wave's rows into the table igemm_scratch_write reads them from; the wave with the other channel half
+      // writes the very same values to the very same slots, and every wave reads back only what it wrote itself
+      f2* stats = reinterpret_cast<f2*>(smem + L::ln_stats);
+      if (lg == 0) {
 #pragma unroll
-  for (int sm = 0; sm < 2; ++sm) {
-    if ((wm >> 1) == sm) {
-      if constexpr (LNF) {
-        // (mean, rstd) of this wave's rows into the table igemm_scratch_write reads them from; the wave with the other channel half
-        // writes the very same values to the very same slots, and every wave reads back only what it wrote itself
-        f2* stats = reinterpret_cast<f2*>(smem + 4 * (BS / 2) * (TN + 4) * 4);
-        if (lg == 0) {
-#pragma unroll
-          for (int j = 0; j < MJ; ++j) stats[(wm & 1) * (BS / 2) + j * 16 + lr] = lstat[j];
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        for (int j = 0; j < MJ; ++j) stats[(wm & 1) * (L::BS / 2) + j * 16 + lr] = lstat[j];
       }
-      igemm_scratch_write<BS, BN>(p, acc, csum, smem, (wm & 1) | (wn << 1), lane);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    barrier();
-    // (two items' loads in flight at a time: half of the accumulators is still live during the first pass)
-    if (F8 && BN == 128 && p.out8) igemm_epilogue<BS, BN, (F8 && BN == 128) ? 2 : 0, false, 2, true>(p, smem, m0 + sm * BS, n0, split, wid & 3, wid >> 2, lane, lbt, n0, lb_m1);   // (block-scaled GEGLU output: the host admits it for act = 1 and 128-wide tiles only)
-    else igemm_epilogue<BS, BN, false, BF, 2, true>(p, smem, m0 + sm * BS, n0, split, wid & 3, wid >> 2, lane, lbt, n0, lb_m1);
-    if (p.gn_part && m0 + sm * BS < p.M) igemm_gn_stats<BS, BN>(p, smem, m0 + sm * BS, n0, wid & 3, wid >> 2, lane);   // (block-uniform: the barrier inside is safe)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    barrier();
-  }
+  });
 }

@@ -1,6 +1,6 @@
 // Part of the implicit-GEMM family of csrc/gemm.hip (see its head comment).
 #pragma once
-#include "gemm_common.h"
+#include "gemm_pingpong.h"
 
 // =====================================================================================================================
 // PATCH form of the ping-pong kernel (round 4): 3 x 3 / stride 1 / pad 1 convolutions whose 192-row tile is a whole number of image rows
@@ -13,17 +13,18 @@
 // dy PW + dx (PW = W + 4: the patch's row pitch).  Per K tile a block then ingests the weight tile (BN x 128 B) plus a ninth of a patch instead of weight tile + 192 x 128 B:
 // 25.6 KB instead of 44.6 KB at 192 x 160 and W = 96, and 3.2 LDS-DMA instructions per wave instead of 5.5.
 //
-// Everything else is k_igemm_pp's one-phase form: all eight waves load and compute, two wave groups one barrier apart, an LDS-DMA ring of three
-// slots (weights only) two tiles ahead -- nine taps = three turns of the ring, so a tap's slot is a compile-time constant; a fourth slot where the
+// The schedule is that of k_igemm_pp's one-phase form, and every piece the two kernels share is one function of gemm_pingpong.h (the LDS layout, weight
+// staging, source descriptors, the MFMA block, the weight scales, the bias prefetch, the epilogue): all eight waves load and compute, two wave groups one
+// barrier apart, an LDS-DMA ring of three slots (weights only) two tiles ahead -- nine taps = three turns of the ring, so a tap's slot is a compile-time constant; a fourth slot where the
 // patches leave room for it measured 3-5 % SLOWER (profiles/r04_pp3.txt): latency is not what this loop waits for -- counted vmcnt waits (run-time counts through a computed jump: the tiles of a slab carry different numbers
-// of loads), LDS image rows XOR-swizzled on the source side and again on the read, the shared epilogue in two passes of 96 rows.
-//   LDS: patch buffer 0 | patch buffer 1 | weight slots 0 .. 2.  patch(g) lives in buffer g & 1; its pieces ride on the first tiles of slab g - 1, one
+// of loads), LDS image rows XOR-swizzled on the source side and again on the read, pp_epilogue in two passes of 96 rows.
+//   LDS (Pp3Lds): patch buffer 0 | patch buffer 1 | weight slots 0 .. 2 | scale patches or the spare activation slot.  patch(g) lives in buffer g & 1; its pieces ride on the first tiles of slab g - 1, one
 //   per wave and tap (the buffer was last read for slab g - 2: behind every barrier those tiles are issued after); slab 0's patch is issued whole in the
 //   prologue.  Patch row pr = py PW + px holds pixel (y0 - 1 + py, px - 1) of the tile's image (y0 = its first image row; px > W + 1 is padding);
 //   output row m of the tile (image row yl = m / W, column x) reads tap (dy, dx) at patch row (yl + dy) PW + x + dx.
 // Channel counts on the 64 grid (the concat pair: a slab lies in one source), no split-K.  The folded 1x1 skip projection of a ResBlock (extra K
 // columns behind the nine taps, their activations the output pixels of x3 | x4: vision/resnet.py:23-31 of the reference) follows as one K tile per
-// 64-channel slab in k_igemm_pp's form -- 192 activation rows per tile through a three-slot ring of its own, laid over the patch buffers (the one the
+// 64-channel slab as k_igemm_pp stages its tiles -- 192 activation rows per tile through a three-slot ring of its own, laid over the patch buffers (the one the
 // last slab does not read holds slots 0 and 1 -- slot 1 in the spare LDS behind the weight ring where a buffer is too small for two -- the other one slot 2).  W -- the OUTPUT row length -- is a
 // template parameter: every patch offset is then an instruction immediate.  The nearest-2x up-sampling of the Upsample convs (vision/unet.py:79-86 of the
 // reference) folds into the patch gather: patch pixel (y, x) comes from source pixel (y >> 1, x >> 1), fetched once per slab instead of once per tap and 2 x 2 copy.
@@ -40,36 +41,30 @@
 // (Issuing part of a tile's loads between its MFMAs instead of in front of the barrier -- balancing the two phases of the ping-pong -- measured
 // 0 ... -5 %, the more the more loads moved: profiles/r04_pp3.txt.  The loop runs at 1.83-1.94 GHz with the matrix pipe busy in ~72 % of its
 // cycles: the chip holds its clock down under this load, and what raises throughput from here is less energy per MFMA, not a tighter issue stream.)
-// F8 = OCP e4m3 operands on the block-scaled MFMA, as k_igemm_pp<F8>: a slab is 128 channels (the 128 bytes of a patch row), the fragment
+// F8 = OCP e4m3 operands on the block-scaled MFMA (pp_mma<F8>; gemm_pp.h's head comment describes the operand layout): a slab is 128 channels (the 128 bytes of a patch row), the fragment
 //   reads and their addresses are the fp16 kernel's, one v_mfma_scale_f32_16x16x128_f8f6f4 takes both 64-byte halves.  The E8M0 bytes of a patch row's
 //   four 32-channel blocks travel as a second, small patch (one dword per patch row, double buffered behind the weight ring): waves 0 .. 6 fetch it with
-//   one buffer_load_dword ... lds each, on tap 7 of the previous slab (the patch pieces ride on taps 0 .. PPW - 1 <= 6), and a lane reads the byte of (its
+//   one buffer_load_dword ... lds (dma4) each, on tap 7 of the previous slab (the patch pieces ride on taps 0 .. PPW - 1 <= 6), and a lane reads the byte of (its
 //   patch row, block lg) with one ds_read_u8 per pixel tile at an immediate offset per tap.  Channel counts on the 128 grid; weights carry one fp32 scale
 //   per output channel, applied to the accumulators in front of the epilogue.
 // H2 (F8 only) = channel counts on the 64 grid (320, 960: one source tensor): the last slab holds 64 channels -- the lanes of its upper 64 bytes fetch out of range
 //   (zero codes; the weight bytes they meet belong to the next tap or row, finite e4m3 values, and contribute nothing) -- and a patch row's four scale bytes sit at
-//   an offset that is only 2-byte aligned (C / 32 = 10 bytes per pixel), so they travel as two buffer_load_ushort ... lds into two tables (blocks 0-1 | blocks 2-3; the
+//   an offset that is only 2-byte aligned (C / 32 = 10 bytes per pixel), so they travel as two buffer_load_ushort ... lds (dma2) into two tables (blocks 0-1 | blocks 2-3; the
 //   second one out of range for the half slab: E8M0 0 instead of a neighbour's byte, which could be the NaN code).
 template <int BN, int W, bool F8 = false, bool H2 = false, bool BF = false>   // BF: bfloat16 operands / outputs (gemm_k_pp3_bf16.hip)
 __global__ void __launch_bounds__(512, 2) k_igemm_pp3(const GemmP p) {
   static_assert(!(BF && F8), "the e4m3 form has fp16 bias / residual / outputs");
   static_assert(F8 || !H2, "the half-slab form is the e4m3 kernel's");
-  constexpr int BM = 192, TN = BN / 2, MJ = 3, NI = TN / 16, NS = 3, D = NS - 1;
+  using L = Pp3Lds<BN, W, F8, H2>;                         // the LDS layout: patch buffers, weight ring, scale patches / spare activation slot, the epilogue's share
+  constexpr int BM = L::BM, TN = BN / 2, MJ = 3, NI = TN / 16, NS = L::NS, D = NS - 1;
   constexpr int ES = F8 ? 1 : 2, SLAB = 128 / ES;          // bytes per element; channels of a slab (128 bytes of a patch row)
-  constexpr int WST = BN * 128;                            // bytes of a weight ring slot
-  constexpr int NWG = BN / 8, WPW = (NWG + 7) / 8, WREM = NWG % 8;
-  constexpr int PW = W + 4, PROWS = (BM / W + 2) * PW, NPP = (PROWS + 7) / 8, PB = NPP * 1024;     // patch: row pitch, rows, 8-row pieces, bytes of a buffer
+  constexpr int WST = L::WST, PW = L::PW, PROWS = L::PROWS, NPP = L::NPP, PB = L::PB, NSW = L::NSW, SCT = L::SCT, SCB = L::SCB, AST = L::AST, XS1 = L::XS1;
+  constexpr int WPW = (BN / 8 + 7) / 8;                    // weight pieces per wave
   constexpr int PPW = (NPP + 7) / 8;                       // patch pieces per wave at most: they ride on taps 0 .. PPW - 1 and are waited for D - 1 tiles later
   static_assert(W % 8 == 0 && BM % W == 0, "the tile is whole image rows; PW = 4 mod 8");
   static_assert(PPW - 1 + D - 1 <= 8, "a slab's patch must have landed when its first tile is read");
-  constexpr int NSW = (PROWS + 63) / 64;                   // waves that fetch scales
-  constexpr int SCT = F8 ? NSW * 256 : 0;                  // bytes of a scale table: one dword per patch row, whole 64-row wave loads
-  constexpr int SCB = (H2 ? 2 : 1) * SCT;                  // bytes of a scale patch (H2: two tables)
-  static_assert(2 * PB + NS * WST + 2 * SCB <= 163840, "LDS budget");
+  static_assert(L::total <= 163840, "LDS budget");
   static_assert(!F8 || (PPW <= 7 && NSW <= 8), "the scale loads ride on tap 7");
-  constexpr int AST = BM * 128;                            // bytes of an activation tile of the extra 1x1 segment
-  constexpr int XS1 = 2 * AST <= PB ? AST : -1;            // its slot 1: behind slot 0 in the free patch buffer, or (-1) in the spare LDS behind the weight ring
-  static_assert(F8 || XS1 > 0 || 2 * PB + NS * WST + AST <= 163840, "LDS budget of the extra segment");
   static_assert(PPW <= 7, "taps 7 and 8 of the last slab carry the first two extra activation tiles");
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -77,21 +72,14 @@ __global__ void __launch_bounds__(512, 2) k_igemm_pp3(const GemmP p) {
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int grp = wid >> 2, wm = wid & 3, wn = wid >> 2;
   const int ntiles = p.ntm * p.ntn;
-  int bid = blockIdx.x;
-  {
-    int q = ntiles >> 3, r = ntiles & 7, xcd = bid & 7, idx = bid >> 3;      // XCD-aware order, as in k_igemm
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
-  int tile_m, tile_n;
-  if (p.order == 0) { tile_m = bid / p.ntn; tile_n = bid - tile_m * p.ntn; }
-  else { tile_n = bid / p.ntm; tile_m = bid - tile_n * p.ntm; }
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
+  const TileMN tmn = tile_decode(xcd_order(blockIdx.x, ntiles), p.order, p.ntm, p.ntn);
+  const int m0 = tmn.m * BM, n0 = tmn.n * BN;
   const int img = m0 / p.HoWo, y0 = (m0 - img * p.HoWo) / W;
   const int G = (p.C + SLAB - 1) / SLAB, nt = G * 9;       // channel slabs (H2: the last one half full), K tiles of the nine taps
   const bool half_last = H2 && (p.C & 64);
   const int GE = F8 ? 0 : (p.C3 + p.C4) >> 6;              // K tiles of the extra 1x1 segment
   const unsigned lds0 = lds_off(smem);
-  const unsigned lds_w = lds0 + 2u * (unsigned)PB;
+  const unsigned lds_w = lds0 + (unsigned)L::weights;
 
   const int ups = p.ups;                                   // nearest-2x up-sampling folded into the gather: the patch holds the UP-SAMPLED pixels (p.H x p.W is the source)
   // ---- staging geometry.  Patch piece q = wid + 8 i covers patch rows 8 q .. 8 q + 7; lane -> row 8 q + sub, source chunk swizzled
@@ -108,11 +96,7 @@ __global__ void __launch_bounds__(512, 2) k_igemm_pp3(const GemmP p) {
   }
   const i4v rs_w = raw_rsrc(p.w, p.w_bytes);
   unsigned gw[WPW];
-#pragma unroll
-  for (int i = 0; i < WPW; ++i) {
-    const int g = wid + 8 * i, n = n0 + 8 * g + sub;
-    gw[i] = (g < NWG && n < p.N) ? (unsigned)(n * p.K) * ES + cs * 16u : TF_OOB;
-  }
+  pp_weight_rows<BN, ES>(p, n0, wid, sub, cs, gw);
   const int C1_ = p.C1, C2_ = p.C2, Cc_ = p.C;
   const unsigned long long px1 = (unsigned long long)p.x, px2 = (unsigned long long)(p.x2 ? p.x2 : p.x);
   const int nb1 = (int)p.x_bytes, nb2 = (int)p.x2_bytes;
@@ -121,10 +105,7 @@ __global__ void __launch_bounds__(512, 2) k_igemm_pp3(const GemmP p) {
     if (wid + 8 * i >= NPP) return 0;
     const int c = g * SLAB;
     const bool second = c >= C1_;
-    const unsigned long long px = second ? px2 : px1;
-    i4v rs;
-    rs[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)px); rs[1] = __builtin_amdgcn_readfirstlane((int)((unsigned)(px >> 32) & 0xffffu));
-    rs[2] = __builtin_amdgcn_readfirstlane(second ? nb2 : nb1); rs[3] = 0x00020000;
+    const i4v rs = pp_src_rsrc(second ? px2 : px1, second ? nb2 : nb1);
     const int ld2 = __builtin_amdgcn_readfirstlane((second ? C2_ : C1_) * ES);
     const int cb = __builtin_amdgcn_readfirstlane((second ? c - C1_ : c) * ES) + csp * 16;
     const bool dead = H2 && half_last && g == G - 1 && csp >= 4;       // the upper 64 bytes of a half slab
@@ -145,43 +126,30 @@ __global__ void __launch_bounds__(512, 2) k_igemm_pp3(const GemmP p) {
     if (wid >= NSW) return 0;
     const int c = g * SLAB;
     const bool second = c >= C1_;
-    const unsigned long long px = second ? px2 : px1;
     const int s_nb = __builtin_amdgcn_readfirstlane(second ? nb2 : nb1);
-    i4v rs;
-    rs[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)px); rs[1] = __builtin_amdgcn_readfirstlane((int)((unsigned)(px >> 32) & 0xffffu));
-    rs[2] = s_nb + (s_nb >> 5); rs[3] = 0x00020000;
+    const i4v rs = pp_scale_rsrc(second ? px2 : px1, s_nb);
     const int ld32 = __builtin_amdgcn_readfirstlane((second ? C2_ : C1_) >> 5), c32 = __builtin_amdgcn_readfirstlane((second ? c - C1_ : c) >> 5);
     const unsigned off = sc_pix >= 0 ? (unsigned)s_nb + (unsigned)(sc_pix * ld32 + c32) : TF_OOB;
-    const unsigned ldsb = lds_w + (unsigned)NS * WST + (unsigned)(g & 1) * SCB + (unsigned)wid * 256u;
+    const unsigned ldsb = lds0 + (unsigned)L::spare + (unsigned)(g & 1) * SCB + (unsigned)wid * 256u;
     if constexpr (H2) {
       const unsigned off_hi = (sc_pix >= 0 && !(half_last && g == G - 1)) ? off + 2u : TF_OOB;
-      asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_ushort %1, %2, 0 offen lds" :: "s"(__builtin_amdgcn_readfirstlane((int)ldsb)), "v"(off), "s"(rs) : "memory");
-      asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_ushort %1, %2, 0 offen lds" :: "s"(__builtin_amdgcn_readfirstlane((int)(ldsb + SCT))), "v"(off_hi), "s"(rs) : "memory");
+      dma2(rs, off, ldsb);
+      dma2(rs, off_hi, ldsb + SCT);
       return 2;
     }
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dword %1, %2, 0 offen lds" :: "s"(__builtin_amdgcn_readfirstlane((int)ldsb)), "v"(off), "s"(rs) : "memory");
+    dma4(rs, off, ldsb);
     return 1;
   };
   // the weight tile at byte offset kb of every row into ring slot `slot`; returns the number of loads issued
-  auto stage_wk = [&](int slot, unsigned kb) -> int {
-    const unsigned base = lds_w + (unsigned)slot * WST + (unsigned)wid * 1024u;
-    int n = 0;
-#pragma unroll
-    for (int i = 0; i < WPW; ++i)
-      if (WREM == 0 || i < WPW - 1 || wid < WREM) { dma16_w(rs_w, gw[i] != TF_OOB ? gw[i] + kb : TF_OOB, base + (unsigned)i * 8192u); ++n; }
-    return n;
-  };
+  auto stage_wk = [&](int slot, unsigned kb) -> int { return pp_stage_weights<BN>(rs_w, gw, wid, lds_w + (unsigned)slot * WST + (unsigned)wid * 1024u, kb); };
   auto stage_w = [&](int slot, int g, int tap) -> int { return stage_wk(slot, (unsigned)(tap * Cc_ + g * SLAB) * ES); };      // (slab g, tap)
   // extra segment: LDS offset of activation slot e % 3, and the activation tile of its 64-channel slab e (3 pieces per wave)
   const int xb_free = (G & 1) * PB;                        // the patch buffer the last slab does not read
-  auto xslot = [&](int e) -> int { const int r = e % 3; return r == 0 ? xb_free : r == 1 ? (XS1 > 0 ? xb_free + AST : 2 * PB + NS * WST) : PB - xb_free; };
+  auto xslot = [&](int e) -> int { const int r = e % 3; return r == 0 ? xb_free : r == 1 ? (XS1 > 0 ? xb_free + AST : L::spare) : PB - xb_free; };
   auto stage_x = [&](int e) -> int {
     const int c = e * 64, C3_ = p.C3;
     const bool second = c >= C3_;
-    const unsigned long long px = (unsigned long long)(second ? p.x4 : p.x3);
-    i4v rs;
-    rs[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)px); rs[1] = __builtin_amdgcn_readfirstlane((int)((unsigned)(px >> 32) & 0xffffu));
-    rs[2] = __builtin_amdgcn_readfirstlane((int)(second ? p.x4_bytes : p.x3_bytes)); rs[3] = 0x00020000;
+    const i4v rs = pp_src_rsrc((unsigned long long)(second ? p.x4 : p.x3), (int)(second ? p.x4_bytes : p.x3_bytes));
     const int ld2 = __builtin_amdgcn_readfirstlane((second ? p.C4 : C3_) * 2);
     const int cb = __builtin_amdgcn_readfirstlane((second ? c - C3_ : c) * 2) + csp * 16;       // (rows 8 q + sub: the patch rows' swizzle)
     const unsigned base = lds0 + (unsigned)xslot(e) + (unsigned)wid * 1024u;
@@ -198,7 +166,7 @@ __global__ void __launch_bounds__(512, 2) k_igemm_pp3(const GemmP p) {
   for (int j = 0; j < MJ; ++j) {
     const int ml = wm * (BM / 4) + j * 16 + lr;
     const int yl = ml / W;
-    asx[j] = 2 * PB + NS * WST + (yl * PW + (ml - yl * W)) * 4 + (H2 ? (lg >> 1) * SCT + (lg & 1) : lg);
+    asx[j] = L::spare + (yl * PW + (ml - yl * W)) * 4 + (H2 ? (lg >> 1) * SCT + (lg & 1) : lg);
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx) {
       const int pr = yl * PW + (ml - yl * W) + dx;
@@ -206,7 +174,7 @@ __global__ void __launch_bounds__(512, 2) k_igemm_pp3(const GemmP p) {
       ax[1][dx][j] = ax[0][dx][j] ^ 64;
     }
   }
-  const int wo0 = 2 * PB + (wn * TN) * 128 + lr * 128 + ((lg ^ ((lr >> 1) & 7)) << 4);      // + slot * WST + i * 2048
+  const int wo0 = L::weights + (wn * TN) * 128 + lr * 128 + ((lg ^ ((lr >> 1) & 7)) << 4);      // + slot * WST + i * 2048
   const int wo1 = wo0 ^ 64;
   f4 acc[NI][MJ];
 #pragma unroll
@@ -249,54 +217,10 @@ __global__ void __launch_bounds__(512, 2) k_igemm_pp3(const GemmP p) {
       wf[1][i] = *reinterpret_cast<const h8*>(wb + wo1 + i * 2048);
     }
   };
-  auto mma = [&]() {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_setprio(1);
-    if constexpr (F8) {
-      typedef int v8i __attribute__((ext_vector_type(8)));
-      typedef int v4i __attribute__((ext_vector_type(4)));
-      v8i xv[MJ];
-#pragma unroll
-      for (int j = 0; j < MJ; ++j) {
-        v4i lo = __builtin_bit_cast(v4i, xf[0][j]), hi = __builtin_bit_cast(v4i, xf[1][j]);
-        xv[j] = (v8i){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      }
-#pragma unroll
-      for (int i = 0; i < NI; ++i) {
-        v4i lo = __builtin_bit_cast(v4i, wf[0][i]), hi = __builtin_bit_cast(v4i, wf[1][i]);
-        const v8i wv = (v8i){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-#pragma unroll
-        for (int j = 0; j < MJ; ++j)      // e4m3 x e4m3; weights at 2^0, activations with their block scales (block b's from lane group b)
-          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wv, xv[j], acc[i][j], 0, 0, 0, 0x7F7F7F7F, 0, sx[j]);
-      }
-      // (pin the results here: the intrinsic has no side effect, and without a use in this phase the compiler sinks a whole slab's MFMAs behind the
-      // last barrier of the slab and parks the fragments in scratch)
-#pragma unroll
-      for (int i = 0; i < NI; ++i)
-#pragma unroll
-        for (int j = 0; j < MJ; ++j) asm volatile("" :: "v"(acc[i][j]));
-    } else {
-#pragma unroll
-      for (int f = 0; f < 2; ++f)
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-#pragma unroll
-          for (int j = 0; j < MJ; ++j) acc[i][j] = mfma16<BF>(wf[f][i], xf[f][j], acc[i][j]);
-    }
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  auto barrier = [&]() {
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  };
+  auto mma = [&]() { pp_mma<F8, BF, 2, NI, MJ, true>(wf, xf, acc, sx); };    // (PIN: see pp_mma)
 
-  // bias and time-embedding values of this tile's columns (as in k_igemm_pp; a tile lies inside one image)
-  float lb_b = 0.f, lb_c0 = 0.f;
-  if (tid < BN && n0 + tid < p.N) {
-    if (p.bias) lb_b = e2f<BF>(p.bias[n0 + tid]);
-    if (p.bias_nc) lb_c0 = e2f<BF>(p.bias_nc[(long long)img * p.bias_nc_stride + n0 + tid]);
-  }
+  // bias and time-embedding values of this tile's columns, fetched now (latency under the K loop); a tile lies inside one image
+  const PpBias lb = pp_bias_prefetch<BN, BF, false>(p, n0, tid, img, true);
 
   // ---- prologue: patch(0) whole, weight tiles 0 .. D - 1; tile 0's loads landed, the others in flight
 #pragma unroll
@@ -306,8 +230,8 @@ __global__ void __launch_bounds__(512, 2) k_igemm_pp3(const GemmP p) {
 #pragma unroll
   for (int s_ = 0; s_ < D; ++s_) nw = stage_w(s_, 0, s_);  // (nt >= 9 > D; every tile of a wave carries the same number of weight loads)
   wait_vm_dyn(nw * (D - 1));
-  barrier();                                               // P: patch(0) and weight tile 0 are visible to every wave
-  if (grp == 1) barrier();                                 // the second half falls one barrier behind
+  pp_barrier();                                            // P: patch(0) and weight tile 0 are visible to every wave
+  if (grp == 1) pp_barrier();                              // the second half falls one barrier behind
 
 #if TF_PP3_STAMP
   unsigned long long* const stamps = reinterpret_cast<unsigned long long*>(p.partial) + (wid >> 2) * 64;
@@ -339,13 +263,13 @@ __global__ void __launch_bounds__(512, 2) k_igemm_pp3(const GemmP p) {
       if (next && grp == 1) wait_vm_dyn(nl);               // tile t + 1 (and every patch piece of an earlier tile) landed
       wait_lds_reads();
       PP3_STAMP(2);
-      barrier();
+      pp_barrier();
       PP3_STAMP(3);
       mma();
       PP3_STAMP(4);
       if (next && grp == 0) wait_vm_dyn(nl);
       PP3_STAMP(5);
-      barrier();
+      pp_barrier();
     }
     // the next slab's patch is the other buffer
     const int flip = (g & 1) ? -PB : PB;
@@ -375,42 +299,17 @@ __global__ void __launch_bounds__(512, 2) k_igemm_pp3(const GemmP p) {
     const bool next = e + 1 < GE;
     if (next && grp == 1) wait_vm_dyn(nl);
     wait_lds_reads();
-    barrier();
+    pp_barrier();
     mma();
     if (next && grp == 0) wait_vm_dyn(nl);
-    barrier();
+    pp_barrier();
   }
-  if (grp == 0) barrier();                                 // the first half waits for the second: every wave is done with the ring and the patches
+  if (grp == 0) pp_barrier();                              // the first half waits for the second: every wave is done with the ring and the patches
 
-  if constexpr (F8) {                                      // per-output-channel weight scales (this lane's 4 consecutive channels of every n-tile)
-    if (p.wscale) {
-#pragma unroll
-      for (int i = 0; i < NI; ++i) {
-        const int n = n0 + wn * TN + i * 16 + lg * 4;
-        f4 w = {1.f, 1.f, 1.f, 1.f};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) if (n + e < p.N) w[e] = p.wscale[n + e];
-#pragma unroll
-        for (int j = 0; j < MJ; ++j) acc[i][j] *= w;
-      }
-    }
-  }
-  // ---- epilogue: two passes of 96 rows through the shared scratch (as k_igemm_pp)
+  if constexpr (F8) pp_apply_wscale(p, acc, n0 + wn * TN, lg);
+  // ---- epilogue: two passes of 96 rows through the shared scratch (pp_epilogue)
   f4 csum[NI];
 #pragma unroll
   for (int i = 0; i < NI; ++i) csum[i] = (f4){0.f, 0.f, 0.f, 0.f};
-  constexpr int BS = BM / 2;
-  float* const lbt = reinterpret_cast<float*>(smem + 4 * (BS / 2) * (TN + 4) * 4 + BS * 8 + 4 * BN * 8);
-  if (tid < BN) { lbt[tid] = lb_b; lbt[BN + tid] = lb_c0; lbt[2 * BN + tid] = 0.f; }
-  const int lb_m1 = (img + 1) * p.HoWo;
-#pragma unroll
-  for (int sm = 0; sm < 2; ++sm) {
-    if ((wm >> 1) == sm) igemm_scratch_write<BS, BN>(p, acc, csum, smem, (wm & 1) | (wn << 1), lane);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    barrier();
-    igemm_epilogue<BS, BN, 0, BF, 2, true>(p, smem, m0 + sm * BS, n0, 0, wid & 3, wid >> 2, lane, lbt, n0, lb_m1);
-    if (p.gn_part) igemm_gn_stats<BS, BN>(p, smem, m0 + sm * BS, n0, wid & 3, wid >> 2, lane);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    barrier();
-  }
+  pp_epilogue<BM, BN, BF, 0>(p, smem, acc, csum, lb, m0, n0, 0, img, tid, []() {});
 }

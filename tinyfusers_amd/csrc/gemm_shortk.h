@@ -1,6 +1,6 @@
 // Part of the implicit-GEMM family of csrc/gemm.hip (see its head comment).
 // What the three persistent short-K kernels have in common -- k_gemm_c4 (gemm_c4.h), k_gemm_c8 (gemm_c8.h), k_gemm_ar (gemm_ar.h) -- each piece ONCE:
-//   the tile-order decode and the chunked walk; a wave's staging rows and the LDS-DMA of one K tile (SkStager); the fragment address, the read of a
+//   the chunked walk (the tile-order decode is tile_decode of gemm_common.h); a wave's staging rows and the LDS-DMA of one K tile (SkStager); the fragment address, the read of a
 //   32-deep half, its MFMAs and LayerNorm row sums; the bias / column-sum request at the head of a tile; the LayerNorm fold + bias on the accumulators;
 //   the row-sum reduce (and the partner exchange of c4 / c8); the rounding of a 16-row quarter; the transposing store of a wave tile (c4 / c8); and
 //   the launchers' CU count, LDS attribute and chunk rule.
@@ -14,10 +14,6 @@
 #include <initializer_list>
 
 // ---- tile order and walk -------------------------------------------------------------------------------------------------------------------------
-// tile index -> (tm, tn); order 0 = n fastest (consecutive tiles share their activation rows), 1 = m fastest (share the weight tile)
-__device__ __forceinline__ void sk_decode(int tile, int order, int ntm, int ntn, int& tm, int& tn) {
-  if (order == 0) { tm = tile / ntn; tn = tile - tm * ntn; } else { tn = tile / ntm; tm = tile - tn * ntm; }
-}
 // a block's tiles: chunks of `chunk` consecutive tiles of the list, the chunks strided by the grid.  Consecutive tiles (n-fastest order) share their
 // rows -- L1 / L2 lines, and with the LayerNorm fold the row statistics, computed for the first tile of a run only -- while the blocks running at the
 // same time stay next to each other in the list (whole runs per block, each block on rows of its own, cost the wide-N shapes 5-15 %).
