@@ -10,6 +10,9 @@ BASELINE config 3: full 50-step sampler, batch 1, end-to-end img/s.
     python -m example.sd1 --steps 50 [--ckpt sd-v1-4.ckpt] [--out rendered.npy]
     python -m example.sd1 --steps 20 --sampler dpmpp2m          # DPM-Solver++(2M); also ddim, ddim-eta, euler-a (--eta)
     python -m example.sd1 --steps 20 --sampler dpmpp2m --init-image x.npy --strength 0.6 [--mask m.npy]   # img2img / inpainting
+    python -m example.sd1 --steps 20 --sampler dpmpp2m --concat inpaint --cond-image x.npy --cond-mask m.npy   # the 9-channel inpainting UNet
+    python -m example.sd1 --steps 20 --sampler dpmpp2m --concat edit --cond-image x.npy [--image-guidance 1.5]   # InstructPix2Pix (8 channels)
+With --ckpt the configuration is read off the checkpoint's conv_in (4, 9 or 8 input channels); --concat picks it on synthetic weights.
 """
 import argparse
 import os
@@ -36,6 +39,12 @@ if __name__ == "__main__":
     ap.add_argument("--init-image", default="", help="image-to-image from this (H,W,3) uint8 image: .npy, or .png / .jpg through PIL")
     ap.add_argument("--strength", type=float, default=None, help="with --init-image: the part of the schedule that runs, in (0, 1] (default 0.6)")
     ap.add_argument("--mask", default="", help="with --init-image: inpaint where this (H,W) mask is >= 0.5 (uint8: nonzero); .npy, .png or .jpg")
+    ap.add_argument("--concat", choices=["inpaint", "edit"], default=None,
+                    help="a concat-conditioned UNet on synthetic weights: the SD-1.5 inpainting checkpoint (9 input channels) or InstructPix2Pix (8); "
+                         "with --ckpt the checkpoint decides")
+    ap.add_argument("--cond-image", default="", help="the image a concat-conditioned UNet reads: the image to inpaint / to edit, (H,W,3) uint8; .npy, .png or .jpg")
+    ap.add_argument("--cond-mask", default="", help="with an inpainting checkpoint: repaint where this (H,W) mask is >= 0.5 (uint8: nonzero)")
+    ap.add_argument("--image-guidance", type=float, default=None, help="with an InstructPix2Pix checkpoint: the image guidance scale (default 1.5)")
     args = ap.parse_args()
     if (args.init_image or args.mask or args.strength is not None) and not args.sampler:
         ap.error("--init-image, --strength and --mask need --sampler")
@@ -54,14 +63,35 @@ if __name__ == "__main__":
     from tinyfusers_amd.storage.synth import synth_normal, synth_state_dict
     from tinyfusers_amd.variants.sd import StableDiffusion
 
-    T.ensure_init(0)
-    model = StableDiffusion()
+    from tinyfusers_amd.vision.unet import SD15, SD15_EDIT, SD15_INPAINT
+
     t0 = time.time()
     import io, contextlib
+    concat = args.concat
     if args.ckpt:
         from tinyfusers_amd.storage.unpicker import load_checkpoint
         state = load_checkpoint(args.ckpt)                       # memory-mapped; update_state streams tensor by tensor
-    else:
+        cin = int(state["model.diffusion_model.input_blocks.0.0.weight"].shape[1])
+        if cin not in (4, 9, 8):
+            sys.exit(f"--ckpt: the UNet's conv_in reads {cin} channels; 4 (text-to-image), 9 (inpainting) and 8 (InstructPix2Pix) are supported")
+        if concat and cin != {"inpaint": 9, "edit": 8}[concat]:
+            sys.exit(f"--concat {concat} does not fit this checkpoint, whose conv_in reads {cin} channels")
+        concat = {4: None, 9: "inpaint", 8: "edit"}[cin]
+    if concat:
+        what = "an inpainting checkpoint (9 input channels)" if concat == "inpaint" else "an InstructPix2Pix checkpoint (8 input channels)"
+        if not args.sampler:
+            ap.error(f"{what} runs with --sampler")
+        if not args.cond_image or (concat == "inpaint" and not args.cond_mask):
+            ap.error(f"{what} needs --cond-image" + (" and --cond-mask" if concat == "inpaint" else "") + ": its UNet reads them at every step")
+        if args.mask:
+            ap.error("--mask (the latent blend) on top of a concat-conditioned checkpoint is not supported; use --cond-mask")
+    if (args.cond_image or args.cond_mask or args.image_guidance is not None) and not concat:
+        ap.error("--cond-image, --cond-mask and --image-guidance need an inpainting or InstructPix2Pix checkpoint (--ckpt, or --concat on synthetic weights)")
+    if (args.cond_mask and concat != "inpaint") or (args.image_guidance is not None and concat != "edit"):
+        ap.error("--cond-mask goes with an inpainting checkpoint, --image-guidance with an InstructPix2Pix one")
+    T.ensure_init(0)
+    model = StableDiffusion({None: SD15, "inpaint": SD15_INPAINT, "edit": SD15_EDIT}[concat])
+    if not args.ckpt:
         state = synth_state_dict(param_shapes(model), 0)       # UNet + VAE decoder + CLIP text encoder, by LDM name
     with contextlib.redirect_stdout(io.StringIO()):
         update_state(model, state, "")
@@ -103,6 +133,24 @@ if __name__ == "__main__":
         if args.mask:
             mask = load_array(args.mask, "L")
             mask = StableDiffusion.latent_mask(mask[None] if mask.ndim == 2 else mask)
+    cond_kw = {}
+    if concat:
+        cond_image = load_array(args.cond_image, "RGB")
+        cond_image = cond_image[None] if cond_image.ndim == 3 else cond_image
+        if cond_image.dtype != np.uint8 or cond_image.ndim != 4 or cond_image.shape[0] != 1 or cond_image.shape[3] != 3:
+            sys.exit(f"--cond-image: expected one uint8 (H,W,3) image, got {cond_image.dtype} {cond_image.shape}")
+        why = StableDiffusion.encoder_size_error(cond_image.shape[1], cond_image.shape[2])
+        if why:
+            sys.exit(f"--cond-image: {why}")
+        if init_image is not None and init_image.shape != cond_image.shape:
+            sys.exit(f"--init-image {init_image.shape} and --cond-image {cond_image.shape} differ in size")
+        lat_hw = (cond_image.shape[1] // 8, cond_image.shape[2] // 8)
+        cond_kw = {"cond_image": cond_image}
+        if concat == "inpaint":
+            cond_mask = load_array(args.cond_mask, "L")
+            cond_kw["cond_mask"] = cond_mask[None] if cond_mask.ndim == 2 else cond_mask
+        if args.image_guidance is not None:
+            cond_kw["image_guidance"] = args.image_guidance
     latent = model.latent_from_numpy(synth_normal(args.seed, "sd.latent", (1, 4) + lat_hw))
     if args.sampler:
         from tinyfusers_amd.variants.samplers import make
@@ -110,7 +158,7 @@ if __name__ == "__main__":
         schedule = make(args.sampler, args.eta).schedule(args.steps, strength=strength)
         print(f"sampler {schedule.sampler}: {len(schedule.timesteps)} steps, timesteps {schedule.timesteps[0]} .. {schedule.timesteps[-1]}"
               + (f" (strength {strength}{', inpainting' if mask is not None else ''})" if init_image is not None else ""))
-        model.compile(unconditional_context, context, latent, sampler=schedule, inpaint=mask is not None)
+        model.compile(unconditional_context, context, latent, sampler=schedule, inpaint=mask is not None, concat=concat)
     else:
         model.compile(unconditional_context, context, latent)
     times = []
@@ -122,9 +170,10 @@ if __name__ == "__main__":
                 x0 = model.encode_image(init_image)              # the VAE encoder: x0 = 0.18215 x its means
             model.synchronize()
             enc = time.perf_counter() - t0
-            model.start(seed=args.seed, image_offset=n, init_latent=x0, mask=mask)   # x0 noised to the schedule's start level
+            model.start(seed=args.seed, image_offset=n, init_latent=x0, mask=mask, **cond_kw)   # x0 noised to the schedule's start level
         elif args.sampler:
-            model.start(seed=args.seed, image_offset=n)          # image n of the seed: its latent and ancestral noise drawn on the device
+            model.start(seed=args.seed, image_offset=n, **cond_kw)   # image n of the seed: its latent and ancestral noise drawn on the device; a
+            #                                                          concat-conditioned UNet's image (and mask) go through the VAE encoder here
         else:
             model.set_latent(synth_normal(args.seed + n, "sd.latent", (1, 4, 64, 64)))
         t0 = time.perf_counter()

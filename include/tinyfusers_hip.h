@@ -505,6 +505,30 @@ int tf_cfg_sampler_step_masked_f32(void* latent, const void* eps2, void* x0_hist
 int tf_cfg_sampler_step_masked_bf16(void* latent, const void* eps2, void* x0_hist, const void* step_params, const void* coeffs, int rows, const void* x0_init,
                                     const void* mask, int B, int C, int H, int W, tfStream_t s);
 
+/* ---- concat-conditioned UNets (csrc/concat.hip): the SD-1.5 inpainting checkpoint (9 input channels [latent | mask | latent of the masked
+ * image]) and InstructPix2Pix (8 input channels [latent | latent of the image to edit], three guidance branches) on the sampler above: the
+ * CFG duplication of variants/sd.py:31 with the conditioning channels appended, the update of variants/sd.py:14-25 behind a three-branch
+ * combine, and the encoder edges of vae/vae.py:12-15 that fill the conditioning buffer. */
+/* tf_cfg_duplicate_* (variants/sd.py:31) for `groups` (2 or 3) copies with cond appended: latent (B,C,H,W) f32 NCHW, cond (B,Cc,H,W) f32 NCHW
+ * -> x_out (groups*B, C+Cc, H, W) NHWC 16-bit; group g, image b = [latent[b] | cond[b]], the cond channels +0 where bit g of drop_bits is set
+ * (bits at or above `groups` are ignored).
+ * The latent channels are rounded as tf_cfg_duplicate_* rounds them */
+int tf_cfg_concat_f16(void* x_out, const void* latent, const void* cond, int B, int C, int Cc, int H, int W, int groups, unsigned drop_bits, tfStream_t s);
+int tf_cfg_concat_bf16(void* x_out, const void* latent, const void* cond, int B, int C, int Cc, int H, int W, int groups, unsigned drop_bits, tfStream_t s);
+/* tf_cfg_sampler_step_* (variants/sd.py:14-25) with three branches: eps3 = [e0 ; e1 ; e2] (3B,C,H,W) NHWC 16-bit,
+ * e = e0 + g_T (e2 - e1) + g_I (e1 - e0), g_T = step_params[3], g_I = edit_params[0]; edit_params: a device block of 4 fp32 words
+ * (tf_set_step_params writes one).  Everything behind the combine as there: x0, x', the tag-1 noise, the x0 history */
+int tf_cfg3_sampler_step_f32(void* latent, const void* eps3, void* x0_hist, const void* step_params, const void* coeffs, int rows, const void* edit_params,
+                             int B, int C, int H, int W, tfStream_t s);
+int tf_cfg3_sampler_step_bf16(void* latent, const void* eps3, void* x0_hist, const void* step_params, const void* coeffs, int rows, const void* edit_params,
+                              int B, int C, int H, int W, tfStream_t s);
+/* tf_image_from_u8_f16 (vae/vae.py:12-15 input) with a uint8 mask (B,H,W): out (B,3,H,W) NHWC fp16 = x / 127.5 - 1 where the mask byte is 0
+ * (bit-identical to tf_image_from_u8_f16 there), exactly 0 where it is not -- the masked image the inpainting model is conditioned on */
+int tf_image_from_u8_masked_f16(void* out, const void* image_u8, const void* mask_u8, int B, int H, int W, tfStream_t s);
+/* tf_means_to_latent_f32 (vae/vae.py:12-15 output) into a conditioning buffer: means (B,4,H,W) fp16 NHWC -> channels [c_off, c_off + 4) of
+ * cond (B,c_total,H,W) fp32 NCHW = scale * means.  Inpainting: scale 0.18215, c_off 1, c_total 5; edit: scale 1 (the unscaled mode), 0, 4 */
+int tf_means_to_cond_f32(void* cond, const void* means, int B, int H, int W, float scale, int c_off, int c_total, tfStream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,9 @@ returns x_{t-1}.  Differences, all MI355X-first:
 Beyond the UNet denoising path the next rows are built too: first_stage_model (VAE decode side, 8(f1))
 and cond_stage_model.transformer.text_model (CLIP text encoder, 8(f2)), under the reference's attribute names so that
 update_state walks the same LDM checkpoint keys.  The encoder side of first_stage_model feeds image-to-image and inpainting
-(``encode_image``, ``start(init_image= / init_latent=, mask=)``, ``compile(..., inpaint=True)``).
+(``encode_image``, ``start(init_image= / init_latent=, mask=)``, ``compile(..., inpaint=True)``) and the conditioning of the
+concat-conditioned checkpoints: the SD-1.5 inpainting UNet (SD15_INPAINT, 9 input channels) and InstructPix2Pix (SD15_EDIT, 8 input channels)
+run through ``compile(..., concat="inpaint" | "edit")`` and ``start(cond_image= / cond_mask= / cond_latent=, image_guidance=)``.
 """
 import ctypes
 from collections import namedtuple
@@ -19,7 +21,7 @@ import numpy as np
 from .. import config
 from ..native import hip
 from ..storage.tensor import Branch, DeviceArray, Stream, _sh, asarray, bfloat16, pool, use_stream
-from ..vision.unet import SD15, StepParams, UNetModel
+from ..vision.unet import SD15, SD15_EDIT, SD15_INPAINT, StepParams, UNetModel
 from .samplers import Schedule, UnsupportedSamplerConfig, get_alphas_cumprod  # noqa: F401  (get_alphas_cumprod: variants/sd.py:61-65, re-exported)
 
 
@@ -27,6 +29,9 @@ def _seed_words(seed):
     """A seed (any int; taken mod 2^64) -> the two 32-bit key words of the device generator."""
     seed = int(seed) % (1 << 64)
     return seed & 0xFFFFFFFF, seed >> 32
+
+
+_CONCAT_CHANNELS = {"inpaint": 5, "edit": 4}       # conditioning channels behind the 4 latent ones: [mask | masked-image latent], [image latent]
 
 
 def _scalar(v):
@@ -38,9 +43,10 @@ class StableDiffusion:
         self.alphas_cumprod = get_alphas_cumprod()
         self.model = namedtuple("DiffusionModel", ["diffusion_model"])(diffusion_model=UNetModel(cfg, init=init))
         from ..vae.vae import AutoencoderKL
-        self.first_stage_model = AutoencoderKL(init=init, init_encoder=False) if cfg is SD15 else None   # text-to-image uses the decode side only: the encoder stays an empty tree until update_state fills it (encode_image needs it)
+        sd15 = any(cfg is c for c in (SD15, SD15_INPAINT, SD15_EDIT))        # the three SD-1.5 checkpoints share the VAE and the text encoder
+        self.first_stage_model = AutoencoderKL(init=init, init_encoder=False) if sd15 else None   # text-to-image uses the decode side only: the encoder stays an empty tree until update_state fills it (encode_image needs it)
         self.cond_stage_model = None
-        if cfg is SD15:                  # variants/sd.py:12: cond_stage_model.transformer.text_model
+        if sd15:                         # variants/sd.py:12: cond_stage_model.transformer.text_model
             from ..vae.encoder import CLIPTextTransformer
             self.cond_stage_model = namedtuple("CondStageModel", ["transformer"])(
                 transformer=namedtuple("Transformer", ["text_model"])(text_model=CLIPTextTransformer(init=init)))
@@ -108,13 +114,7 @@ class StableDiffusion:
         """vae/vae.py:12-15 for image-to-image: uint8 (B,H,W,3) images (host or device) -> x0 = 0.18215 x means, a device fp32 NCHW latent
         (B,4,H/8,W/8) -- the inverse of decode's 1/0.18215 (variants/sd.py:49).  uint8 -> x/127.5 - 1 (tf_image_from_u8_f16) -> Encoder +
         quant_conv, means only (AutoencoderKL.encode) -> tf_means_to_latent_f32.  Asynchronous, on the current stream."""
-        fsm = self.first_stage_model
-        if fsm is None:
-            raise RuntimeError("StableDiffusion.encode_image: this model has no first_stage_model (SD-1.5 configuration only)")
-        enc = fsm.encoder
-        if any(m.weight is None for m in (enc.conv_in, enc.conv_out, fsm.quant_conv)):
-            raise RuntimeError("StableDiffusion.encode_image: the VAE encoder has no weights -- it is built empty; fill it with update_state "
-                               "from an LDM checkpoint (or synth_state_dict(param_shapes(model)))")
+        fsm = self._encoder_side("encode_image")
         if isinstance(images, DeviceArray):
             dev = images
         else:
@@ -136,6 +136,17 @@ class StableDiffusion:
         x0._base = (dev, x, means)                                       # (referenced until the kernels have run)
         return x0
 
+    def _encoder_side(self, who):
+        """first_stage_model with a filled encoder, or the RuntimeError ``who`` raises."""
+        fsm = self.first_stage_model
+        if fsm is None:
+            raise RuntimeError(f"StableDiffusion.{who}: this model has no first_stage_model (SD-1.5 configurations only)")
+        enc = fsm.encoder
+        if any(m.weight is None for m in (enc.conv_in, enc.conv_out, fsm.quant_conv)):
+            raise RuntimeError(f"StableDiffusion.{who}: the VAE encoder has no weights -- it is built empty; fill it with update_state "
+                               "from an LDM checkpoint (or synth_state_dict(param_shapes(model)))")
+        return fsm
+
     @staticmethod
     def latent_mask(mask):
         """Host helper: an inpainting mask at image resolution (B,H,W) -- bool, uint8 or float, >= 0.5 (uint8: nonzero) means repaint -- to the
@@ -156,6 +167,28 @@ class StableDiffusion:
         rep = (m != 0) if m.dtype == np.uint8 else (m >= 0.5)
         return rep.reshape(b, 1, h // 8, 8, w // 8, 8).any(axis=(3, 5)).astype(np.float32)
 
+    @staticmethod
+    def concat_mask_u8(mask):
+        """Host helper: an inpainting mask at image resolution (B,H,W) -- bool, uint8 or float, latent_mask's repaint convention (>= 0.5, uint8:
+        nonzero) -- binarised to uint8 (B,H,W), 1 = repaint: what tf_image_from_u8_masked_f16 reads to blank the masked image."""
+        m = np.asarray(mask)
+        if m.dtype != np.bool_ and m.dtype != np.uint8 and m.dtype.kind != "f":
+            raise TypeError(f"StableDiffusion.concat_mask: bool, uint8 or float masks, got {m.dtype}")
+        if m.dtype.kind == "f" and not (np.isfinite(m).all() and (m >= 0).all() and (m <= 1).all()):
+            raise ValueError("StableDiffusion.concat_mask: float mask values must lie in [0, 1]")
+        if m.ndim != 3 or m.shape[0] < 1 or m.shape[1] < 8 or m.shape[2] < 8 or m.shape[1] % 8 or m.shape[2] % 8:
+            raise ValueError(f"StableDiffusion.concat_mask: takes (B,H,W) with H and W multiples of 8, got {m.shape}")
+        return np.ascontiguousarray((m != 0) if m.dtype == np.uint8 else (m >= 0.5) if m.dtype.kind == "f" else m, dtype=np.uint8)
+
+    @staticmethod
+    def concat_mask(mask):
+        """Host helper: the mask channel of the SD-1.5 inpainting UNet, (B,1,H/8,W/8) fp32, from an image-resolution mask (B,H,W) (bool, uint8
+        or float; latent_mask's repaint convention).  The mask is binarised at image resolution, then latent pixel [i, j] takes image pixel
+        [8i, 8j]: the nearest-neighbour resize the inpainting weights were trained and are sampled with.  Deliberately NOT latent_mask's
+        maximum over each 8x8 block -- that rule serves the latent blend, where a latent pixel is repainted when any of its image pixels is;
+        here the channel is an input of the network and has to look like what it saw in training."""
+        return StableDiffusion.concat_mask_u8(mask)[:, None, ::8, ::8].astype(np.float32)
+
     # -- helpers ---------------------------------------------------------------------------------
     def _step_params(self):
         if self._params is None:
@@ -170,12 +203,24 @@ class StableDiffusion:
         (hip.tf_cfg_duplicate_bf16 if config.is_bf16() else hip.tf_cfg_duplicate_f16)(x2.ptr, latent.ptr, b, c, h, w, _sh())
         return x2
 
+    def _cfg_concat(self):
+        """variants/sd.py:31 for a concat-conditioned UNet: [latent | cond] for every guidance group, NHWC in the step's 16-bit type; an edit
+        model's first group (bit 0 of drop_bits) reads zeros in place of the conditioning."""
+        b, c, h, w = self._latent.shape
+        cc = self._cond.shape[1]
+        x = DeviceArray.empty((self._groups * b, c + cc, h, w), bfloat16 if config.is_bf16() else np.float16, "nhwc")
+        (hip.tf_cfg_concat_bf16 if config.is_bf16() else hip.tf_cfg_concat_f16)(
+            x.ptr, self._latent.ptr, self._cond.ptr, b, c, cc, h, w, self._groups, 0b001 if self._concat == "edit" else 0, _sh())
+        return x
+
     @staticmethod
-    def _stack_context(unconditional_context, context):
+    def _stack_context(unconditional_context, context, groups=2):
+        """[unc ; ctx], or for the three guidance branches of an edit model [unc ; unc ; ctx]."""
         b, t, d = context.shape
-        ctx = DeviceArray.empty((2 * b, t, d), context.dtype, "row")
-        hip.tf_memcpy_async(ctx.ptr, unconditional_context.ptr, context.nbytes, 3, _sh())
-        hip.tf_memcpy_async(ctx.ptr + context.nbytes, context.ptr, context.nbytes, 3, _sh())
+        ctx = DeviceArray.empty((groups * b, t, d), context.dtype, "row")
+        for g in range(groups):
+            src = context if g == groups - 1 else unconditional_context
+            hip.tf_memcpy_async(ctx.ptr + g * context.nbytes, src.ptr, context.nbytes, 3, _sh())
         if config.is_bf16():
             from ..ff.linear import to_bf16
             ctx = to_bf16(ctx)                                 # (the bfloat16 step takes fp16 or bfloat16 contexts)
@@ -204,7 +249,7 @@ class StableDiffusion:
         return out
 
     # -- whole-step HIP graph ------------------------------------------------------------------------
-    def compile(self, unconditional_context, context, latent, stream=None, warmup=2, timesteps=None, sampler=None, inpaint=False):
+    def compile(self, unconditional_context, context, latent, stream=None, warmup=2, timesteps=None, sampler=None, inpaint=False, concat=None):
         """Capture one denoising step for these (static) buffers into a HIP graph.  Afterwards
         ``step(timestep, a_t, a_prev, guidance)`` updates ``latent`` in place with one graph launch.
 
@@ -224,7 +269,31 @@ class StableDiffusion:
 
         ``inpaint=True`` (with a sampler only): the model owns private fp32 ``x0_init`` (the clean latent) and ``mask`` (B,1,H,W) buffers, the
         mask all ones, and the captured step ends in the masked update (tf_cfg_sampler_step_masked_*), which keeps the region where the mask is
-        0 on the noised trajectory of x0_init.  ``start(init_image= / init_latent=, mask=)`` fills them."""
+        0 on the noised trajectory of x0_init.  ``start(init_image= / init_latent=, mask=)`` fills them.
+
+        ``concat="inpaint" | "edit"`` (with a sampler only): a concat-conditioned UNet -- SD15_INPAINT, in_channels 9, reads [latent(4) | mask(1) |
+        0.18215 x means of the masked image(4)]; SD15_EDIT (InstructPix2Pix), in_channels 8, reads [latent(4) | unscaled means of the image to
+        edit(4)].  The model owns a private fp32 conditioning buffer (B, 5 | 4, h, w), zero until ``start(cond_image= / cond_latent=)`` fills it, and
+        the captured step opens with tf_cfg_concat_* in place of tf_cfg_duplicate_* (the same launch count).  "inpaint" runs the two CFG groups with
+        the conditioning in both and ends in tf_cfg_sampler_step_*; "edit" runs three groups [x|0, unc ; x|c, unc ; x|c, ctx] and ends in
+        tf_cfg3_sampler_step_*: e = e0 + g_T (e2 - e1) + g_I (e1 - e0), g_T the guidance of step_sampler / run and g_I the image guidance (1.5 until
+        ``start(image_guidance=)`` sets it).  A model whose in_channels is not 4 compiles with the matching ``concat`` only."""
+        cin = self.model.diffusion_model.cfg.in_channels
+        if concat not in (None, "inpaint", "edit"):
+            raise ValueError(f"StableDiffusion.compile: concat= takes None, 'inpaint' or 'edit', got {concat!r}")
+        if concat is None and cin != 4:
+            raise ValueError(f"StableDiffusion.compile: a UNet with in_channels={cin} is concat-conditioned: pass concat='inpaint' (9 channels) or concat='edit' (8)")
+        if concat is not None:
+            if sampler is None:
+                raise ValueError(f"StableDiffusion.compile: concat={concat!r} needs a sampler schedule (sampler=<Schedule>)")
+            if cin != 4 + _CONCAT_CHANNELS[concat]:
+                raise ValueError(f"StableDiffusion.compile: concat={concat!r} needs a UNet with in_channels={4 + _CONCAT_CHANNELS[concat]}, this one has {cin}")
+            if inpaint:
+                raise ValueError("StableDiffusion.compile: concat= and inpaint=True together (the latent blend on top of a concat-conditioned model) are not supported")
+            if config.cfg_parallel:
+                raise UnsupportedSamplerConfig("StableDiffusion.compile: a concat-conditioned model has no two-chain CFG form (TF_CFG_PARALLEL)")
+            if latent.shape[1] != 4:
+                raise ValueError(f"StableDiffusion.compile: the latent of a concat-conditioned model has 4 channels, got {latent.shape}")
         if config.is_bf16() and (config.parallel_branches or config.cfg_parallel):
             raise RuntimeError("StableDiffusion.compile: the bfloat16 step has no parallel-branch / two-chain CFG form (TF_PARALLEL_BRANCHES / TF_CFG_PARALLEL are fp16-only experiments)")
         if inpaint and sampler is None:
@@ -237,7 +306,8 @@ class StableDiffusion:
             timesteps = sampler.timesteps
         self._stream = stream or Stream()
         self._latent, self._unc, self._ctx = latent, unconditional_context, context
-        self._sched, self._inpaint = sampler, bool(inpaint)
+        self._sched, self._inpaint, self._concat = sampler, bool(inpaint), concat
+        self._groups = 3 if concat == "edit" else 2
         if sampler is not None:
             with use_stream(self._stream):
                 self._params = StepParams.__new__(StepParams)          # the sampler block: the 4 step scalars + row, seed, image offset
@@ -248,11 +318,16 @@ class StableDiffusion:
                     b, _, h, w = latent.shape
                     self._x0_init = DeviceArray.zeros(latent.shape, np.float32, "row")
                     self._mask = DeviceArray.from_numpy(np.ones((b, 1, h, w), np.float32), np.float32, "row")
+                if concat is not None:
+                    b, _, h, w = latent.shape
+                    self._cond = DeviceArray.zeros((b, _CONCAT_CHANNELS[concat], h, w), np.float32, "row")
+                    self._edit = DeviceArray.zeros((4,), np.float32, "row")      # [0] g_I, the image guidance of the three-branch update
+                    hip.tf_set_step_params(self._edit.ptr, 1.5, 0.0, 0.0, 0.0, _sh())
             self._seed, self._image_offset, self._cursor = (0, 0), 0, 0
         sp = self._step_params()
         unet = self.model.diffusion_model
         with use_stream(self._stream):
-            self._ctx2 = self._stack_context(unconditional_context, context)
+            self._ctx2 = self._stack_context(unconditional_context, context, self._groups)
             self._kv_all, self._kv_key, self._emb_cur, self._emb_rows, self._emb_key = None, None, None, {}, None
             if config.hoist_step_invariants and not config.cfg_parallel:
                 self._kv_all, self._kv_key = unet.context_kv(self._ctx2), unet.weights_key()
@@ -297,7 +372,8 @@ class StableDiffusion:
 
     def _eager_step(self, sp):
         b, c, h, w = self._latent.shape
-        x2 = self._cfg_duplicate(self._latent)
+        concat = getattr(self, "_concat", None)
+        x2 = self._cfg_concat() if concat else self._cfg_duplicate(self._latent)
         unet = self.model.diffusion_model
         if config.cfg_parallel:
             # the unconditional and the conditional half of the CFG pair (variants/sd.py:31-32) as two independent UNet chains: one runs
@@ -317,7 +393,10 @@ class StableDiffusion:
             out = unet(x2, sp, self._ctx2, shared=(None, self._emb_cur, self._kv_all))     # (step() has put this timestep's row into _emb_cur)
         else:
             out = unet(x2, sp, self._ctx2)
-        if getattr(self, "_inpaint", False):
+        if concat == "edit":
+            (hip.tf_cfg3_sampler_step_bf16 if config.is_bf16() else hip.tf_cfg3_sampler_step_f32)(
+                self._latent.ptr, out.ptr, self._x0_hist.ptr, sp.dev.ptr, self._coeffs.ptr, len(self._sched.timesteps), self._edit.ptr, b, c, h, w, _sh())
+        elif getattr(self, "_inpaint", False):
             (hip.tf_cfg_sampler_step_masked_bf16 if config.is_bf16() else hip.tf_cfg_sampler_step_masked_f32)(
                 self._latent.ptr, out.ptr, self._x0_hist.ptr, sp.dev.ptr, self._coeffs.ptr, len(self._sched.timesteps), self._x0_init.ptr, self._mask.ptr,
                 b, c, h, w, _sh())
@@ -362,7 +441,8 @@ class StableDiffusion:
             raise UnsupportedSamplerConfig(f"StableDiffusion.{what}: compile(..., sampler=<Schedule>) first (this model runs the DDIM step())")
         return self._sched
 
-    def start(self, seed=None, noise=None, image_offset=0, init_image=None, init_latent=None, mask=None):
+    def start(self, seed=None, noise=None, image_offset=0, init_image=None, init_latent=None, mask=None, cond_image=None, cond_mask=None,
+              cond_latent=None, image_guidance=None):
         """A new image batch for the compiled sampler: sets the latent in place and rewinds the schedule.  ``seed``: the initial latent is
         drawn on the device (tag 0; image b is global image image_offset + b), and the ancestral noise of every step comes from the same seed
         (tag 1); ``noise``: a host (B,C,H,W) array for the initial latent instead (the ancestral noise then uses ``seed``, default 0).
@@ -372,8 +452,23 @@ class StableDiffusion:
         sets latent = sqrt(a) x0 + sqrt(1 - a) z at the schedule's start level a = alphas[0] (Sampler.schedule(..., strength=)), z the tag-0
         noise of ``seed`` -- the noise a text-to-image start from that seed draws.  Inpainting (a model compiled with inpaint=True, which
         requires an init): ``mask`` -- a latent_mask() input, or a device fp32 (B,1,h,w) array; 1 = repaint -- is written into the model's mask
-        buffer (all ones without one) and x0 into its x0_init buffer."""
+        buffer (all ones without one) and x0 into its x0_init buffer.
+
+        A concat-conditioned model (compile(..., concat=)) needs its conditioning at every start, orthogonally to the arguments above (image-to-image
+        on an inpainting checkpoint works).  ``cond_image`` (uint8 (B,H,W,3), host or device) goes through the VAE encoder on the device: "edit"
+        keeps the unscaled means of the image; "inpaint" needs ``cond_mask`` too (a concat_mask() input, host (B,H,W); 1 = repaint) and writes
+        [concat_mask | 0.18215 x means of the image with the masked pixels set to 0].  ``cond_latent``: the fp32 (B, 5 | 4, h, w) conditioning itself,
+        host or device, copied as it is.  ``image_guidance`` ("edit" only): g_I of the three-branch update, kept until the next value.  Every
+        argument is checked before anything is written."""
         self._require_sampler("start")
+        cond = self._check_cond(cond_image, cond_mask, cond_latent, image_guidance)
+        latent = self._start_latent(seed, noise, image_offset, init_image, init_latent, mask)
+        if cond is not None:
+            self._write_cond(*cond)
+        return latent
+
+    def _start_latent(self, seed, noise, image_offset, init_image, init_latent, mask):
+        """start()'s latent side: text-to-image, image-to-image and the latent-blend inpainting buffers."""
         init = init_image if init_image is not None else init_latent
         if init_image is not None and init_latent is not None:
             raise ValueError("StableDiffusion.start: pass init_image= or init_latent=, not both")
@@ -432,6 +527,90 @@ class StableDiffusion:
                                       self._image_offset, _sh())
             self._start_keep = x0                                       # (referenced until the kernels have run)
         return self._latent
+
+    def _check_cond(self, cond_image, cond_mask, cond_latent, image_guidance):
+        """start()'s conditioning arguments, checked against the compiled model before anything changes: None for a model without concat=, else
+        (image or None, uint8 image-size mask or None, latent mask or None, cond_latent or None, g_I or None), host arrays converted."""
+        concat = getattr(self, "_concat", None)
+        if concat is None:
+            if any(v is not None for v in (cond_image, cond_mask, cond_latent, image_guidance)):
+                raise ValueError("StableDiffusion.start: cond_image=, cond_mask=, cond_latent= and image_guidance= need a model compiled with concat=")
+            return None
+        if cond_image is None and cond_latent is None:
+            raise ValueError(f"StableDiffusion.start: a model compiled with concat={concat!r} reads its conditioning channels at every step -- pass "
+                             "cond_image=" + (" and cond_mask=" if concat == "inpaint" else "") + ", or cond_latent=")
+        if cond_image is not None and cond_latent is not None:
+            raise ValueError("StableDiffusion.start: pass cond_image= or cond_latent=, not both")
+        if image_guidance is not None:
+            if concat != "edit":
+                raise ValueError("StableDiffusion.start: image_guidance= belongs to a model compiled with concat='edit'")
+            image_guidance = float(image_guidance)
+            if not np.isfinite(image_guidance):
+                raise ValueError(f"StableDiffusion.start: image_guidance={image_guidance}")
+        if cond_mask is not None and (concat != "inpaint" or cond_image is None):
+            raise ValueError("StableDiffusion.start: cond_mask= goes with cond_image= on a model compiled with concat='inpaint' (a cond_latent carries its mask channel)")
+        shape = self._cond.shape
+        if cond_latent is not None:
+            if isinstance(cond_latent, DeviceArray):
+                if cond_latent.shape != shape or cond_latent.dtype != np.float32 or cond_latent.layout != "row":
+                    raise ValueError(f"StableDiffusion.start: a device cond_latent must be an fp32 NCHW {shape} array, got {cond_latent}")
+            else:
+                cond_latent = np.ascontiguousarray(cond_latent, dtype=np.float32)
+                if cond_latent.shape != shape:
+                    raise ValueError(f"StableDiffusion.start: cond_latent must have the shape {shape}, got {cond_latent.shape}")
+            return None, None, None, cond_latent, image_guidance
+        self._encoder_side("start")
+        if not isinstance(cond_image, DeviceArray):
+            cond_image = np.ascontiguousarray(cond_image)
+        ish = tuple(int(v) for v in cond_image.shape)
+        if np.dtype(cond_image.dtype) != np.uint8 or len(ish) != 4 or ish[3] != 3 or (ish[0], ish[1], ish[2]) != (shape[0], 8 * shape[2], 8 * shape[3]):
+            raise ValueError(f"StableDiffusion.start: cond_image must be uint8 {(shape[0], 8 * shape[2], 8 * shape[3], 3)} for the compiled latent, "
+                             f"got {np.dtype(cond_image.dtype)} {ish}")
+        why = self.encoder_size_error(ish[1], ish[2])
+        if why:
+            raise ValueError(f"StableDiffusion.start: cond_image: {why}")
+        m8 = lat_mask = None
+        if concat == "inpaint":
+            if cond_mask is None:
+                raise ValueError("StableDiffusion.start: an inpainting checkpoint's cond_image= needs cond_mask= (the region to repaint)")
+            m8 = self.concat_mask_u8(cond_mask)
+            if m8.shape != ish[:3]:
+                raise ValueError(f"StableDiffusion.start: cond_mask is {m8.shape}, the cond_image needs {ish[:3]}")
+            lat_mask = self.concat_mask(m8)
+        return cond_image, m8, lat_mask, None, image_guidance
+
+    def _write_cond(self, image, m8, lat_mask, cond_latent, image_guidance):
+        """Fill the conditioning buffer (and g_I) on the sampler stream, behind every step already queued."""
+        if isinstance(image, DeviceArray) or isinstance(cond_latent, DeviceArray):
+            hip.tf_stream_sync(_sh())                                  # (made on the caller's stream)
+        self.synchronize()
+        b, cc, h, w = self._cond.shape
+        with use_stream(self._stream):
+            if image_guidance is not None:
+                hip.tf_set_step_params(self._edit.ptr, image_guidance, 0.0, 0.0, 0.0, _sh())
+            if isinstance(cond_latent, DeviceArray):
+                hip.tf_memcpy_async(self._cond.ptr, cond_latent.ptr, cond_latent.nbytes, 3, _sh())
+                self._cond_keep = cond_latent
+                return
+            if cond_latent is not None:
+                self._cond.copy_from_numpy(cond_latent)
+                return
+            fsm = self.first_stage_model
+            dev = image if isinstance(image, DeviceArray) else DeviceArray.from_numpy(image, np.uint8, "row")
+            x = DeviceArray.empty((b, 3, 8 * h, 8 * w), np.float16, "nhwc")      # NHWC: the (B,H,W,3) element order of the uint8 image
+            if m8 is None:                                                   # edit: the unscaled mode of the posterior
+                hip.tf_image_from_u8_f16(x.ptr, dev.ptr, x.size, _sh())
+                means = fsm.encode(x)
+                hip.tf_means_to_cond_f32(self._cond.ptr, means.ptr, b, h, w, 1.0, 0, cc, _sh())
+                self._cond_keep = (dev, x, means)                            # (referenced until the kernels have run)
+                return
+            dm8 = DeviceArray.from_numpy(m8, np.uint8, "row")
+            dlm = DeviceArray.from_numpy(lat_mask, np.float32, "row")
+            hip.tf_image_from_u8_masked_f16(x.ptr, dev.ptr, dm8.ptr, b, 8 * h, 8 * w, _sh())
+            means = fsm.encode(x)
+            hip.tf_memcpy_2d_async(self._cond.ptr, cc * h * w * 4, dlm.ptr, h * w * 4, h * w * 4, b, _sh())     # channel 0: the latent mask
+            hip.tf_means_to_cond_f32(self._cond.ptr, means.ptr, b, h, w, 0.18215, 1, cc, _sh())
+            self._cond_keep = (dev, x, means, dm8, dlm)
 
     def _mask_for_start(self, mask):
         """The inpainting mask start() writes: all ones without one; a device fp32 (B,1,h,w) array as it is; anything else through latent_mask."""
@@ -497,7 +676,7 @@ class StableDiffusion:
         """New prompts for the compiled step: refresh the stacked context in place (the captured graph reads these buffers) and the
         cross-attention K|V projection that was hoisted out of the step.  Ordered on the sampler stream."""
         with use_stream(self._stream):
-            new = self._stack_context(unconditional_context, context)       # (in the step's 16-bit type)
+            new = self._stack_context(unconditional_context, context, getattr(self, "_groups", 2))       # (in the step's 16-bit type)
             assert new.nbytes == self._ctx2.nbytes, "set_context: the contexts must have the shape the step was compiled for"
             hip.tf_memcpy_async(self._ctx2.ptr, new.ptr, new.nbytes, 3, _sh())
             self._ctx_tmp = new                                    # (referenced until the copy has run)

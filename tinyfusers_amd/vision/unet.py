@@ -12,7 +12,7 @@ Step-level batching that the reference does not do (results unchanged):
   * the channel concat of :72 is never materialised (GroupNorm / conv read both tensors), the nearest-2x
     upsample of :81-83 is folded into the following conv's gather.
 """
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Tuple
 
 import numpy as np
@@ -40,6 +40,8 @@ class UNetConfig:
 
 
 SD15 = UNetConfig()
+SD15_INPAINT = replace(SD15, in_channels=9)   # sd-v1-5-inpainting: [latent(4) | mask(1) | latent of the masked image(4)]
+SD15_EDIT = replace(SD15, in_channels=8)      # InstructPix2Pix: [latent(4) | latent of the image to edit(4)]
 TINY = UNetConfig(model_channels=64, channel_mult=(1, 2, 2), attention_levels=(0, 1), n_heads=2, context_dim=64)
 
 

@@ -3,9 +3,12 @@
 tf_cfg_sampler_step_f32) against the DDIM step (tf_cfg_ddim_step_f32), 100 graph replays each, alternated over several rounds; and the
 config-3 end-to-end img/s (CLIP x2 -> steps -> VAE decode, batch 1) at 20 DPM++2M steps against 50 DDIM steps.
 
-    python tools/sampler_bench.py [--replays 100] [--rounds 5] [--images 3] [--dpm-steps 20] [--inpaint]
+    python tools/sampler_bench.py [--replays 100] [--rounds 5] [--images 3] [--dpm-steps 20] [--inpaint] [--concat inpaint|edit]
 --inpaint adds the masked DPM++2M step (tf_cfg_sampler_step_masked_f32, a model compiled with inpaint=True on the same shape, half the
 latent repainted) to the alternation, and the VAE encoder's time for a 512^2 image (StableDiffusion.encode_image).
+--concat adds the DPM++2M step of a concat-conditioned UNet (SD15_INPAINT: 9 input channels, two CFG groups; SD15_EDIT: 8 input channels, three
+groups, so UNet batch 3 instead of 2) to the alternation -- the same weights but for conv_in -- and the time of start(cond_image=...) for a 512^2
+image (upload, VAE encoder, conditioning buffer).
 Prints one JSON line."""
 import argparse
 import contextlib
@@ -28,6 +31,7 @@ def main():
     ap.add_argument("--images", type=int, default=3)
     ap.add_argument("--dpm-steps", type=int, default=20)
     ap.add_argument("--inpaint", action="store_true", help="also time the masked step against the unmasked one, and the VAE encoder")
+    ap.add_argument("--concat", choices=["inpaint", "edit"], default=None, help="also time the step of the 9-channel inpainting / 8-channel edit UNet against the plain one")
     args = ap.parse_args()
 
     import torch  # noqa: F401  (the weight arena is a torch allocation)
@@ -66,6 +70,20 @@ def main():
         inp_m.compile(unc, ctx, lat_c, sampler=dpm_sched, inpaint=True)
         half = np.zeros((1, 1, 64, 64), np.float32); half[..., :32] = 1.0
         inp_m.start(seed=1234, init_latent=0.5 * noise, mask=half)
+    if args.concat:
+        from tinyfusers_amd.storage.synth import synth_tensor
+        from tinyfusers_amd.vision.unet import SD15_EDIT, SD15_INPAINT
+        cfg = SD15_INPAINT if args.concat == "inpaint" else SD15_EDIT
+        cat_m = StableDiffusion(cfg)
+        conv_in = "input_blocks.0.0.weight"
+        update_state(cat_m.model.diffusion_model, dict(state, **{conv_in: synth_tensor(0, conv_in, (320, cfg.in_channels, 3, 3))}), "")
+        cat_m.first_stage_model = ddim_m.first_stage_model                 # (the model whose first_stage_model holds weights)
+        lat_d = cat_m.latent_from_numpy(noise)
+        cat_m.compile(unc, ctx, lat_d, sampler=dpm_sched, concat=args.concat)
+        cond = 0.5 * synth_normal(1234, "sd.cond", (1, cfg.in_channels - 4, 64, 64))
+        if args.concat == "inpaint":
+            cond[:, 0] = 0.0; cond[:, 0, :, :32] = 1.0
+        cat_m.start(seed=1234, cond_latent=cond)
     lat0 = T.DeviceArray.from_numpy(noise, np.float32, "row")
     ts, al, ap_ = ddim_sched.timesteps, ddim_sched.alphas, ddim_sched.alphas_prev
 
@@ -92,6 +110,14 @@ def main():
                 hip.tf_memcpy_async(lat_c.ptr, lat0.ptr, lat_c.nbytes, 3, inp_m._stream.handle)
             inp_m.step_sampler(i, 7.5)
 
+    def cat_replays(n):
+        k = len(dpm_sched.timesteps)
+        for s in range(n):
+            i = s % k
+            if i == 0:
+                hip.tf_memcpy_async(lat_d.ptr, lat0.ptr, lat_d.nbytes, 3, cat_m._stream.handle)
+            cat_m.step_sampler(i, 7.5)
+
     def timed(model, fn, n):
         ev0, ev1, ms = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_float()
         hip.tf_event_create(ctypes.byref(ev0)); hip.tf_event_create(ctypes.byref(ev1))
@@ -109,11 +135,17 @@ def main():
     if args.inpaint:
         inp_replays(20)
         step_ms["dpmpp2m_masked"] = []
+    cat_key = f"dpmpp2m_concat_{args.concat}"
+    if args.concat:
+        cat_replays(20)
+        step_ms[cat_key] = []
     for _ in range(args.rounds):
         step_ms["ddim"].append(timed(ddim_m, ddim_replays, args.replays))
         step_ms["dpmpp2m"].append(timed(dpm_m, dpm_replays, args.replays))
         if args.inpaint:
             step_ms["dpmpp2m_masked"].append(timed(inp_m, inp_replays, args.replays))
+        if args.concat:
+            step_ms[cat_key].append(timed(cat_m, cat_replays, args.replays))
     med = {k: float(np.median(v)) for k, v in step_ms.items()}
     extra = {}
     if args.inpaint:
@@ -127,6 +159,17 @@ def main():
                 enc.append(time.perf_counter() - t0)                     # (includes the 0.75 MB host -> device upload of the image)
         extra = {"dpmpp2m_masked_step_ms": round(med["dpmpp2m_masked"], 4), "masked_over_unmasked": round(med["dpmpp2m_masked"] / med["dpmpp2m"], 4),
                  "encode_512_ms": round(1e3 * float(np.median(enc[1:])), 3)}
+    if args.concat:
+        img = np.random.default_rng(0).integers(0, 256, (1, 512, 512, 3), dtype=np.uint8)
+        kw = {"cond_mask": np.arange(512)[None, None, :].repeat(512, 1) < 256} if args.concat == "inpaint" else {}
+        cnd = []
+        for r in range(args.rounds + 1):
+            t0 = time.perf_counter()
+            cat_m.start(seed=1234, cond_image=img, **kw)
+            cat_m.synchronize()
+            cnd.append(time.perf_counter() - t0)                         # (includes the 0.75 MB host -> device upload of the image)
+        extra.update({f"{cat_key}_step_ms": round(med[cat_key], 4), "concat_over_plain": round(med[cat_key] / med["dpmpp2m"], 4),
+                      "start_cond_image_512_ms": round(1e3 * float(np.median(cnd[1:])), 3)})
 
     def e2e(model, steps, sample):
         recs = []
