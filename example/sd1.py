@@ -12,6 +12,7 @@ BASELINE config 3: full 50-step sampler, batch 1, end-to-end img/s.
     python -m example.sd1 --steps 20 --sampler dpmpp2m --init-image x.npy --strength 0.6 [--mask m.npy]   # img2img / inpainting
     python -m example.sd1 --steps 20 --sampler dpmpp2m --concat inpaint --cond-image x.npy --cond-mask m.npy   # the 9-channel inpainting UNet
     python -m example.sd1 --steps 20 --sampler dpmpp2m --concat edit --cond-image x.npy [--image-guidance 1.5]   # InstructPix2Pix (8 channels)
+    python -m example.sd1 --steps 20 --sampler dpmpp2m --control-image edges.npy [--control-ckpt control_v11p_sd15_canny.safetensors] [--control-scale 1.0]   # ControlNet
 With --ckpt the configuration is read off the checkpoint's conv_in (4, 9 or 8 input channels); --concat picks it on synthetic weights.
 """
 import argparse
@@ -45,7 +46,14 @@ if __name__ == "__main__":
     ap.add_argument("--cond-image", default="", help="the image a concat-conditioned UNet reads: the image to inpaint / to edit, (H,W,3) uint8; .npy, .png or .jpg")
     ap.add_argument("--cond-mask", default="", help="with an inpainting checkpoint: repaint where this (H,W) mask is >= 0.5 (uint8: nonzero)")
     ap.add_argument("--image-guidance", type=float, default=None, help="with an InstructPix2Pix checkpoint: the image guidance scale (default 1.5)")
+    ap.add_argument("--control-image", default="", help="condition on this ControlNet hint (edges, depth, pose ...), one (H,W,3) uint8 image; .npy, .png or .jpg")
+    ap.add_argument("--control-ckpt", default="", help="with --control-image: the ControlNet checkpoint (its control_model.* tensors); default: synthetic weights")
+    ap.add_argument("--control-scale", type=float, default=None, help="with --control-image: the strength of the control residuals (default 1.0)")
     args = ap.parse_args()
+    if (args.control_ckpt or args.control_scale is not None) and not args.control_image:
+        ap.error("--control-ckpt and --control-scale need --control-image")
+    if args.control_image and not args.sampler:
+        ap.error("--control-image needs --sampler")
     if (args.init_image or args.mask or args.strength is not None) and not args.sampler:
         ap.error("--init-image, --strength and --mask need --sampler")
     if (args.mask or args.strength is not None) and not args.init_image:
@@ -85,6 +93,8 @@ if __name__ == "__main__":
             ap.error(f"{what} needs --cond-image" + (" and --cond-mask" if concat == "inpaint" else "") + ": its UNet reads them at every step")
         if args.mask:
             ap.error("--mask (the latent blend) on top of a concat-conditioned checkpoint is not supported; use --cond-mask")
+    if concat and args.control_image:
+        ap.error("--control-image on a concat-conditioned checkpoint is not supported")
     if (args.cond_image or args.cond_mask or args.image_guidance is not None) and not concat:
         ap.error("--cond-image, --cond-mask and --image-guidance need an inpainting or InstructPix2Pix checkpoint (--ckpt, or --concat on synthetic weights)")
     if (args.cond_mask and concat != "inpaint") or (args.image_guidance is not None and concat != "edit"):
@@ -96,6 +106,20 @@ if __name__ == "__main__":
     with contextlib.redirect_stdout(io.StringIO()):
         update_state(model, state, "")
     del state
+    if args.control_image:
+        from tinyfusers_amd.vision.controlnet import ControlNet
+        net = ControlNet(SD15)
+        if args.control_ckpt:
+            from tinyfusers_amd.storage.unpicker import load_checkpoint
+            cstate = load_checkpoint(args.control_ckpt)
+            if not any(k.startswith("control_model.") for k in cstate):
+                sys.exit("--control-ckpt: the file holds no control_model.* tensors")
+        else:
+            cstate = synth_state_dict(param_shapes(net, "control_model"), 1)
+        with contextlib.redirect_stdout(io.StringIO()):
+            update_state(net, cstate, "control_model.")
+        del cstate
+        model.attach_control(net)
     print(f"weights installed in {time.time() - t0:.1f}s")
     # run through CLIP to get the contexts (example/sd1.py:44-49); token ids stand in for tokenizer.encode(prompt)
     if args.vocab:
@@ -151,6 +175,17 @@ if __name__ == "__main__":
             cond_kw["cond_mask"] = cond_mask[None] if cond_mask.ndim == 2 else cond_mask
         if args.image_guidance is not None:
             cond_kw["image_guidance"] = args.image_guidance
+    if args.control_image:
+        hint = load_array(args.control_image, "RGB")
+        hint = hint[None] if hint.ndim == 3 else hint
+        if hint.dtype != np.uint8 or hint.ndim != 4 or hint.shape[0] != 1 or hint.shape[3] != 3 or hint.shape[1] % 8 or hint.shape[2] % 8:
+            sys.exit(f"--control-image: expected one uint8 (H,W,3) image with H and W multiples of 8, got {hint.dtype} {hint.shape}")
+        if init_image is not None and init_image.shape != hint.shape:
+            sys.exit(f"--init-image {init_image.shape} and --control-image {hint.shape} differ in size")
+        lat_hw = (hint.shape[1] // 8, hint.shape[2] // 8)
+        cond_kw = {"control_image": hint}
+        if args.control_scale is not None:
+            cond_kw["control_scale"] = args.control_scale
     latent = model.latent_from_numpy(synth_normal(args.seed, "sd.latent", (1, 4) + lat_hw))
     if args.sampler:
         from tinyfusers_amd.variants.samplers import make
@@ -158,7 +193,7 @@ if __name__ == "__main__":
         schedule = make(args.sampler, args.eta).schedule(args.steps, strength=strength)
         print(f"sampler {schedule.sampler}: {len(schedule.timesteps)} steps, timesteps {schedule.timesteps[0]} .. {schedule.timesteps[-1]}"
               + (f" (strength {strength}{', inpainting' if mask is not None else ''})" if init_image is not None else ""))
-        model.compile(unconditional_context, context, latent, sampler=schedule, inpaint=mask is not None, concat=concat)
+        model.compile(unconditional_context, context, latent, sampler=schedule, inpaint=mask is not None, concat=concat, control=bool(args.control_image))
     else:
         model.compile(unconditional_context, context, latent)
     times = []

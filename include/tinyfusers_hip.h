@@ -505,6 +505,19 @@ int tf_cfg_sampler_step_masked_f32(void* latent, const void* eps2, void* x0_hist
 int tf_cfg_sampler_step_masked_bf16(void* latent, const void* eps2, void* x0_hist, const void* step_params, const void* coeffs, int rows, const void* x0_init,
                                     const void* mask, int B, int C, int H, int W, tfStream_t s);
 
+/* ---- ControlNet (csrc/control.hip; vision/controlnet.py): a second copy of the encoder half of vision/unet.py:51-76 whose 13 outputs are
+ * added to what the UNet saves for its skip concats (vision/unet.py:72) and to its middle block's output, inside the captured step. */
+typedef struct { void* dst; const void* skip; const void* residual; long long n; } tfControlEntry;
+/* ONE launch for up to 16 entries: dst_i[k] = round16(fmaf(scales[i], residual_i[k], skip_i[k])), k < n_i, 16-bit tensors of `dtype`.  table: a
+ * HOST array of n_entries tfControlEntry, copied into the kernel arguments by the call (nothing is uploaded; a captured graph node owns its
+ * copy); n_i a positive multiple of 8, every pointer 16-byte aligned.  scales: n_entries fp32 ON THE DEVICE, read when the kernel runs -- a
+ * strength written between two replays takes effect without a recapture.  scales[i] == 0 leaves dst_i = skip_i bit for bit (also where
+ * residual_i is not finite).  dst_i may be skip_i.  No atomics: deterministic */
+int tf_control_add_16(int dtype, const void* table, int n_entries, const void* scales_f32, tfStream_t s);
+/* uint8 (B,H,W,3) -> 16-bit x / 255 in the same element order: the [0, 1] NHWC (B,3,H,W) hint of the ControlNet stem (not the VAE's
+ * x / 127.5 - 1 of vae/vae.py:12-15); n = B*H*W*3 */
+int tf_hint_from_u8_16(int dtype, void* out, const void* x_u8, long long n, tfStream_t s);
+
 /* ---- concat-conditioned UNets (csrc/concat.hip): the SD-1.5 inpainting checkpoint (9 input channels [latent | mask | latent of the masked
  * image]) and InstructPix2Pix (8 input channels [latent | latent of the image to edit], three guidance branches) on the sampler above: the
  * CFG duplication of variants/sd.py:31 with the conditioning channels appended, the update of variants/sd.py:14-25 behind a three-branch

@@ -96,6 +96,12 @@ class _Hip:
 
 hip = _Hip()
 
+
+class ControlEntry(ctypes.Structure):
+    """tfControlEntry of include/tinyfusers_hip.h: one (dst, skip, residual, n elements) row of tf_control_add_16's host table."""
+    _fields_ = [("dst", ctypes.c_void_p), ("skip", ctypes.c_void_p), ("residual", ctypes.c_void_p), ("n", ctypes.c_longlong)]
+
+
 # per-shape GEMM configurations measured on MI355X for the SD-1.x step (tools/tune_best.sh); shapes that are not in the
 # table are autotuned on their first eager call
 # TF_GEMM_TUNE_TABLE=<path> uses another table, TF_GEMM_TUNE_TABLE= (empty) none: every shape is tuned afresh (tools/tune_best.sh)

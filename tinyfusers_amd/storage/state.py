@@ -47,7 +47,7 @@ def _slots(root, prefix=""):
                 continue
             else:
                 yield from walk(dotted, child, path)
-    yield from walk(prefix, root, frozenset())
+    yield from walk(prefix.rstrip("."), root, frozenset())      # ("control_model." and "control_model" name the same subtree)
 
 
 def _to_numpy(v):

@@ -12,6 +12,8 @@ update_state walks the same LDM checkpoint keys.  The encoder side of first_stag
 (``encode_image``, ``start(init_image= / init_latent=, mask=)``, ``compile(..., inpaint=True)``) and the conditioning of the
 concat-conditioned checkpoints: the SD-1.5 inpainting UNet (SD15_INPAINT, 9 input channels) and InstructPix2Pix (SD15_EDIT, 8 input channels)
 run through ``compile(..., concat="inpaint" | "edit")`` and ``start(cond_image= / cond_mask= / cond_latent=, image_guidance=)``.
+A ControlNet (vision/controlnet.py; ``attach_control``, ``compile(..., control=True)``, ``start(control_image= / control_hint=, control_scale=)``)
+runs inside the same captured step: its residuals enter the UNet's skip connections through one launch (tf_control_add_16).
 """
 import ctypes
 from collections import namedtuple
@@ -20,7 +22,7 @@ import numpy as np
 
 from .. import config
 from ..native import hip
-from ..storage.tensor import Branch, DeviceArray, Stream, _sh, asarray, bfloat16, pool, use_stream
+from ..storage.tensor import Branch, DeviceArray, Stream, _sh, asarray, bfloat16, dtag, pool, use_stream
 from ..vision.unet import SD15, SD15_EDIT, SD15_INPAINT, StepParams, UNetModel
 from .samplers import Schedule, UnsupportedSamplerConfig, get_alphas_cumprod  # noqa: F401  (get_alphas_cumprod: variants/sd.py:61-65, re-exported)
 
@@ -50,8 +52,21 @@ class StableDiffusion:
             from ..vae.encoder import CLIPTextTransformer
             self.cond_stage_model = namedtuple("CondStageModel", ["transformer"])(
                 transformer=namedtuple("Transformer", ["text_model"])(text_model=CLIPTextTransformer(init=init)))
+        self.control_model = None        # a ControlNet (vision/controlnet.py), under the LDM checkpoint's name: attach_control sets it
         self._params = None
         self._graph = None
+
+    def attach_control(self, net):
+        """Give the model a ControlNet (vision/controlnet.py) built for the UNet's configuration: ``compile(..., control=True)`` then captures
+        the controlled step.  update_state(sd, W) fills it from the checkpoint's ``control_model.*`` tensors."""
+        from dataclasses import replace
+        from ..vision.controlnet import ControlNet
+        if not isinstance(net, ControlNet):
+            raise TypeError(f"StableDiffusion.attach_control: takes a ControlNet, got {type(net).__name__}")
+        if replace(net.cfg, in_channels=4) != replace(self.model.diffusion_model.cfg, in_channels=4):
+            raise ValueError(f"StableDiffusion.attach_control: the ControlNet was built for {net.cfg}, the UNet is {self.model.diffusion_model.cfg}")
+        self.control_model = net
+        return self
 
     # -- reference surface -------------------------------------------------------------------------
     def get_model_output(self, unconditional_context, context, latent, timestep, unconditional_guidance_scale, params=None):
@@ -249,7 +264,7 @@ class StableDiffusion:
         return out
 
     # -- whole-step HIP graph ------------------------------------------------------------------------
-    def compile(self, unconditional_context, context, latent, stream=None, warmup=2, timesteps=None, sampler=None, inpaint=False, concat=None):
+    def compile(self, unconditional_context, context, latent, stream=None, warmup=2, timesteps=None, sampler=None, inpaint=False, concat=None, control=False):
         """Capture one denoising step for these (static) buffers into a HIP graph.  Afterwards
         ``step(timestep, a_t, a_prev, guidance)`` updates ``latent`` in place with one graph launch.
 
@@ -277,10 +292,28 @@ class StableDiffusion:
         the captured step opens with tf_cfg_concat_* in place of tf_cfg_duplicate_* (the same launch count).  "inpaint" runs the two CFG groups with
         the conditioning in both and ends in tf_cfg_sampler_step_*; "edit" runs three groups [x|0, unc ; x|c, unc ; x|c, ctx] and ends in
         tf_cfg3_sampler_step_*: e = e0 + g_T (e2 - e1) + g_I (e1 - e0), g_T the guidance of step_sampler / run and g_I the image guidance (1.5 until
-        ``start(image_guidance=)`` sets it).  A model whose in_channels is not 4 compiles with the matching ``concat`` only."""
+        ``start(image_guidance=)`` sets it).  A model whose in_channels is not 4 compiles with the matching ``concat`` only.
+
+        ``control=True`` (with a sampler and an attached ControlNet, ``attach_control``): the captured step runs the UNet's encoder, the ControlNet on
+        the same stacked latent, and one launch (tf_control_add_16) that adds the 13 residuals to the skip tensors and the middle output, scaled by a
+        device fp32 array -- all inside the one graph.  The model owns a private hint embedding (G B, model_channels, h, w), zero until
+        ``start(control_image= / control_hint=)`` fills it, the scales (all ones until ``start(control_scale=)``), and the ControlNet's hoisted K|V
+        projection; its time-embedding row travels behind the UNet's in the one buffer the parameter launch copies.  Combines with ``inpaint=True``
+        (the latent blend lives in the sampler tail); not with ``concat=``, TF_CFG_PARALLEL or the fp8 policy."""
         cin = self.model.diffusion_model.cfg.in_channels
         if concat not in (None, "inpaint", "edit"):
             raise ValueError(f"StableDiffusion.compile: concat= takes None, 'inpaint' or 'edit', got {concat!r}")
+        if control:
+            if self.control_model is None:
+                raise ValueError("StableDiffusion.compile: control=True needs a ControlNet: attach_control(ControlNet(cfg)) first")
+            if sampler is None:
+                raise ValueError("StableDiffusion.compile: control=True needs a sampler schedule (sampler=<Schedule>)")
+            if concat is not None:
+                raise ValueError(f"StableDiffusion.compile: control=True and concat={concat!r} together (a ControlNet on a concat-conditioned model) are not supported")
+            if config.cfg_parallel:
+                raise UnsupportedSamplerConfig("StableDiffusion.compile: a controlled model has no two-chain CFG form (TF_CFG_PARALLEL)")
+            if config.dtype == "fp8":
+                raise UnsupportedSamplerConfig("StableDiffusion.compile: control=True runs in the fp16 and the bf16 step, not under the fp8 policy (config.set_dtype('fp8'))")
         if concat is None and cin != 4:
             raise ValueError(f"StableDiffusion.compile: a UNet with in_channels={cin} is concat-conditioned: pass concat='inpaint' (9 channels) or concat='edit' (8)")
         if concat is not None:
@@ -306,7 +339,7 @@ class StableDiffusion:
             timesteps = sampler.timesteps
         self._stream = stream or Stream()
         self._latent, self._unc, self._ctx = latent, unconditional_context, context
-        self._sched, self._inpaint, self._concat = sampler, bool(inpaint), concat
+        self._sched, self._inpaint, self._concat, self._control = sampler, bool(inpaint), concat, bool(control)
         self._groups = 3 if concat == "edit" else 2
         if sampler is not None:
             with use_stream(self._stream):
@@ -323,15 +356,22 @@ class StableDiffusion:
                     self._cond = DeviceArray.zeros((b, _CONCAT_CHANNELS[concat], h, w), np.float32, "row")
                     self._edit = DeviceArray.zeros((4,), np.float32, "row")      # [0] g_I, the image guidance of the three-branch update
                     hip.tf_set_step_params(self._edit.ptr, 1.5, 0.0, 0.0, 0.0, _sh())
+                if control:
+                    b, _, h, w = latent.shape
+                    self._hint_emb = DeviceArray.zeros((self._groups * b, self.control_model.cfg.model_channels, h, w),
+                                                       bfloat16 if config.is_bf16() else np.float16, "nhwc")
+                    self._control_scales = DeviceArray.from_numpy(np.ones((16,), np.float32), np.float32, "row")     # one per residual; 16: whole 4-word writes
             self._seed, self._image_offset, self._cursor = (0, 0), 0, 0
         sp = self._step_params()
         unet = self.model.diffusion_model
         with use_stream(self._stream):
             self._ctx2 = self._stack_context(unconditional_context, context, self._groups)
-            self._kv_all, self._kv_key, self._emb_cur, self._emb_rows, self._emb_key = None, None, None, {}, None
+            self._kv_all, self._kv_key, self._emb_cur, self._emb_rows, self._emb_key, self._ckv_all = None, None, None, {}, None, None
             if config.hoist_step_invariants and not config.cfg_parallel:
-                self._kv_all, self._kv_key = unet.context_kv(self._ctx2), unet.weights_key()
-                _, row = unet.time_embedding_all(sp.set(981.0))
+                self._kv_all, self._kv_key = unet.context_kv(self._ctx2), self._weights_key()
+                if control:
+                    self._ckv_all = self.control_model.context_kv(self._ctx2)
+                row = self._time_row(sp.set(981.0))
                 self._emb_cur = DeviceArray.empty(row.shape, row.dtype, "row")       # what the captured step reads (fp16, or bfloat16 bits in the bf16 step)
                 assert self._emb_cur.nbytes % 16 == 0
                 hip.tf_memcpy_async(self._emb_cur.ptr, row.ptr, row.nbytes, 3, _sh())   # (the warm-up steps below run at t = 981)
@@ -389,7 +429,18 @@ class StableDiffusion:
             hip.tf_cfg_ddim_step2_f32(self._latent.ptr, out_u.ptr, out_c.ptr, sp.dev.ptr, b, c, h, w, _sh())
             self._keep = (x2, out_u, out_c, emb, emb_all, kv_all)
             return
-        if getattr(self, "_emb_cur", None) is not None:
+        if getattr(self, "_control", False):
+            # the UNet's encoder, then the ControlNet on the same stacked latent, then the seam (UNetModel.__call__ calls `residuals` behind its
+            # middle block); each model reads its own view of the hoisted row [UNet's | ControlNet's]
+            cn, scales = self.control_model, self._control_scales
+            if getattr(self, "_emb_cur", None) is not None:
+                nu = self._emb_cur.shape[1] - cn._prepare()["emb_w"].shape[0]
+                row_u, row_c = self._emb_cur.view((1, nu), "row"), self._emb_cur.view((1, self._emb_cur.shape[1] - nu), "row", nu)
+                residuals = lambda: cn(x2, self._hint_emb, sp, self._ctx2, shared=(None, row_c, self._ckv_all))
+                out = unet(x2, sp, self._ctx2, shared=(None, row_u, self._kv_all), control=(residuals, scales))
+            else:
+                out = unet(x2, sp, self._ctx2, control=(lambda: cn(x2, self._hint_emb, sp, self._ctx2), scales))
+        elif getattr(self, "_emb_cur", None) is not None:
             out = unet(x2, sp, self._ctx2, shared=(None, self._emb_cur, self._kv_all))     # (step() has put this timestep's row into _emb_cur)
         else:
             out = unet(x2, sp, self._ctx2)
@@ -427,12 +478,10 @@ class StableDiffusion:
 
     def _hoisted_row(self, timestep):
         """The cached time-embedding row of this timestep for the replay's parameter launch; refreshes the hoisted K|V first if a weight changed."""
-        key = self.model.diffusion_model.weights_key()
+        key = self._weights_key()
         if getattr(self, "_kv_all", None) is not None and self._kv_key != key:
             # a to_k / to_v (or any hoisted) weight was replaced since compile(): the K|V projection the graph reads is stale -- refresh it in place
-            kv = self.model.diffusion_model.context_kv(self._ctx2)
-            hip.tf_memcpy_async(self._kv_all.ptr, kv.ptr, kv.nbytes, 3, _sh())
-            self._kv_tmp, self._kv_key = kv, key
+            self._kv_tmp, self._kv_key = self._refresh_kv(), key
         return self._emb_row(float(timestep), key)     # (computed on this stream the first time a timestep is seen)
 
     # -- sampler schedules (compile(..., sampler=Schedule)) -----------------------------------------------------------------------
@@ -442,7 +491,7 @@ class StableDiffusion:
         return self._sched
 
     def start(self, seed=None, noise=None, image_offset=0, init_image=None, init_latent=None, mask=None, cond_image=None, cond_mask=None,
-              cond_latent=None, image_guidance=None):
+              cond_latent=None, image_guidance=None, control_image=None, control_hint=None, control_scale=None):
         """A new image batch for the compiled sampler: sets the latent in place and rewinds the schedule.  ``seed``: the initial latent is
         drawn on the device (tag 0; image b is global image image_offset + b), and the ancestral noise of every step comes from the same seed
         (tag 1); ``noise``: a host (B,C,H,W) array for the initial latent instead (the ancestral noise then uses ``seed``, default 0).
@@ -459,13 +508,86 @@ class StableDiffusion:
         keeps the unscaled means of the image; "inpaint" needs ``cond_mask`` too (a concat_mask() input, host (B,H,W); 1 = repaint) and writes
         [concat_mask | 0.18215 x means of the image with the masked pixels set to 0].  ``cond_latent``: the fp32 (B, 5 | 4, h, w) conditioning itself,
         host or device, copied as it is.  ``image_guidance`` ("edit" only): g_I of the three-branch update, kept until the next value.  Every
-        argument is checked before anything is written."""
+        argument is checked before anything is written.
+
+        A controlled model (compile(..., control=True)) needs its hint at every start: ``control_image`` (uint8 (B | 1, 8h, 8w, 3), host or device;
+        x / 255 on the device) or ``control_hint`` (a host float (B | 1, 3, 8h, 8w) array in [0, 1]) goes through the ControlNet's hint stem once,
+        here; a single hint serves every image.  ``control_scale``: the strength of the 13 residuals, one float or one per residual (12 skip
+        connections in input-block order, then the middle block); 1 when not given.  Hint and scales follow a new start without a recompile."""
         self._require_sampler("start")
+        ctrl = self._check_control(control_image, control_hint, control_scale)
         cond = self._check_cond(cond_image, cond_mask, cond_latent, image_guidance)
         latent = self._start_latent(seed, noise, image_offset, init_image, init_latent, mask)
         if cond is not None:
             self._write_cond(*cond)
+        if ctrl is not None:
+            self._write_control(*ctrl)
         return latent
+
+    def _check_control(self, control_image, control_hint, control_scale):
+        """start()'s ControlNet arguments, checked against the compiled model before anything changes: None for a model without control=True, else
+        (device or host uint8 image or None, host float hint or None, the 16 fp32 scale words)."""
+        if not getattr(self, "_control", False):
+            if any(v is not None for v in (control_image, control_hint, control_scale)):
+                raise ValueError("StableDiffusion.start: control_image=, control_hint= and control_scale= need a model compiled with control=True")
+            return None
+        if control_image is None and control_hint is None:
+            raise ValueError("StableDiffusion.start: a model compiled with control=True reads its hint at every step -- pass control_image= or control_hint=")
+        if control_image is not None and control_hint is not None:
+            raise ValueError("StableDiffusion.start: pass control_image= or control_hint=, not both")
+        b, _, h, w = self._latent.shape
+        n_res = len(self.control_model.input_blocks) + 1
+        scales = np.ones((16,), np.float32)
+        if control_scale is not None:
+            sc = np.asarray(control_scale, dtype=np.float32)
+            if sc.ndim > 1 or (sc.ndim == 1 and sc.shape[0] != n_res):
+                raise ValueError(f"StableDiffusion.start: control_scale= takes one float or {n_res} (one per residual), got shape {sc.shape}")
+            if not np.isfinite(sc).all():
+                raise ValueError(f"StableDiffusion.start: control_scale={control_scale}")
+            scales[:n_res] = sc
+        if control_image is not None:
+            if not isinstance(control_image, DeviceArray):
+                control_image = np.ascontiguousarray(control_image)
+            ish = tuple(int(v) for v in control_image.shape)
+            if np.dtype(control_image.dtype) != np.uint8 or len(ish) != 4 or ish[0] not in (1, b) or ish[1:] != (8 * h, 8 * w, 3):
+                raise ValueError(f"StableDiffusion.start: control_image must be uint8 {(b, 8 * h, 8 * w, 3)} (or one image for all) for the compiled latent, "
+                                 f"got {np.dtype(control_image.dtype)} {ish}")
+            return control_image, None, scales
+        if isinstance(control_hint, DeviceArray):
+            raise TypeError("StableDiffusion.start: control_hint= takes a host array (a device image goes through control_image=)")
+        hint = np.ascontiguousarray(control_hint, dtype=np.float32)
+        if hint.ndim != 4 or hint.shape[0] not in (1, b) or hint.shape[1:] != (3, 8 * h, 8 * w):
+            raise ValueError(f"StableDiffusion.start: control_hint must be float {(b, 3, 8 * h, 8 * w)} (or one hint for all) for the compiled latent, got {hint.shape}")
+        if not (np.isfinite(hint).all() and (hint >= 0).all() and (hint <= 1).all()):
+            raise ValueError("StableDiffusion.start: control_hint values must lie in [0, 1]")
+        return None, hint, scales
+
+    def _write_control(self, image, hint, scales):
+        """Fill the scales and the hint embedding of every guidance group on the sampler stream, behind every step already queued."""
+        if isinstance(image, DeviceArray):
+            hip.tf_stream_sync(_sh())                                  # (made on the caller's stream)
+        self.synchronize()
+        b, _, h, w = self._latent.shape
+        dt = self._hint_emb.dtype
+        with use_stream(self._stream):
+            for q in range(4):                                           # stream-ordered: the values travel as kernel arguments
+                hip.tf_set_step_params(self._control_scales.ptr + 16 * q, *(float(v) for v in scales[4 * q:4 * q + 4]), _sh())
+            if image is not None:
+                dev = image if isinstance(image, DeviceArray) else DeviceArray.from_numpy(image, np.uint8, "row")
+                x = DeviceArray.empty((dev.shape[0], 3, 8 * h, 8 * w), dt, "nhwc")     # NHWC: the (B,H,W,3) element order of the uint8 image
+                hip.tf_hint_from_u8_16(dtag(dt), x.ptr, dev.ptr, x.size, _sh())
+            else:
+                dev, x = None, DeviceArray.from_numpy(hint, dt, "nhwc")
+            emb = self.control_model.hint_embedding(x)
+            per = emb.nbytes // emb.shape[0]
+            assert emb.shape[1:] == self._hint_emb.shape[1:], (emb.shape, self._hint_emb.shape)
+            for g in range(self._groups):
+                if emb.shape[0] == b:
+                    hip.tf_memcpy_async(self._hint_emb.ptr + g * b * per, emb.ptr, b * per, 3, _sh())
+                else:                                                    # one hint for every image
+                    for k in range(b):
+                        hip.tf_memcpy_async(self._hint_emb.ptr + (g * b + k) * per, emb.ptr, per, 3, _sh())
+            self._control_keep = (dev, x, emb)                           # (referenced until the kernels have run)
 
     def _start_latent(self, seed, noise, image_offset, init_image, init_latent, mask):
         """start()'s latent side: text-to-image, image-to-image and the latent-blend inpainting buffers."""
@@ -659,8 +781,7 @@ class StableDiffusion:
 
     def _emb_row(self, t, key=None):
         """The cached time-embedding row of timestep t (keyed by the weights it was computed from; at most 1024 rows are kept)."""
-        unet = self.model.diffusion_model
-        key = unet.weights_key() if key is None else key
+        key = self._weights_key() if key is None else key
         if self._emb_key != key:
             self._emb_rows, self._emb_key = {}, key
         row = self._emb_rows.get(t)
@@ -668,9 +789,38 @@ class StableDiffusion:
             if len(self._emb_rows) >= 1024:
                 self._emb_rows.clear()
             tmp = StepParams().set(t)
-            row = self._emb_rows[t] = unet.time_embedding_all(tmp)[1]
+            row = self._emb_rows[t] = self._time_row(tmp)
             row._base = (row._base, tmp)
         return row
+
+    def _weights_key(self):
+        """weights_key() of everything the hoisted tables were computed from: the UNet and, in a controlled model, the ControlNet."""
+        key = self.model.diffusion_model.weights_key()
+        return key + self.control_model.weights_key() if getattr(self, "_control", False) else key
+
+    def _time_row(self, params):
+        """The hoisted time-embedding row of one timestep: the UNet's, and behind it in the same buffer a controlled model's ControlNet's -- one
+        copy in the parameter launch hands both to the replay."""
+        row = self.model.diffusion_model.time_embedding_all(params)[1]
+        if not getattr(self, "_control", False):
+            return row
+        crow = self.control_model.time_embedding_all(params)[1]
+        both = DeviceArray.empty((1, row.shape[1] + crow.shape[1]), row.dtype, "row")
+        hip.tf_memcpy_async(both.ptr, row.ptr, row.nbytes, 3, _sh())
+        hip.tf_memcpy_async(both.ptr + row.nbytes, crow.ptr, crow.nbytes, 3, _sh())
+        both._base = (row, crow)
+        return both
+
+    def _refresh_kv(self):
+        """Recompute the hoisted K|V projections of the stacked context into the buffers the captured step reads; returns what must stay referenced
+        until the copies have run."""
+        kv = self.model.diffusion_model.context_kv(self._ctx2)
+        hip.tf_memcpy_async(self._kv_all.ptr, kv.ptr, kv.nbytes, 3, _sh())
+        ckv = None
+        if getattr(self, "_ckv_all", None) is not None:
+            ckv = self.control_model.context_kv(self._ctx2)
+            hip.tf_memcpy_async(self._ckv_all.ptr, ckv.ptr, ckv.nbytes, 3, _sh())
+        return kv, ckv
 
     def set_context(self, unconditional_context, context):
         """New prompts for the compiled step: refresh the stacked context in place (the captured graph reads these buffers) and the
@@ -681,9 +831,7 @@ class StableDiffusion:
             hip.tf_memcpy_async(self._ctx2.ptr, new.ptr, new.nbytes, 3, _sh())
             self._ctx_tmp = new                                    # (referenced until the copy has run)
             if getattr(self, "_kv_all", None) is not None:
-                kv = self.model.diffusion_model.context_kv(self._ctx2)
-                hip.tf_memcpy_async(self._kv_all.ptr, kv.ptr, kv.nbytes, 3, _sh())
-                self._kv_tmp, self._kv_key = kv, self.model.diffusion_model.weights_key()   # (referenced until the copy has run)
+                self._kv_tmp, self._kv_key = self._refresh_kv(), self._weights_key()   # (referenced until the copies have run)
         self._unc, self._ctx = unconditional_context, context
 
     def synchronize(self):

@@ -122,9 +122,10 @@ def _conv(x, w, bias, padding, stride, dilation, bias_nc=None, residual=None, up
 _BAND_BYTES = 1 << 30      # patch-matrix bytes per launch of the small-C path
 
 
-def _conv_small_c(x, w, bias, padding, stride, cache, gn=0):
+def _conv_small_c(x, w, bias, padding, stride, cache, gn=0, residual=None):
     """Cin % 8 != 0 (the 4-channel conv_in): im2col to K padded to 64, then the same GEMM kernel -- as a 1x1 convolution over the
-    (n, ho, wo, kpad) patch image, so that the GroupNorm statistics of the output can ride along (gn) like for any other conv."""
+    (n, ho, wo, kpad) patch image, so that the GroupNorm statistics of the output can ride along (gn) like for any other conv, and a
+    residual (n, k, ho, wo) be added in its epilogue (a ControlNet's conv_in + hint embedding)."""
     n, c, h, wd = x.shape
     k, _, r, s = w.shape
     kk = r * s * c
@@ -139,10 +140,10 @@ def _conv_small_c(x, w, bias, padding, stride, cache, gn=0):
     if n * ho * wo * kpad * 2 <= _BAND_BYTES:
         col = DeviceArray.empty((n * ho * wo, kpad), x.dtype, "row")
         hip.tf_im2col_nhwc_f16(col.ptr, x.ptr, n, h, wd, c, r, s, stride[0], padding[0], kpad, _sh())     # (a 2-byte gather: either element type)
-        return _conv(col.view((n, kpad, ho, wo), "nhwc"), cache["w"].view((k, kpad, 1, 1), "nhwc"), bias, [0, 0], [1, 1], [1, 1], gn=gn)
+        return _conv(col.view((n, kpad, ho, wo), "nhwc"), cache["w"].view((k, kpad, 1, 1), "nhwc"), bias, [0, 0], [1, 1], [1, 1], residual=residual, gn=gn)
     # large images (the reference's own conv test is 10000 x 10000, tests/conv2d.py:13-33): bands of output rows, image by image,
     # each band's patch matrix and GEMM operands far below the 2 GiB one buffer descriptor spans
-    assert gn == 0, "banded small-C conv: no GroupNorm statistics"
+    assert gn == 0 and residual is None, "banded small-C conv: no GroupNorm statistics, no residual"
     y = DeviceArray.empty((n, k, ho, wo), x.dtype, "nhwc")
     rows = max(1, _BAND_BYTES // (wo * kpad * 2))
     wv = cache["w"].view((k, kpad, 1, 1), "nhwc")
@@ -258,8 +259,8 @@ class Conv2d:
             x8 = fp8.group_norm_mx(x, gn_in[0], gn_in[1])
             return fp8.conv2d_mx(x8, w8, wsc, self.bias, self.weight.shape, self.padding, bias_nc, residual, gn)
         if cin % 8 != 0:
-            assert bias_nc is None and residual is None and not upsample
+            assert bias_nc is None and not upsample
             if gn_in is not None:
                 x = gn_in[0](x, silu=gn_in[1])
-            return _conv_small_c(x, self.weight, self.bias, self.padding, self.stride, self._cache, gn)
+            return _conv_small_c(x, self.weight, self.bias, self.padding, self.stride, self._cache, gn, residual)
         return _conv(x, self.weight, self.bias, self.padding, self.stride, self.dilation, bias_nc, residual, upsample, gn, gn_in=gn_in, out_norm=out_norm)

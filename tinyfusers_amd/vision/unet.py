@@ -11,7 +11,11 @@ Step-level batching that the reference does not do (results unchanged):
     layer then reads its K|V column slice through SDPA strides;
   * the channel concat of :72 is never materialised (GroupNorm / conv read both tensors), the nearest-2x
     upsample of :81-83 is folded into the following conv's gather.
+
+The encoder half (block plan, batched projections, the walk over input_blocks and middle_block) lives in ``encoder_plan`` / ``StepModel``: a
+ControlNet (vision/controlnet.py) is a second copy of it, and ``UNetModel.__call__(control=...)`` takes its residuals in (``control_add``).
 """
+import ctypes
 from dataclasses import dataclass, replace
 from typing import Tuple
 
@@ -20,9 +24,9 @@ import numpy as np
 from ..attention.attention import SpatialTransformer, _concat_rows
 from ..ff.group_norm import GroupNorm
 from ..ff.linear import Linear, gemv_f16, linear_f16
-from ..native import hip
+from ..native import ControlEntry, hip
 from .. import config
-from ..storage.tensor import Branch, DeviceArray, Tensor, _sh, asarray, bfloat16, is_bfloat16
+from ..storage.tensor import Branch, DeviceArray, Tensor, _sh, asarray, bfloat16, dtag, is_bfloat16
 from .conv2d import Conv2d
 from .resnet import ResBlock
 
@@ -100,45 +104,39 @@ def timestep_embedding(timesteps, dim, max_period=10000):
     return out
 
 
-class UNetModel:
-    def __init__(self, cfg: UNetConfig = SD15, init=False):
-        self.cfg = cfg
-        mc, emb = cfg.model_channels, cfg.model_channels * 4
-        nh, cd = cfg.n_heads, cfg.context_dim
-        R = lambda i, o: ResBlock(i, emb, o, init=init)
-        S = lambda c: SpatialTransformer(c, cd, nh, c // nh, init=init)
-        self.time_embed = [Linear(mc, emb, init=init), Tensor.silu, Linear(emb, emb, init=init)]
-        self.input_blocks = [[Conv2d(cfg.in_channels, mc, kernel_size=[3, 3], padding=[1, 1], init=init)]]
-        chans, ch, nlev = [mc], mc, len(cfg.channel_mult)
-        for lev, mult in enumerate(cfg.channel_mult):
-            for _ in range(cfg.num_res_blocks):
-                blk = [R(ch, mc * mult)]
-                ch = mc * mult
-                if lev in cfg.attention_levels:
-                    blk.append(S(ch))
-                self.input_blocks.append(blk)
-                chans.append(ch)
-            if lev != nlev - 1:
-                self.input_blocks.append([Downsample(ch, init=init)])
-                chans.append(ch)
-        self.middle_block = [R(ch, ch), S(ch), R(ch, ch)]
-        self.output_blocks = []
-        for lev in reversed(range(nlev)):
-            mult = cfg.channel_mult[lev]
-            for i in range(cfg.num_res_blocks + 1):
-                blk = [R(ch + chans.pop(), mc * mult)]
-                ch = mc * mult
-                if lev in cfg.attention_levels:
-                    blk.append(S(ch))
-                if lev > 0 and i == cfg.num_res_blocks:
-                    blk.append(Upsample(ch, init=init))
-                self.output_blocks.append(blk)
-        self.out = [GroupNorm(32, mc, init=init), Tensor.silu, Conv2d(mc, cfg.out_channels, kernel_size=[3, 3], padding=[1, 1], init=init)]
-        self._batched = None
+def encoder_plan(cfg, in_channels, init=False):
+    """The encoder half of vision/unet.py:12-37 from the channel plan: (time_embed, input_blocks, middle_block, chans) -- chans[i] = the channel
+    count input block i saves for the skip concat.  Built once for the UNet and for a ControlNet (vision/controlnet.py), whose trunk is this."""
+    mc, emb = cfg.model_channels, cfg.model_channels * 4
+    nh, cd = cfg.n_heads, cfg.context_dim
+    R = lambda i, o: ResBlock(i, emb, o, init=init)
+    S = lambda c: SpatialTransformer(c, cd, nh, c // nh, init=init)
+    time_embed = [Linear(mc, emb, init=init), Tensor.silu, Linear(emb, emb, init=init)]
+    input_blocks = [[Conv2d(in_channels, mc, kernel_size=[3, 3], padding=[1, 1], init=init)]]
+    chans, ch, nlev = [mc], mc, len(cfg.channel_mult)
+    for lev, mult in enumerate(cfg.channel_mult):
+        for _ in range(cfg.num_res_blocks):
+            blk = [R(ch, mc * mult)]
+            ch = mc * mult
+            if lev in cfg.attention_levels:
+                blk.append(S(ch))
+            input_blocks.append(blk)
+            chans.append(ch)
+        if lev != nlev - 1:
+            input_blocks.append([Downsample(ch, init=init)])
+            chans.append(ch)
+    middle_block = [R(ch, ch), S(ch), R(ch, ch)]
+    return time_embed, input_blocks, middle_block, chans
+
+
+class StepModel:
+    """What the UNet and a ControlNet share: the step-level batched projections (one GEMV for every ResBlock's time-embedding Linear, one GEMM
+    for every cross-attention K|V) and the walk over the encoder half.  A subclass has cfg, time_embed, input_blocks, middle_block and, the
+    UNet, output_blocks."""
 
     # -- step-level batched projections (built once per weight set, on the device)
     def _all(self, kind):
-        blocks = [bb for b in self.input_blocks for bb in b] + list(self.middle_block) + [bb for b in self.output_blocks for bb in b]
+        blocks = [bb for b in self.input_blocks for bb in b] + list(self.middle_block) + [bb for b in getattr(self, "output_blocks", ()) for bb in b]
         return [bb for bb in blocks if isinstance(bb, kind)]
 
     def _prepare(self):
@@ -188,22 +186,26 @@ class UNetModel:
         emb, emb_all = self.time_embedding_all(timesteps)
         return emb, emb_all, self.context_kv(context)
 
-    def __call__(self, x, timesteps=None, context=None, shared=None):
-        cfg = self.cfg
+    def _shared(self, timesteps, context, shared):
+        """(emb, emb_all, kv_all, br) of one call: handed in (``shared``) or computed here; br is the open side branch the K|V projection runs
+        on (config.parallel_branches), joined by the first SpatialTransformer."""
         bt = self._prepare()
-        br = None
         if shared is not None:
-            emb, emb_all, kv_all = shared          # kv_all: this call's rows (b, tk, kv_n) of the step-level projection; emb may be None (emb_all is what the ResBlocks read)
-        else:
-            if config.parallel_branches and bt["kv_w"] is not None:
-                br = Branch()                          # the context projection is independent of the time-embedding chain
-                with br:
-                    kv_all = linear_f16(context, bt["kv_w"])      # (either element type since round 5)
-            emb, emb_all = self.time_embedding_all(timesteps)                            # Linear -> SiLU -> Linear, then every ResBlock's Linear(SiLU(emb))
-            if br is None:
-                kv_all = self.context_kv(context)                                         # every attn2's K|V of the context
+            return (*shared, None)                     # kv_all: this call's rows (b, tk, kv_n) of the step-level projection; emb may be None (emb_all is what the ResBlocks read)
+        br = kv_all = None
+        if config.parallel_branches and bt["kv_w"] is not None:
+            br = Branch()                              # the context projection is independent of the time-embedding chain
+            with br:
+                kv_all = linear_f16(context, bt["kv_w"])      # (either element type since round 5)
+        emb, emb_all = self.time_embedding_all(timesteps)                            # Linear -> SiLU -> Linear, then every ResBlock's Linear(SiLU(emb))
+        if br is None:
+            kv_all = self.context_kv(context)                                         # every attn2's K|V of the context
+        return emb, emb_all, kv_all, br
 
-        def run(x, bb, nxt, force_gn=0):
+    def _runner(self, emb, emb_all, kv_all, context):
+        bt = self._prepare()
+
+        def run(x, bb, nxt, force_gn=0, residual=None):
             # nxt = the module that reads this one's output as a single tensor (None across a concat): when it opens
             # with a GroupNorm, the statistics are produced by this module's last conv.  force_gn: the output (also) enters
             # an equal-split concat whose GroupNorm merges the two producers' partials (tf_group_norm_apply2_f16)
@@ -220,9 +222,16 @@ class UNetModel:
             if isinstance(bb, (Downsample, Upsample)):
                 return bb(x, out_gn=gn, out_norm=on)
             if isinstance(bb, Conv2d):
+                if residual is not None:                       # a ControlNet's conv_in: + the hint embedding, in the conv's epilogue
+                    return bb(x, residual=residual, gn=gn, out_norm=on)
                 return bb(x, gn=gn, out_norm=on)               # conv_in: its output feeds the first ResBlock's GroupNorm and the last skip concat
             return bb(x)
+        return run
 
+    def _encode(self, run, x, br=None, concat_stats=True, residual=None):
+        """input_blocks and middle_block over x: (the middle block's output, what every input block saves for the skip concats).  concat_stats:
+        the saved tensors and the output enter the output path's concats as they are -- their producers emit the statistics those concats'
+        GroupNorms merge (config.concat_stats).  residual: added to the first module's (conv_in's) output."""
         saved_inputs = []
         joined = br is None
         seq = [bb for b in self.input_blocks for bb in b] + list(self.middle_block)
@@ -236,12 +245,69 @@ class UNetModel:
             if not joined and isinstance(bb, SpatialTransformer):
                 br.join(); joined = True            # first consumer of kv_all
             # tensors saved for (or entering) the output path's concat carry 32-group statistics when the concat is an equal split
-            want = config.concat_stats and (i in ends or nxt is None) and x.size <= config.concat_stats_max_elems
-            x = run(x, bb, nxt, force_gn=32 if want else 0)
+            want = concat_stats and config.concat_stats and (i in ends or nxt is None) and x.size <= config.concat_stats_max_elems
+            x = run(x, bb, nxt, force_gn=32 if want else 0, residual=residual if i == 0 else None)
             if i in ends:
                 saved_inputs.append(x)
         if not joined:
             br.join()
+        return x, saved_inputs
+
+
+def control_add(skips, residuals, scales):
+    """The seam of a controlled step: new_i = skip_i + s_i residual_i for every tensor of ``skips`` in ONE launch (tf_control_add_16; s: the
+    device fp32 array ``scales``).  The new tensors carry no GroupNorm statistics (.gn) and no normalised twin (.normed): those of the skips
+    describe the tensors before the add."""
+    if len(residuals) != len(skips) or len(skips) > 16:
+        raise ValueError(f"control_add: {len(residuals)} residuals for {len(skips)} skip tensors (at most 16)")
+    if scales.dtype != np.float32 or scales.size < len(skips):
+        raise ValueError(f"control_add: scales must hold {len(skips)} fp32 values, got {scales}")
+    table, outs = (ControlEntry * len(skips))(), []
+    for e, k, r in zip(table, skips, residuals):
+        if r.shape != k.shape or r.layout != k.layout or dtag(r.dtype) != dtag(k.dtype) or k.dtype.itemsize != 2 or k.size % 8:
+            raise ValueError(f"control_add: residual {r} does not match the skip tensor {k} (16-bit, a multiple of 8 elements)")
+        o = DeviceArray.empty(k.shape, k.dtype, k.layout)
+        e.dst, e.skip, e.residual, e.n = o.ptr, k.ptr, r.ptr, k.size
+        o._base = (k, r)                                  # (referenced while the launch is queued)
+        outs.append(o)
+    hip.tf_control_add_16(dtag(skips[0].dtype), ctypes.cast(table, ctypes.c_void_p), len(skips), scales.ptr, _sh())
+    return outs
+
+
+class UNetModel(StepModel):
+    def __init__(self, cfg: UNetConfig = SD15, init=False):
+        self.cfg = cfg
+        mc, emb = cfg.model_channels, cfg.model_channels * 4
+        nh, cd = cfg.n_heads, cfg.context_dim
+        R = lambda i, o: ResBlock(i, emb, o, init=init)
+        S = lambda c: SpatialTransformer(c, cd, nh, c // nh, init=init)
+        self.time_embed, self.input_blocks, self.middle_block, chans = encoder_plan(cfg, cfg.in_channels, init)
+        ch, nlev = chans[-1], len(cfg.channel_mult)
+        self.output_blocks = []
+        for lev in reversed(range(nlev)):
+            mult = cfg.channel_mult[lev]
+            for i in range(cfg.num_res_blocks + 1):
+                blk = [R(ch + chans.pop(), mc * mult)]
+                ch = mc * mult
+                if lev in cfg.attention_levels:
+                    blk.append(S(ch))
+                if lev > 0 and i == cfg.num_res_blocks:
+                    blk.append(Upsample(ch, init=init))
+                self.output_blocks.append(blk)
+        self.out = [GroupNorm(32, mc, init=init), Tensor.silu, Conv2d(mc, cfg.out_channels, kernel_size=[3, 3], padding=[1, 1], init=init)]
+        self._batched = None
+
+    def __call__(self, x, timesteps=None, context=None, shared=None, control=None):
+        """control = (residuals, scales): a ControlNet's len(input_blocks) + 1 residual tensors (or a callable that returns them, called behind
+        the middle block) and the device fp32 array of their strengths.  Behind the middle block one launch (control_add) makes new skip tensors
+        and a new middle output, skip_i + s_i residual_i, which carry no statistics: the output path's concat GroupNorms then compute theirs
+        (ff/group_norm.py::_gn, the explicit path), and no producer is asked for concat statistics.  None: the step as it always was."""
+        emb, emb_all, kv_all, br = self._shared(timesteps, context, shared)
+        run = self._runner(emb, emb_all, kv_all, context)
+        x, saved_inputs = self._encode(run, x, br, concat_stats=control is None)
+        if control is not None:
+            residuals, scales = control
+            *saved_inputs, x = control_add(saved_inputs + [x], residuals() if callable(residuals) else residuals, scales)
         for bi, b in enumerate(self.output_blocks):
             x = (x, saved_inputs.pop())            # channel concat (unet.py:72), consumed un-materialised
             for j, bb in enumerate(b):
@@ -251,7 +317,7 @@ class UNetModel:
                 # the output enters the next concat: emit its statistics in sub-groups as wide as the 32 groups of the saved partner
                 # (32 sub-groups for an equal split, 64 for the 2:1 splits), so that the concat's GroupNorm is apply-only
                 fg = 0
-                if config.concat_stats and nxt is None and saved_inputs and saved_inputs[-1].size <= config.concat_stats_max_elems:
+                if control is None and config.concat_stats and nxt is None and saved_inputs and saved_inputs[-1].size <= config.concat_stats_max_elems:
                     c2 = saved_inputs[-1].shape[1]
                     sub = c2 // 32
                     if c2 % 32 == 0 and sub >= 4 and cout % sub == 0 and ((cout + c2) // 32) % sub == 0 and cout // sub <= 256:

@@ -3,12 +3,15 @@
 tf_cfg_sampler_step_f32) against the DDIM step (tf_cfg_ddim_step_f32), 100 graph replays each, alternated over several rounds; and the
 config-3 end-to-end img/s (CLIP x2 -> steps -> VAE decode, batch 1) at 20 DPM++2M steps against 50 DDIM steps.
 
-    python tools/sampler_bench.py [--replays 100] [--rounds 5] [--images 3] [--dpm-steps 20] [--inpaint] [--concat inpaint|edit]
+    python tools/sampler_bench.py [--replays 100] [--rounds 5] [--images 3] [--dpm-steps 20] [--inpaint] [--concat inpaint|edit] [--control]
 --inpaint adds the masked DPM++2M step (tf_cfg_sampler_step_masked_f32, a model compiled with inpaint=True on the same shape, half the
 latent repainted) to the alternation, and the VAE encoder's time for a 512^2 image (StableDiffusion.encode_image).
 --concat adds the DPM++2M step of a concat-conditioned UNet (SD15_INPAINT: 9 input channels, two CFG groups; SD15_EDIT: 8 input channels, three
 groups, so UNet batch 3 instead of 2) to the alternation -- the same weights but for conv_in -- and the time of start(cond_image=...) for a 512^2
 image (upload, VAE encoder, conditioning buffer).
+--control adds the controlled DPM++2M step (compile(..., control=True): the same UNet weights plus a synthetic SD-1.5 ControlNet) to the
+alternation, the time of start(control_image=...) for a 512^2 hint (upload, x / 255, the hint stem), and k_control_add's achieved GB/s on the
+13 skip shapes of the step next to tf_add_16 on the same byte count.
 Prints one JSON line."""
 import argparse
 import contextlib
@@ -24,6 +27,40 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def control_add_bench(T, hip, model, timed, args):
+    """k_control_add (one launch over the 13 skip shapes of the SD-1.5 step at CFG batch 2) against tf_add_16 (one launch over one tensor of the
+    same byte count): achieved GB/s of each, two reads and one write of every element, medians of --rounds rounds of --replays launches."""
+    from tinyfusers_amd.native import ControlEntry
+    shapes = [(2, c, s, s) for c, s in zip([320] * 4 + [640] * 3 + [1280] * 6, [64] * 3 + [32] * 3 + [16] * 3 + [8] * 4)]
+    with T.use_stream(model._stream):
+        skips, ress, dsts = ([T.DeviceArray.zeros(sh, np.float16, "nhwc") for sh in shapes] for _ in range(3))
+        total = sum(k.size for k in skips)
+        a, b, y = (T.DeviceArray.zeros((total,), np.float16, "row") for _ in range(3))
+        scales = T.DeviceArray.from_numpy(np.full((16,), 0.75, np.float32), np.float32, "row")
+    table = (ControlEntry * len(shapes))()
+    for e, d, k, r in zip(table, dsts, skips, ress):
+        e.dst, e.skip, e.residual, e.n = d.ptr, k.ptr, r.ptr, k.size
+    tp = ctypes.cast(table, ctypes.c_void_p)
+
+    def ctl(n):
+        for _ in range(n):
+            hip.tf_control_add_16(0, tp, len(shapes), scales.ptr, model._stream.handle)
+
+    def add(n):
+        for _ in range(n):
+            hip.tf_add_16(0, y.ptr, a.ptr, b.ptr, total, model._stream.handle)
+
+    ctl(10); add(10)
+    ms = {"ctl": [], "add": []}
+    for _ in range(args.rounds):
+        ms["ctl"].append(timed(model, ctl, args.replays))
+        ms["add"].append(timed(model, add, args.replays))
+    nbytes = 3 * 2 * total
+    c, d = float(np.median(ms["ctl"])), float(np.median(ms["add"]))
+    return {"control_add_bytes": nbytes, "control_add_us": round(1e3 * c, 2), "control_add_gb_s": round(nbytes / c / 1e6, 1),
+            "add_16_us": round(1e3 * d, 2), "add_16_gb_s": round(nbytes / d / 1e6, 1)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--replays", type=int, default=100)
@@ -32,6 +69,7 @@ def main():
     ap.add_argument("--dpm-steps", type=int, default=20)
     ap.add_argument("--inpaint", action="store_true", help="also time the masked step against the unmasked one, and the VAE encoder")
     ap.add_argument("--concat", choices=["inpaint", "edit"], default=None, help="also time the step of the 9-channel inpainting / 8-channel edit UNet against the plain one")
+    ap.add_argument("--control", action="store_true", help="also time the ControlNet-conditioned step against the plain one, start(control_image=), and k_control_add")
     args = ap.parse_args()
 
     import torch  # noqa: F401  (the weight arena is a torch allocation)
@@ -84,6 +122,16 @@ def main():
         if args.concat == "inpaint":
             cond[:, 0] = 0.0; cond[:, 0, :, :32] = 1.0
         cat_m.start(seed=1234, cond_latent=cond)
+    if args.control:
+        from tinyfusers_amd.vision.controlnet import ControlNet
+        ctl_m, net = StableDiffusion(), ControlNet()
+        update_state(ctl_m.model.diffusion_model, state, "")
+        with contextlib.redirect_stdout(io.StringIO()):
+            update_state(net, synth_state_dict(param_shapes(net), 1), "")
+        lat_e = ctl_m.latent_from_numpy(noise)
+        ctl_m.attach_control(net).compile(unc, ctx, lat_e, sampler=dpm_sched, control=True)
+        hint_img = np.random.default_rng(1).integers(0, 256, (1, 512, 512, 3), dtype=np.uint8)
+        ctl_m.start(seed=1234, control_image=hint_img)
     lat0 = T.DeviceArray.from_numpy(noise, np.float32, "row")
     ts, al, ap_ = ddim_sched.timesteps, ddim_sched.alphas, ddim_sched.alphas_prev
 
@@ -118,6 +166,14 @@ def main():
                 hip.tf_memcpy_async(lat_d.ptr, lat0.ptr, lat_d.nbytes, 3, cat_m._stream.handle)
             cat_m.step_sampler(i, 7.5)
 
+    def ctl_replays(n):
+        k = len(dpm_sched.timesteps)
+        for s in range(n):
+            i = s % k
+            if i == 0:
+                hip.tf_memcpy_async(lat_e.ptr, lat0.ptr, lat_e.nbytes, 3, ctl_m._stream.handle)
+            ctl_m.step_sampler(i, 7.5)
+
     def timed(model, fn, n):
         ev0, ev1, ms = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_float()
         hip.tf_event_create(ctypes.byref(ev0)); hip.tf_event_create(ctypes.byref(ev1))
@@ -139,6 +195,9 @@ def main():
     if args.concat:
         cat_replays(20)
         step_ms[cat_key] = []
+    if args.control:
+        ctl_replays(20)
+        step_ms["dpmpp2m_control"] = []
     for _ in range(args.rounds):
         step_ms["ddim"].append(timed(ddim_m, ddim_replays, args.replays))
         step_ms["dpmpp2m"].append(timed(dpm_m, dpm_replays, args.replays))
@@ -146,6 +205,8 @@ def main():
             step_ms["dpmpp2m_masked"].append(timed(inp_m, inp_replays, args.replays))
         if args.concat:
             step_ms[cat_key].append(timed(cat_m, cat_replays, args.replays))
+        if args.control:
+            step_ms["dpmpp2m_control"].append(timed(ctl_m, ctl_replays, args.replays))
     med = {k: float(np.median(v)) for k, v in step_ms.items()}
     extra = {}
     if args.inpaint:
@@ -170,6 +231,16 @@ def main():
             cnd.append(time.perf_counter() - t0)                         # (includes the 0.75 MB host -> device upload of the image)
         extra.update({f"{cat_key}_step_ms": round(med[cat_key], 4), "concat_over_plain": round(med[cat_key] / med["dpmpp2m"], 4),
                       "start_cond_image_512_ms": round(1e3 * float(np.median(cnd[1:])), 3)})
+
+    if args.control:
+        st = []
+        for r in range(args.rounds + 1):
+            t0 = time.perf_counter()
+            ctl_m.start(seed=1234, control_image=hint_img)
+            ctl_m.synchronize()
+            st.append(time.perf_counter() - t0)                          # (includes the 0.75 MB host -> device upload of the hint)
+        extra.update({"dpmpp2m_control_step_ms": round(med["dpmpp2m_control"], 4), "control_over_plain": round(med["dpmpp2m_control"] / med["dpmpp2m"], 4),
+                      "start_control_image_512_ms": round(1e3 * float(np.median(st[1:])), 3), **control_add_bench(T, hip, ctl_m, timed, args)})
 
     def e2e(model, steps, sample):
         recs = []
