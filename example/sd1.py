@@ -13,6 +13,7 @@ BASELINE config 3: full 50-step sampler, batch 1, end-to-end img/s.
     python -m example.sd1 --steps 20 --sampler dpmpp2m --concat inpaint --cond-image x.npy --cond-mask m.npy   # the 9-channel inpainting UNet
     python -m example.sd1 --steps 20 --sampler dpmpp2m --concat edit --cond-image x.npy [--image-guidance 1.5]   # InstructPix2Pix (8 channels)
     python -m example.sd1 --steps 20 --sampler dpmpp2m --control-image edges.npy [--control-ckpt control_v11p_sd15_canny.safetensors] [--control-scale 1.0]   # ControlNet
+    python -m example.sd1 --steps 20 --sampler dpmpp2m --lora style.safetensors:0.8 --lora lcm.safetensors:1:0   # LoRA adapters, FILE[:w[:w_te]], merged on the device
 With --ckpt the configuration is read off the checkpoint's conv_in (4, 9 or 8 input channels); --concat picks it on synthetic weights.
 """
 import argparse
@@ -49,7 +50,27 @@ if __name__ == "__main__":
     ap.add_argument("--control-image", default="", help="condition on this ControlNet hint (edges, depth, pose ...), one (H,W,3) uint8 image; .npy, .png or .jpg")
     ap.add_argument("--control-ckpt", default="", help="with --control-image: the ControlNet checkpoint (its control_model.* tensors); default: synthetic weights")
     ap.add_argument("--control-scale", type=float, default=None, help="with --control-image: the strength of the control residuals (default 1.0)")
+    ap.add_argument("--lora", action="append", default=[], metavar="FILE[:w[:w_te]]",
+                    help="merge this LoRA adapter (.safetensors / .ckpt / .pt; kohya or PEFT keys) at UNet weight w (default 1) and text-encoder weight w_te "
+                         "(default w); repeatable")
     args = ap.parse_args()
+    loras = []
+    for spec in args.lora:
+        parts = spec.split(":")
+        cut = len(parts)
+        while cut > 1 and len(parts) - cut < 2:
+            try:
+                float(parts[cut - 1])
+            except ValueError:
+                break
+            cut -= 1
+        try:
+            ws = [float(v) for v in parts[cut:]]
+        except ValueError:
+            ws = None
+        if ws is None or not parts[0]:
+            ap.error(f"--lora {spec}: expected FILE[:w[:w_te]]")
+        loras.append((":".join(parts[:cut]), ws[0] if ws else 1.0, ws[1] if len(ws) > 1 else (ws[0] if ws else 1.0)))
     if (args.control_ckpt or args.control_scale is not None) and not args.control_image:
         ap.error("--control-ckpt and --control-scale need --control-image")
     if args.control_image and not args.sampler:
@@ -121,6 +142,12 @@ if __name__ == "__main__":
         del cstate
         model.attach_control(net)
     print(f"weights installed in {time.time() - t0:.1f}s")
+    if loras:                                                    # before the prompts are encoded (text-encoder adapters) and before compile
+        t0 = time.perf_counter()
+        names = [model.load_lora(path, name=f"{i}:{os.path.basename(path)}") for i, (path, _, _) in enumerate(loras)]
+        model.set_adapters(names, [w for _, w, _ in loras], [w for _, _, w in loras])
+        T.hip.tf_stream_sync(None)
+        print(f"LoRA: {', '.join(f'{n} at {w} / {wt}' for n, (w, wt) in model.adapters().items())} merged in {1e3 * (time.perf_counter() - t0):.1f} ms (load + merge)")
     # run through CLIP to get the contexts (example/sd1.py:44-49); token ids stand in for tokenizer.encode(prompt)
     if args.vocab:
         from tinyfusers_amd.tokenizer.clip import ClipTokenizer

@@ -505,6 +505,19 @@ int tf_cfg_sampler_step_masked_f32(void* latent, const void* eps2, void* x0_hist
 int tf_cfg_sampler_step_masked_bf16(void* latent, const void* eps2, void* x0_hist, const void* step_params, const void* coeffs, int rows, const void* x0_init,
                                     const void* mask, int B, int C, int H, int W, tfStream_t s);
 
+/* ---- LoRA adapters (csrc/lora.hip; storage/lora.py, variants/sd.py:set_adapters): the reference has no adapters -- its weights come from
+ * update_state alone (storage/checkpoint.py).  Every weight is a row matrix (N, Kd) of 16-bit elements: a Linear (out, in), a conv in KRSC
+ * storage (K, R S C); an adapter of it is up (N, r) and down (r, Kd). */
+typedef struct { const void* up; const void* down_t; int rp; float scale; } tfLoraEntry;
+/* ONE launch merges up to 8 adapters into a fresh copy of a weight:
+ *   dst[n, k] = round16(base[n, k] + sum_i scale_i * sum_j up_i[n, j] * down_i[j, k]),  16-bit tensors of `dtype`.
+ * table: a HOST array of n_adapters tfLoraEntry, copied into the kernel arguments by the call (nothing is uploaded).  up_i is (N, rp_i) and
+ * down_t_i the TRANSPOSED down (Kd, rp_i), both contiguous along the rank, the rank zero-padded to rp_i, a multiple of 32; both 16-byte aligned.
+ * The inner sum runs on the 16-bit MFMA with an fp32 accumulator per adapter (products of two 16-bit values are exact in fp32), scale_i is applied
+ * to the accumulator, the base is added in fp32 and the sum is rounded once.  scale_i == 0 contributes nothing whatever the adapter holds; with
+ * every scale 0 dst has base's bits.  Any N, Kd >= 1; dst and base are distinct buffers, base is only read.  No atomics: deterministic */
+int tf_lora_merge_16(int dtype, void* dst, const void* base, const void* table, int n_adapters, int N, int Kd, tfStream_t s);
+
 /* ---- ControlNet (csrc/control.hip; vision/controlnet.py): a second copy of the encoder half of vision/unet.py:51-76 whose 13 outputs are
  * added to what the UNet saves for its skip concats (vision/unet.py:72) and to its middle block's output, inside the captured step. */
 typedef struct { void* dst; const void* skip; const void* residual; long long n; } tfControlEntry;

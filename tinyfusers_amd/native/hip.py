@@ -102,6 +102,11 @@ class ControlEntry(ctypes.Structure):
     _fields_ = [("dst", ctypes.c_void_p), ("skip", ctypes.c_void_p), ("residual", ctypes.c_void_p), ("n", ctypes.c_longlong)]
 
 
+class LoraEntry(ctypes.Structure):
+    """tfLoraEntry of include/tinyfusers_hip.h: one (up (N, rp), down_t (Kd, rp), rp, scale) row of tf_lora_merge_16's host table."""
+    _fields_ = [("up", ctypes.c_void_p), ("down_t", ctypes.c_void_p), ("rp", ctypes.c_int), ("scale", ctypes.c_float)]
+
+
 # per-shape GEMM configurations measured on MI355X for the SD-1.x step (tools/tune_best.sh); shapes that are not in the
 # table are autotuned on their first eager call
 # TF_GEMM_TUNE_TABLE=<path> uses another table, TF_GEMM_TUNE_TABLE= (empty) none: every shape is tuned afresh (tools/tune_best.sh)

@@ -14,6 +14,8 @@ concat-conditioned checkpoints: the SD-1.5 inpainting UNet (SD15_INPAINT, 9 inpu
 run through ``compile(..., concat="inpaint" | "edit")`` and ``start(cond_image= / cond_mask= / cond_latent=, image_guidance=)``.
 A ControlNet (vision/controlnet.py; ``attach_control``, ``compile(..., control=True)``, ``start(control_image= / control_hint=, control_scale=)``)
 runs inside the same captured step: its residuals enter the UNet's skip connections through one launch (tf_control_add_16).
+LoRA adapters (storage/lora.py; ``load_lora``, ``set_adapters``, ``adapters``, ``unload_lora``) are merged on the device into fresh weight buffers
+(tf_lora_merge_16, one launch per touched module, from the kept base weight); a compiled model re-captures its step.
 """
 import ctypes
 from collections import namedtuple
@@ -55,6 +57,7 @@ class StableDiffusion:
         self.control_model = None        # a ControlNet (vision/controlnet.py), under the LDM checkpoint's name: attach_control sets it
         self._params = None
         self._graph = None
+        self._lora = None                # storage/lora.py::LoraRegistry, made by the first load_lora
 
     def attach_control(self, net):
         """Give the model a ControlNet (vision/controlnet.py) built for the UNet's configuration: ``compile(..., control=True)`` then captures
@@ -251,6 +254,7 @@ class StableDiffusion:
         every step already queued (the sampler stream is drained first)."""
         self.synchronize()
         self._latent.copy_from_numpy(x)
+        self._needs_start = False
         return self._latent
 
     @staticmethod
@@ -299,7 +303,9 @@ class StableDiffusion:
         device fp32 array -- all inside the one graph.  The model owns a private hint embedding (G B, model_channels, h, w), zero until
         ``start(control_image= / control_hint=)`` fills it, the scales (all ones until ``start(control_scale=)``), and the ControlNet's hoisted K|V
         projection; its time-embedding row travels behind the UNet's in the one buffer the parameter launch copies.  Combines with ``inpaint=True``
-        (the latent blend lives in the sampler tail); not with ``concat=``, TF_CFG_PARALLEL or the fp8 policy."""
+        (the latent blend lives in the sampler tail); not with ``concat=``, TF_CFG_PARALLEL or the fp8 policy.
+
+        The arguments are remembered: ``set_adapters`` (LoRA) on a compiled model swaps weight handles and calls ``compile`` again with the same ones."""
         cin = self.model.diffusion_model.cfg.in_channels
         if concat not in (None, "inpaint", "edit"):
             raise ValueError(f"StableDiffusion.compile: concat= takes None, 'inpaint' or 'edit', got {concat!r}")
@@ -337,6 +343,9 @@ class StableDiffusion:
             if config.cfg_parallel:
                 raise UnsupportedSamplerConfig("StableDiffusion.compile: a sampler schedule has no two-chain CFG form (TF_CFG_PARALLEL is an fp16-only experiment)")
             timesteps = sampler.timesteps
+        self._compile_args = dict(unconditional_context=unconditional_context, context=context, latent=latent, warmup=warmup, timesteps=timesteps,
+                                  sampler=sampler, inpaint=inpaint, concat=concat, control=control)       # (set_adapters captures the step again)
+        self._needs_start = False
         self._stream = stream or Stream()
         self._latent, self._unc, self._ctx = latent, unconditional_context, context
         self._sched, self._inpaint, self._concat, self._control = sampler, bool(inpaint), concat, bool(control)
@@ -461,9 +470,11 @@ class StableDiffusion:
     def step(self, timestep, a_t, a_prev, guidance, eager=False):
         """One denoising step on the sampler stream, asynchronous.  The stream switch is un-ordered on purpose: an event
         edge between two graph launches costs 0.2 ms per step (measured, tools/ab3.sh), and consecutive steps are ordered by
-        the stream itself.  Work on other streams that touches the latent goes through set_latent() / synchronize()."""
+        the stream itself.  Work on other streams that touches the latent goes through set_latent() / synchronize().
+        After a ``set_adapters`` that changed a weight of a compiled model, ``set_latent`` must come first (UnsupportedSamplerConfig otherwise)."""
         if getattr(self, "_sched", None) is not None:
             raise UnsupportedSamplerConfig("StableDiffusion.step: this model was compiled with a sampler schedule -- drive it with start() / run() / step_sampler()")
+        self._require_started("step")
         sp = self._params
         with use_stream(self._stream, ordered=False):
             if getattr(self, "_emb_cur", None) is not None:
@@ -485,6 +496,11 @@ class StableDiffusion:
         return self._emb_row(float(timestep), key)     # (computed on this stream the first time a timestep is seen)
 
     # -- sampler schedules (compile(..., sampler=Schedule)) -----------------------------------------------------------------------
+    def _require_started(self, what):
+        if getattr(self, "_needs_start", False):
+            raise UnsupportedSamplerConfig(f"StableDiffusion.{what}: set_adapters captured the step again and the previous start's state (latent, mask, "
+                                           "conditioning, hint, cursor) did not survive -- call start() (or set_latent(), for the DDIM step) first")
+
     def _require_sampler(self, what):
         if getattr(self, "_sched", None) is None:
             raise UnsupportedSamplerConfig(f"StableDiffusion.{what}: compile(..., sampler=<Schedule>) first (this model runs the DDIM step())")
@@ -606,6 +622,7 @@ class StableDiffusion:
         if inpaint and init is None:
             raise ValueError("StableDiffusion.start: an inpainting model starts from init_image= or init_latent=")
         self._seed, self._image_offset, self._cursor = _seed_words(0 if seed is None else seed), int(image_offset), 0
+        self._needs_start = False
         if init is None:
             if noise is not None:
                 return self.set_latent(noise)
@@ -753,6 +770,7 @@ class StableDiffusion:
         """Step i of the compiled schedule (asynchronous, on the sampler stream): one parameter launch (timestep scalars, schedule row, seed and
         -- hoisted -- the cached time-embedding row) and one graph replay, the same launches as ``step``."""
         sched = self._require_sampler("step_sampler")
+        self._require_started("step_sampler")
         n = len(sched.timesteps)
         i = int(i)
         if not 0 <= i < n:
@@ -775,6 +793,7 @@ class StableDiffusion:
     def run(self, guidance, eager=False):
         """Every remaining step of the schedule (all of them after ``start``); returns the latent (asynchronous: synchronize() to read it)."""
         sched = self._require_sampler("run")
+        self._require_started("run")
         for i in range(self._cursor, len(sched.timesteps)):
             self.step_sampler(i, guidance, eager=eager)
         return self._latent
@@ -836,3 +855,71 @@ class StableDiffusion:
 
     def synchronize(self):
         self._stream.synchronize()
+
+    # -- LoRA adapters (storage/lora.py) ---------------------------------------------------------------------------------------------------------
+    def load_lora(self, src, name=None, strict=True):
+        """Read a LoRA adapter -- a path (.safetensors, torch-zip .ckpt / .pt) or a dict of arrays, kohya or PEFT / diffusers keys (storage/lora.py) --
+        check every tensor against this model's targets (ValueError naming the key; nothing is uploaded before all of it passed) and upload its
+        operands in the step's 16-bit type (config.is_bf16(); an fp32 file is ROUNDED to it).  Nothing is merged yet: ``set_adapters`` does that.
+        ``name``: the adapter's name (default: the file's base name, or "lora<n>").  Keys that match no target raise, or with strict=False print
+        ``skipped: <key>``; a model without a text encoder has no ``lora_te_*`` targets.  Returns the name."""
+        import os
+        from ..storage import lora as L
+        reg = self._lora if self._lora is not None else L.LoraRegistry()
+        if name is None:
+            name = os.path.splitext(os.path.basename(str(src)))[0] if not isinstance(src, dict) else f"lora{len(reg.loaded)}"
+        if name in reg.loaded:
+            raise ValueError(f"StableDiffusion.load_lora: an adapter named {name!r} is loaded already (unload_lora it first, or pass name=)")
+        mods, other = L.parse_lora(src)
+        shapes = {k: L.weight_shape(m) for k, m in L.lora_targets(self).items()}
+        weights = L.check_lora(mods, other, shapes, strict=strict, bf16=config.is_bf16(), has_text_encoder=self.cond_stage_model is not None)
+        reg.loaded[name] = L.upload(weights, config.is_bf16())
+        self._lora = reg
+        return name
+
+    def set_adapters(self, names, weights=1.0, text_encoder_weights=None):
+        """Activate the loaded adapters ``names`` (a list; empty: none) at ``weights`` (one float, or one per name; ``text_encoder_weights`` likewise for
+        the ``lora_te_*`` targets, default: the UNet weight).  Every module an adapter with a non-zero weight touches gets a fresh weight
+        W' = round16(W + sum_i s_i up_i down_i), s_i = weight_i alpha_i / rank_i (float64, rounded to fp32 once), by one tf_lora_merge_16 launch from
+        the kept BASE weight -- at most 8 adapters per module; a module no active adapter touches gets its base handle, the same object, back:
+        ``set_adapters([])`` restores the model bit for bit.  A weight installed by update_state in between becomes the new base.
+
+        A compiled model captures its step again: the sampler stream is drained and ``compile`` -- which destroys the old graph before it captures the
+        new one -- is called with the arguments it was given, before any replaced buffer is released.  The previous ``start``'s state (latent, mask, conditioning, hint, cursor) does not
+        survive: ``step_sampler`` / ``run`` / ``step`` raise UnsupportedSamplerConfig until ``start`` (or ``set_latent``, for the DDIM ``step``)
+        has been called again.  A model that was never compiled only swaps handles.  Contexts encoded before a text-encoder adapter changed are
+        not re-encoded: encode the prompts again and hand them to ``set_context``."""
+        from ..storage import lora as L
+        if isinstance(names, str):
+            raise TypeError("StableDiffusion.set_adapters: names is a list of adapter names")
+        reg = self._lora if self._lora is not None else L.LoraRegistry()
+        plan, active = L.plan_adapters(reg.loaded, names, weights, text_encoder_weights)
+        compiled = getattr(self, "_graph", None) is not None and getattr(self, "_compile_args", None) is not None
+        if compiled:
+            self.synchronize()
+        hip.tf_stream_sync(_sh())
+        changed, retired = reg.apply(plan, L.lora_targets(self), L.merge_device)
+        reg.active = active
+        self._lora = reg
+        if changed:
+            hip.tf_stream_sync(_sh())                                    # the merges have run: the adapters' and the retired buffers may go
+            if compiled:
+                # compile destroys the previous graph itself, behind its warm-up steps: the arrays the old capture left referenced (_keep) are
+                # let go while the graph still owns their blocks, and only then do the blocks go back to the pool -- once
+                self.compile(stream=self._stream, **self._compile_args)
+                self._needs_start = True
+        del retired
+        return self
+
+    def adapters(self):
+        """{name: (weight, text_encoder_weight)} of the adapters now merged in (set_adapters' order)."""
+        return dict(self._lora.active) if self._lora is not None else {}
+
+    def unload_lora(self, name):
+        """Forget a loaded adapter and release its device buffers; an adapter that is active (``adapters()``) is refused -- set_adapters without it first."""
+        reg = self._lora
+        if reg is None or name not in reg.loaded:
+            raise ValueError(f"StableDiffusion.unload_lora: unknown adapter {name!r}")
+        if name in reg.active:
+            raise ValueError(f"StableDiffusion.unload_lora: {name!r} is active -- set_adapters([...]) without it first")
+        del reg.loaded[name]

@@ -12,6 +12,10 @@ image (upload, VAE encoder, conditioning buffer).
 --control adds the controlled DPM++2M step (compile(..., control=True): the same UNet weights plus a synthetic SD-1.5 ControlNet) to the
 alternation, the time of start(control_image=...) for a 512^2 hint (upload, x / 255, the hint stem), and k_control_add's achieved GB/s on the
 13 skip shapes of the step next to tf_add_16 on the same byte count.
+--lora adds, for a synthetic adapter of rank 16 and of rank 128 over the 192 UNet attention / FF / proj targets plus the 72 text-encoder targets:
+lora_merge_ms (one set_adapters on an uncompiled model, every launch, wall clock incl. the final sync), lora_merge_gb_s (base read + dst write
+over the launches' device time) next to add_16_gb_s, lora_recapture_ms (set_adapters on a compiled model minus the merge), lora_step_over_plain
+(the adapted DPM++2M step against the plain one) and host_merge_ms (the same merge in numpy float32 plus the upload).  No target is set for any.
 Prints one JSON line."""
 import argparse
 import contextlib
@@ -61,6 +65,116 @@ def control_add_bench(T, hip, model, timed, args):
             "add_16_us": round(1e3 * d, 2), "add_16_gb_s": round(nbytes / d / 1e6, 1)}
 
 
+def synthetic_lora(targets, rank, seed):
+    """A kohya-format adapter over ``targets`` ({kohya name: module}): up, down ~ N(0, 1) in fp16, alpha such that alpha / rank = 0.05 / sqrt(Kd rank)
+    (about 5 % of a synthetic weight's norm: the sampler stays finite)."""
+    from tinyfusers_amd.storage.lora import weight_shape
+    rng = np.random.default_rng(seed)
+    out = {}
+    for k, m in targets.items():
+        shape = weight_shape(m)
+        kd = int(np.prod(shape[1:]))
+        out[k + ".lora_up.weight"] = rng.standard_normal((shape[0], rank) + ((1, 1) if len(shape) == 4 else ()), dtype=np.float32).astype(np.float16)
+        out[k + ".lora_down.weight"] = rng.standard_normal((rank,) + shape[1:], dtype=np.float32).astype(np.float16)
+        out[k + ".alpha"] = np.asarray(0.05 * rank / np.sqrt(kd * rank), np.float32)
+    return out
+
+
+def lora_bench(T, hip, timed, args, state, donor, unc, ctx, noise, sched, plain_m, plain_replays, lat0):
+    """The figures of --lora (see the module docstring) for rank 16 and rank 128.  donor: the model whose text encoder holds weights."""
+    from tinyfusers_amd.storage import lora as L
+    from tinyfusers_amd.storage.state import update_state
+    from tinyfusers_amd.variants.sd import StableDiffusion
+    attn = ("_proj_in", "_proj_out", "_to_q", "_to_k", "_to_v", "_to_out_0", "_ff_net_0_proj", "_ff_net_2")
+
+    def model():
+        m = StableDiffusion()
+        update_state(m.model.diffusion_model, state, "")
+        m.cond_stage_model = donor.cond_stage_model
+        return m
+    eager_m, graph_m = model(), model()
+    targets = {k: t for k, t in L.lora_targets(eager_m).items() if k.startswith("lora_te_") or ("_attentions_" in k and k.endswith(attn))}
+    assert len(targets) == 264, len(targets)
+    elems = sum(t.weight.size for t in targets.values())
+    lat = graph_m.latent_from_numpy(noise)
+    graph_m.compile(unc, ctx, lat, sampler=sched)
+
+    def adapted_replays(n):
+        k = len(sched.timesteps)
+        for s in range(n):
+            i = s % k
+            if i == 0:
+                hip.tf_memcpy_async(lat.ptr, lat0.ptr, lat.nbytes, 3, graph_m._stream.handle)
+            graph_m.step_sampler(i, 7.5)
+
+    n_add = min(elems, 1 << 26)
+    a, b, y = (T.DeviceArray.zeros((n_add,), np.float16, "row") for _ in range(3))
+    hip.tf_stream_sync(None)
+
+    def add(n):
+        for _ in range(n):
+            hip.tf_add_16(0, y.ptr, a.ptr, b.ptr, n_add, plain_m._stream.handle)
+    add(10)
+    add_ms = float(np.median([timed(plain_m, add, args.replays) for _ in range(args.rounds)]))
+    out = {"lora_targets": len(targets), "lora_weight_elems": elems, "add_16_gb_s": round(3 * 2 * n_add / add_ms / 1e6, 1)}
+    ev0, ev1, ms, host = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_float(), {}
+    hip.tf_event_create(ctypes.byref(ev0)); hip.tf_event_create(ctypes.byref(ev1))
+    for rank in (16, 128):
+        ad = synthetic_lora(targets, rank, rank)
+        name = f"r{rank}"
+        eager_m.load_lora(ad, name); graph_m.load_lora(ad, name)
+        wall, dev = [], []
+        for r in range(args.rounds + 1):
+            hip.tf_stream_sync(None)
+            t0 = time.perf_counter()
+            hip.tf_event_record(ev0, None)
+            eager_m.set_adapters([name])
+            hip.tf_event_record(ev1, None)
+            hip.tf_stream_sync(None)
+            wall.append(1e3 * (time.perf_counter() - t0))
+            hip.tf_event_elapsed_ms(ctypes.byref(ms), ev0, ev1)
+            dev.append(ms.value)
+            eager_m.set_adapters([])
+        merge_ms, dev_ms = float(np.median(wall[1:])), float(np.median(dev[1:]))
+        recap = []
+        for r in range(3):
+            t0 = time.perf_counter()
+            graph_m.set_adapters([name])
+            graph_m.synchronize()
+            recap.append(1e3 * (time.perf_counter() - t0))
+            if r < 2:
+                graph_m.set_adapters([])
+        graph_m.start(seed=1234)
+        adapted_replays(20); plain_replays(20)
+        step = {"plain": [], "lora": []}
+        for _ in range(args.rounds):
+            step["plain"].append(timed(plain_m, plain_replays, args.replays))
+            step["lora"].append(timed(graph_m, adapted_replays, args.replays))
+        assert np.isfinite(lat.numpy()).all()
+        graph_m.set_adapters([])
+        # the same merge on the host: numpy float32, one rounding to fp16, one upload per module
+        if not host:
+            host.update({k: t.weight.numpy().reshape(t.weight.shape[0], -1) for k, t in targets.items()})      # (Linear and 1x1 conv weights: (N, Kd) as stored)
+        keep = []
+        t0 = time.perf_counter()
+        for k in targets:
+            w = host[k]
+            up = ad[k + ".lora_up.weight"].reshape(w.shape[0], rank).astype(np.float32)
+            dn = ad[k + ".lora_down.weight"].reshape(rank, -1).astype(np.float32)
+            s = np.float32(float(ad[k + ".alpha"]) / rank)
+            keep.append(T.DeviceArray.from_numpy((w + s * (up @ dn)).astype(np.float16), np.float16, "row"))
+        hip.tf_stream_sync(None)
+        host_ms = 1e3 * (time.perf_counter() - t0)
+        del keep
+        eager_m.unload_lora(name); graph_m.unload_lora(name)
+        p, l = float(np.median(step["plain"])), float(np.median(step["lora"]))
+        out[f"rank{rank}"] = {"lora_merge_ms": round(merge_ms, 3), "lora_merge_device_ms": round(dev_ms, 3), "lora_merge_gb_s": round(2 * 2 * elems / dev_ms / 1e6, 1),
+                              "lora_recapture_ms": round(float(np.median(recap)) - merge_ms, 2), "lora_step_ms": round(l, 4), "plain_step_ms": round(p, 4),
+                              "lora_step_over_plain": round(l / p, 4), "host_merge_ms": round(host_ms, 1)}
+    hip.tf_event_destroy(ev0); hip.tf_event_destroy(ev1)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--replays", type=int, default=100)
@@ -70,6 +184,7 @@ def main():
     ap.add_argument("--inpaint", action="store_true", help="also time the masked step against the unmasked one, and the VAE encoder")
     ap.add_argument("--concat", choices=["inpaint", "edit"], default=None, help="also time the step of the 9-channel inpainting / 8-channel edit UNet against the plain one")
     ap.add_argument("--control", action="store_true", help="also time the ControlNet-conditioned step against the plain one, start(control_image=), and k_control_add")
+    ap.add_argument("--lora", action="store_true", help="also time the LoRA merge (tf_lora_merge_16), the re-capture and the adapted step, for rank 16 and rank 128")
     args = ap.parse_args()
 
     import torch  # noqa: F401  (the weight arena is a torch allocation)
@@ -241,6 +356,9 @@ def main():
             st.append(time.perf_counter() - t0)                          # (includes the 0.75 MB host -> device upload of the hint)
         extra.update({"dpmpp2m_control_step_ms": round(med["dpmpp2m_control"], 4), "control_over_plain": round(med["dpmpp2m_control"] / med["dpmpp2m"], 4),
                       "start_control_image_512_ms": round(1e3 * float(np.median(st[1:])), 3), **control_add_bench(T, hip, ctl_m, timed, args)})
+
+    if args.lora:
+        extra.update(lora_bench(T, hip, timed, args, state, ddim_m, unc, ctx, noise, dpm_sched, dpm_m, dpm_replays, lat0))
 
     def e2e(model, steps, sample):
         recs = []
