@@ -313,6 +313,11 @@ int tf_sdpa_f16(void* o, const void* q, const void* k, const void* v, int B, int
                 long long q_sb, long long q_sh, long long q_st, long long k_sb, long long k_sh, long long k_st,
                 long long v_sb, long long v_sh, long long v_st, long long o_sb, long long o_sh, long long o_st,
                 int causal, tfStream_t s);
+/* test / tuning hook: key slices inside the attention block (two slices of the key tiles per query group, merged through LDS in slice order; d = 40 / 80,
+ * no causal mask).  ks = 0: per-shape choice (where the unsplit grid leaves the SIMDs short of waves), 1: never, 2: wherever a split kernel exists
+ * (other launches stay unsplit).  tf_sdpa_split_ks: the number of slices (1 or 2) a tf_sdpa_f16 launch of that shape takes under the current setting. */
+int tf_sdpa_force_split(int ks);
+int tf_sdpa_split_ks(int B, int NH, int Tq, int Tk, int HS, int causal);
 /* row softmax over (N, C) fp32 -- Device.softmax (storage/device.py:129-157; softmax_func.cu:22-113) */
 int tf_softmax_rows_f32(void* out, const void* inp, int N, int C, tfStream_t s);
 /* softmax step of the UNFUSED attention (attention/sdpa.py:63-75 as the reference runs it: scale * matmul, + mask (:67-68: bool ->

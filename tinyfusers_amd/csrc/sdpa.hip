@@ -17,6 +17,9 @@
 //                                                     tile with ds_read_b64_tr_b16.
 #include "common.h"
 #include "../../include/tinyfusers_hip.h"
+#ifndef TF_TU_SPLIT
+#define TF_TU_SPLIT 0      // 1: the key-slice instances only (sdpa_split.hip / sdpa_split_bf16.hip), so that this unit's code objects stay what they were
+#endif
 
 struct SdpaP {
   const half_t* q; const half_t* k; const half_t* v; half_t* o;
@@ -333,237 +336,59 @@ struct SdpaDma {
 
 // NW = waves per block (4, or 8 for long sequences: twice the queries per fetched K/V tile -- the tile fetch, not the barrier, is what the
 // ablation prices at 19 % of the d = 40 loop at 9216 tokens -- and four waves per SIMD instead of three at two blocks per CU)
+//
+// KS > 1 (k_sdpa_split, sdpa_split.hip): key slices inside the block, for grids that leave the SIMDs short of waves when every (batch, head, query) is
+// already spent.  The NW waves are NQ = NW / KS query groups x KS slices; slice s walks the contiguous key tiles [s TPS, (s + 1) TPS), TPS =
+// ceil(ntiles / KS) (the last slice shorter or empty), through a ring of its own (SR stages, staged by its own NQ waves), with its own online softmax
+// ("first tile adopts its maximum" per slice).  EVERY wave runs TPS loop iterations and executes the s_barrier of each: a slice that has run out of
+// tiles has nothing in flight (vmcnt(0) is immediate), issues nothing and skips the work behind the barrier, never the barrier.  After the loop the
+// rings are dead: the slices >= 1 leave their unnormalised O^T, row sums and reference maxima in that LDS and the slice-0 waves fold them in in slice
+// order, O = sum_s O_s 2^(m_s - M), M = max m_s over the slices that saw a tile (an empty slice contributes nothing; a weight that underflows to 0 is
+// what it should be) -- no atomics, no traffic between blocks, the same sum in the same order on every run.
+// The body is one text, sdpa_dma_body.inc, #included into both __global__ functions below.
+
+// the split forms the launcher knows (tf_sdpa_f16 picks; sdpa_split.hip / sdpa_split_bf16.hip hold the kernels): k_sdpa_split<HS, QT, NW, KS, SR>.
+// Measured and NOT kept (profiles/r06_sdpa_split.txt): <40, 2, 8, 2, 3> (4 x 2 waves, 128 queries per block, two blocks per CU: 84-85 us
+// against the unsplit 82 -- half the queries per fetched tile) and <80, 2, 8, 2, 3> (32-query waves: 128 blocks, half the CUs; 20.2 us against 17.2).
+enum { SDPA_SPLIT_40_W16 = 1,    // <40, 2, 16, 2, 4>: 8 query waves x 2 slices, 256 queries per block, one block per CU (104 KiB): four waves per SIMD
+       SDPA_SPLIT_80_Q16 = 2 };  // <80, 1, 8, 2, 3>: 16-query waves, 4 x 2, 64 queries per block (126 KiB): two waves per SIMD
+int tfk_sdpa_split(const SdpaP& p, int form, hipStream_t st);
+int tfk_sdpa_split_bf16(const SdpaP& p, int form, hipStream_t st);
+
+#if TF_TU_SPLIT
+template <int HS, int QT, int NW, int KS, int SR, bool BF>
+__global__ void __launch_bounds__(NW * 64) k_sdpa_split(const SdpaP p) {
+  constexpr int DBG = 0;
+#include "sdpa_dma_body.inc"
+}
+
+template <int HS, int QT, int NW, int KS, int SR>
+static int launch_sdpa_split(const SdpaP& p, hipStream_t st) {
+  constexpr int smem = KS * SR * SdpaDma<HS>::STAGE_B;
+  static_assert(smem <= 160 * 1024, "the rings must fit the CU's LDS");
+  constexpr int QB = 16 * (NW / KS) * QT;
+  static bool attr_set = false;
+  if (!attr_set) {
+    TF_HIP(hipFuncSetAttribute((const void*)k_sdpa_split<HS, QT, NW, KS, SR, kBF>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+    attr_set = true;
+  }
+  hipLaunchKernelGGL((k_sdpa_split<HS, QT, NW, KS, SR, kBF>), dim3((unsigned)((p.Tq + QB - 1) / QB * p.NH * p.B)), dim3(NW * 64), smem, st, p);
+  TF_LAUNCH_CHECK();
+  return TF_OK;
+}
+
+int TFK(tfk_sdpa_split)(const SdpaP& p, int form, hipStream_t st) {
+  if (form == SDPA_SPLIT_40_W16) return launch_sdpa_split<40, 2, 16, 2, 4>(p, st);
+  if (form == SDPA_SPLIT_80_Q16) return launch_sdpa_split<80, 1, 8, 2, 3>(p, st);
+  tf_set_error("tf_sdpa: no split kernel of form %d", form);
+  return TF_E_UNSUPPORTED;
+}
+#else   // !TF_TU_SPLIT: everything below is the unsplit units' (sdpa.hip, sdpa_bf16.hip)
+
 template <int HS, int QT, int DBG = 0, int NW = 4, bool BF = false>        // DBG: compile-time ablation mask (tools/sdpa_dbg.py; bits as SdpaP::dbg); BF: bfloat16 q / k / v / o (sdpa_bf16.hip)
 __global__ void __launch_bounds__(NW * 64) k_sdpa_dma(const SdpaP p) {
-  static_assert(!(BF && DBG), "the ablation instances are fp16");
-  constexpr int QW = 16 * QT, QB = NW * QW, NT = NW * 64;   // queries per wave / per block, threads
-  using C = SdpaDma<HS>;
-  constexpr int NKS = C::NKS, NDT = C::NDT, CK = C::CK, KPC = C::KPC, VPC = C::VPC, KP = C::KP, VP = C::VP, VSK = C::VSK, VGC = C::VGC;
-  constexpr int STAGE_B = C::STAGE_B, NI = C::NI, LPW = (C::NI + NW - 1) / NW;
-  constexpr int S = sdpa_ring(STAGE_B, NW, C::S);
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-
-  const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int lr = lane & 15, lg = lane >> 4;
-  const SdpaBlk blk = sdpa_block(p, QB);
-  const int b = blk.b, h = blk.h;
-  const int qblk = blk.qb * QB + wid * QW;
-  const half_t* qb = p.q + b * p.q_sb + h * p.q_sh;
-  const half_t* kb = p.k + b * p.k_sb + h * p.k_sh;
-  const half_t* vb = p.v + b * p.v_sb + h * p.v_sh;
-
-  typedef unsigned u4 __attribute__((ext_vector_type(4)));
-  for (int i = tid; i < S * STAGE_B / 16; i += NT) reinterpret_cast<u4*>(smem_raw)[i] = (u4){0, 0, 0, 0};
-  constexpr bool HAS_PAD = C::HAS_PAD;
-  if constexpr (HAS_PAD) {
-    __syncthreads();                     // ones column of V (column HS of every key row, every ring stage): written once
-    for (int i = tid; i < S * 64; i += NT) {
-      int st_ = i >> 6, R = i & 63;
-      reinterpret_cast<half_t*>(smem_raw + st_ * STAGE_B + C::K_BYTES)[(R >> 3) * VGC * 8 + (R & 7) * VP + HS] = f2e<BF>(1.0f);
-    }
-  }
-
-  h8 qf[QT][NKS];
-#pragma unroll
-  for (int qt = 0; qt < QT; ++qt) {
-    int qi = qblk + qt * 16 + lr;
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-      int d0 = ks * 32 + lg * 8;
-      h8 qv = (qi < p.Tq && d0 < HS) ? *reinterpret_cast<const h8*>(qb + qi * p.q_st + d0) : (h8){0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-      for (int j = 0; j < 8; ++j) qv[j] = f2e<BF>(e2f<BF>(qv[j]) * p.scale_log2e);
-      qf[qt][ks] = qv;
-    }
-  }
-
-  int ntiles = (p.Tk + 63) / 64;
-  if (p.causal) {
-    int last_q = min(p.Tq, blk.qb * QB + QB) - 1;
-    ntiles = min(ntiles, last_q / 64 + 1);
-  }
-
-  // this wave's 1-KiB pieces of a tile: piece j = wid + 4 i (clamped: the spare slots of the last round repeat piece
-  // NI-1, same bytes to the same place); j < KPC -> K image, else V image
-  const i4v rs_k = sdpa_rsrc(kb, (unsigned)(((long long)(p.Tk - 1) * p.k_st + HS) * 2));
-  const i4v rs_v = sdpa_rsrc(vb, (unsigned)(((long long)(p.Tk - 1) * p.v_st + HS) * 2));
-  unsigned voff[LPW];
-  const unsigned k_adv = 64u * (unsigned)p.k_st * 2u, v_adv = 64u * (unsigned)p.v_st * 2u;
-#pragma unroll
-  for (int i = 0; i < LPW; ++i) {
-    int j = min(wid + NW * i, NI - 1);
-    if (j < KPC) {
-      int x = 64 * j + lane, r = x / KPC, cc = x - r * KPC;
-      int kt = r >> 4, rr = r & 15;
-      int key = 32 * (kt >> 1) + 8 * (rr >> 2) + 4 * (kt & 1) + (rr & 3);
-      voff[i] = cc < CK ? (unsigned)(key * (int)p.k_st + cc * 8) * 2u : 0x80000000u;
-    } else {
-      // V image: groups of 8 rows (VPC chunks each) followed by VSC skew chunks; pad / skew / tail chunks are fetched out of range
-      int x = 64 * (j - KPC) + lane, grp = x / VGC, rem = x - grp * VGC;
-      int rr = rem / VPC, cc = rem - rr * VPC, r = 8 * grp + rr;
-      voff[i] = (rr < 8 && grp < 8 && cc < CK) ? (unsigned)(r * (int)p.v_st + cc * 8) * 2u : 0x80000000u;
-      if (HAS_PAD && rr < 8 && grp < 8 && cc == CK) voff[i] = 0xFFFFFFFFu;     // the preset ones column: this lane stays out of the DMA
-    }
-  }
-  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem_raw;
-  auto issue = [&](int tt) {
-    const unsigned base = lds0 + (unsigned)(tt % S) * STAGE_B;
-#pragma unroll
-    for (int i = 0; i < LPW; ++i) {
-      int j = min(wid + NW * i, NI - 1);
-      if (j < KPC) sdpa_dma16(rs_k, voff[i] + (unsigned)tt * k_adv, base + j * 1024);
-      else if (!HAS_PAD) sdpa_dma16(rs_v, voff[i] + (unsigned)tt * v_adv, base + j * 1024);
-      else if (voff[i] != 0xFFFFFFFFu) sdpa_dma16(rs_v, voff[i] + (unsigned)tt * v_adv, base + j * 1024);   // (EXEC-masked: the skipped lanes write nothing)
-    }
-  };
-
-  f4 ot[NDT][QT], lt[QT];
-#pragma unroll
-  for (int dt = 0; dt < NDT; ++dt) { for (int q_ = 0; q_ < QT; ++q_) ot[dt][q_] = (f4){0, 0, 0, 0}; }
-  for (int q_ = 0; q_ < QT; ++q_) lt[q_] = (f4){0, 0, 0, 0};
-  float m_run[QT];
-  for (int q_ = 0; q_ < QT; ++q_) m_run[q_] = 0.f;
-  const half_t one1 = f2e<BF>(1.f);
-  const h8 ones = {one1, one1, one1, one1, one1, one1, one1, one1};
-
-  __syncthreads();                       // zero fill done (and drained) before the first DMA lands
-#pragma unroll
-  for (int tt = 0; tt < S - 1; ++tt)
-    if (tt < ntiles) issue(tt);
-
-  for (int t = 0; t < ntiles; ++t) {
-    // tile t landed (this wave's pieces), leaving the younger tiles in flight; the barrier extends that to every wave
-    // and tells that all of them are done reading tile t-1, whose slot the next issue refills
-    {
-      int younger = min(S - 2, ntiles - 1 - t);
-      if (younger >= 4 && S >= 6 && 4 * LPW <= 63) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * LPW > 63 ? 63 : 4 * LPW) : "memory");
-      else if (younger >= 3 && S >= 5 && 3 * LPW <= 63) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * LPW > 63 ? 63 : 3 * LPW) : "memory");
-      else if (younger >= 2 && S >= 4) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * LPW > 63 ? 63 : 2 * LPW) : "memory");
-      else if (younger >= 1 && S >= 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPW > 63 ? 63 : LPW) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    if (!(DBG & 8)) __builtin_amdgcn_s_barrier();
-    if (t + S - 1 < ntiles && !(DBG & 16)) issue(t + S - 1);
-
-    const half_t* ks_ = reinterpret_cast<const half_t*>(smem_raw + (t % S) * STAGE_B);
-    const half_t* vs_ = ks_ + C::K_BYTES / 2;
-
-    f4 st[4][QT];
-    f4 init4[QT];
-#pragma unroll
-    for (int q_ = 0; q_ < QT; ++q_) init4[q_] = (f4){-m_run[q_], -m_run[q_], -m_run[q_], -m_run[q_]};
-#pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-#pragma unroll
-      for (int ks = 0; ks < NKS; ++ks) {
-        h8 kf = *reinterpret_cast<const h8*>(ks_ + (16 * kt + lr) * KP + ks * 32 + lg * 8);
-#pragma unroll
-        for (int q_ = 0; q_ < QT; ++q_) {
-          if (DBG & 4) { if (ks == 0) st[kt][q_] = init4[q_] + (f4){(float)kf[0], (float)kf[1], (float)kf[2], (float)kf[3]}; }
-          else st[kt][q_] = mfma16<BF>(kf, qf[q_][ks], ks == 0 ? init4[q_] : st[kt][q_]);
-        }
-      }
-    }
-    const int kbase = t * 64 + 8 * lg;
-    if (t * 64 + 64 > p.Tk || p.causal) {
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          int key = kbase + 32 * (kt >> 1) + 4 * (kt & 1) + e;
-#pragma unroll
-          for (int qt = 0; qt < QT; ++qt) {
-            int qi = qblk + qt * 16 + lr;
-            if (key >= p.Tk || (p.causal && key > qi)) st[kt][qt][e] = -INFINITY;
-          }
-        }
-    }
-    constexpr float RESCALE_THR = 6.0f;
-    float mx[QT];
-#pragma unroll
-    for (int qt = 0; qt < QT; ++qt) {
-      if (DBG & 64) { mx[qt] = st[0][qt][0]; continue; }
-      float m0_ = fmaxf(fmaxf(st[0][qt][0], st[0][qt][1]), fmaxf(st[0][qt][2], st[0][qt][3]));
-#pragma unroll
-      for (int kt = 1; kt < 4; ++kt) {
-        m0_ = fmaxf(fmaxf(m0_, st[kt][qt][0]), st[kt][qt][1]);
-        m0_ = fmaxf(fmaxf(m0_, st[kt][qt][2]), st[kt][qt][3]);
-      }
-      m0_ = max_over_lane_groups(m0_);
-      mx[qt] = m0_;
-    }
-    bool over = false;
-#pragma unroll
-    for (int q_ = 0; q_ < QT; ++q_) over = over || (mx[q_] > RESCALE_THR);
-    if (t == 0 || __any(over)) {
-#pragma unroll
-      for (int qt = 0; qt < QT; ++qt) {
-        float delta = mx[qt] == -INFINITY ? 0.f : (t == 0 ? mx[qt] : fmaxf(mx[qt], 0.f));
-        m_run[qt] += delta;
-        if (t != 0) {
-          float alpha = __builtin_amdgcn_exp2f(-delta);
-#pragma unroll
-          for (int dt = 0; dt < NDT; ++dt) ot[dt][qt] *= alpha;
-          lt[qt] *= alpha;
-        }
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) st[kt][qt][e] -= delta;
-      }
-    }
-    h8 pf[2][QT];
-#pragma unroll
-    for (int qt = 0; qt < QT; ++qt)
-#pragma unroll
-      for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) pf[kt >> 1][qt][(kt & 1) * 4 + e] = (DBG & 1) ? (half_t)st[kt][qt][e] : f2e<BF>(__builtin_amdgcn_exp2f(st[kt][qt][e]));
-    if constexpr (!HAS_PAD) {
-#pragma unroll
-      for (int kc = 0; kc < 2; ++kc) {
-#pragma unroll
-        for (int q_ = 0; q_ < QT; ++q_) lt[q_] = mfma16<BF>(ones, pf[kc][q_], lt[q_]);
-      }
-    }
-#pragma unroll
-    for (int dt = 0; dt < NDT; ++dt) {
-#pragma unroll
-      for (int kc = 0; kc < 2; ++kc) {
-        const half_t* va = vs_ + (32 * kc + 8 * lg + (lr >> 2)) * VP + (4 * kc + lg) * VSK + dt * 16 + 4 * (lr & 3);
-        union { struct { s4v a, b; } s; h8 h; } u;
-        if (DBG & 32) u.h = pf[kc][0];
-        else { u.s.a = lds_tr16(va); u.s.b = lds_tr16(va + 4 * VP); }
-#pragma unroll
-        for (int q_ = 0; q_ < QT; ++q_) {
-          if (DBG & 2) ot[dt][q_] += (f4){(float)u.h[0] * (float)pf[kc][q_][0], (float)u.h[1], (float)u.h[2], (float)pf[kc][q_][7]};
-          else ot[dt][q_] = mfma16<BF>(u.h, pf[kc][q_], ot[dt][q_]);
-        }
-      }
-    }
-  }
-
-  half_t* ob = p.o + b * p.o_sb + h * p.o_sh;
-#pragma unroll
-  for (int qt = 0; qt < QT; ++qt) {
-    // row sum: the ones-MFMA's accumulator, or row HS of O^T (the preset ones column of V): accumulator tile HS / 16, lane group (HS % 16) / 4
-    float l = lt[qt][0];
-    if constexpr (HAS_PAD) l = __shfl(ot[(HS / 16) % NDT][qt][0], lr + 16 * ((HS % 16) / 4), 64);
-    float inv = l > 0.f ? 1.0f / l : 0.f;
-    int qi = qblk + qt * 16 + lr;
-    if (qi < p.Tq) {
-#pragma unroll
-      for (int dt = 0; dt < NDT; ++dt) {
-        int d = dt * 16 + lg * 4;
-        if (d < HS) {
-          h4 o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = f2e<BF>(ot[dt][qt][e] * inv);
-          *reinterpret_cast<h4*>(ob + qi * p.o_st + d) = o;
-        }
-      }
-    }
-  }
+  constexpr int KS = 1, SR = 0;      // no key slices: the kernel as it always was
+#include "sdpa_dma_body.inc"
 }
 
 template <int HS, int QT, int NW = 4>
@@ -617,6 +442,41 @@ static const int g_sdpa_dbg = 0;   // the shipped library ignores TF_SDPA_DBG: i
 #endif
 static int g_sdpa_nw = getenv("TF_SDPA_NW") ? atoi(getenv("TF_SDPA_NW")) : 0;      // A/B: 4 / 8 waves per block where both exist (0 = per-shape choice)
 static int g_sdpa_qt = getenv("TF_SDPA_QT") ? atoi(getenv("TF_SDPA_QT")) : 0;   // debugging: force the register-staged kernel
+static int g_sdpa_ks = getenv("TF_SDPA_KS") ? atoi(getenv("TF_SDPA_KS")) : 0;   // A/B: key slices inside the block: 0 = per-shape choice, 1 = never, 2 = wherever a split form exists
+extern int g_sdpa_force_ks;                                                      // tf_sdpa_force_split (tests): the same three values, in front of TF_SDPA_KS
+
+// Which split form (SDPA_SPLIT_*, 0 = none) a launch takes: from the shape alone, so eager and captured launches of a shape run the same kernel.
+// A form exists for the two SD head sizes whose rings fit twice (d = 40, 80; d = 160: 2 x 2 x 43 KiB does not), never under the causal mask (the
+// slices' tile ranges would depend on the query block).  Chosen when the unsplit grid leaves a SIMD short of four waves AND the split form adds
+// waves to it (d = 40: the eight-wave instance at one block per CU; d = 80: the 16-query instance at one block per CU) AND every slice gets two
+// tiles.  ks = 2 (forced) asks only whether a form exists: other head sizes and causal launches stay unsplit.  The per-shape choice also steps aside
+// when TF_SDPA_NW / TF_SDPA_QT / TF_SDPA_DBG name an unsplit instance.
+static int sdpa_split_form(int B, int NH, int Tq, int Tk, int HS, int causal, bool small) {
+  const int ks = g_sdpa_force_ks ? g_sdpa_force_ks : g_sdpa_ks;
+  if (ks == 1 || causal || !small || g_sdpa_generic || (HS != 40 && HS != 80)) return 0;
+  const int form = HS == 40 ? SDPA_SPLIT_40_W16 : SDPA_SPLIT_80_Q16;
+  if (ks >= 2) return form;
+  if (g_sdpa_nw || g_sdpa_qt || g_sdpa_dbg) return 0;
+  const int ntiles = (Tk + 63) / 64;
+  if (ntiles < 4) return 0;                                                      // two slices of at least two tiles
+  const long long blocks8 = (long long)((Tq + 255) / 256) * NH * B, blocks1 = (long long)((Tq + 63) / 64) * NH * B;
+  // d = 40: the unsplit launch is <40, 2, 8> (blocks8 >= 256); up to 256 blocks it puts 8 waves on a CU, two per SIMD, and 16-wave blocks make that four
+  if (HS == 40) return blocks8 >= 256 && blocks8 * 8 < 4 * 1024 ? form : 0;
+  // d = 80: the unsplit launch is <80, 1> (fewer than 256 blocks of 128 queries) at one block per CU (84 KiB of ring): one wave per SIMD, split two
+  const long long blocks2 = (long long)((Tq + 127) / 128) * NH * B;
+  return blocks2 < 256 && blocks1 <= 256 ? form : 0;
+}
+#if !TF_TU_BF
+int g_sdpa_force_ks = 0;
+extern "C" int tf_sdpa_force_split(int ks) {
+  TF_REQUIRE(ks >= 0 && ks <= 2, "tf_sdpa_force_split: ks=%d (0 = per-shape choice, 1 = unsplit, 2 = two key slices)", ks);
+  g_sdpa_force_ks = ks;
+  return TF_OK;
+}
+extern "C" int tf_sdpa_split_ks(int B, int NH, int Tq, int Tk, int HS, int causal) {
+  return sdpa_split_form(B, NH, Tq, Tk, HS, causal, true) ? 2 : 1;
+}
+#endif
 
 // one body for both element types: this unit's kernels (kBF) behind tf_sdpa_f16 here, behind tfk_sdpa_bf16 in sdpa_bf16.hip (#define TF_TU_BF 1 + #include of this file)
 int tfk_sdpa_bf16(void* o, const void* q, const void* k, const void* v, int B, int NH, int Tq, int Tk, int HS, long long q_sb, long long q_sh, long long q_st, long long k_sb,
@@ -656,6 +516,7 @@ extern "C" int tf_sdpa_f16(
   TfProfScope prof_(TF_PROF_FAM_SDPA, 4.0 * B * NH * (double)Tq * Tk * HS, st);      // (FLOPs = 4 B NH Tq Tk d)
   // K/V offsets inside a (batch, head) slice must fit the 32-bit buffer offsets of the DMA kernels
   const bool small = ((long long)Tk * k_st + HS) * 2 < (1ll << 31) && ((long long)Tk * v_st + HS) * 2 < (1ll << 31);
+  if (const int form = sdpa_split_form(B, NH, Tq, Tk, HS, causal, small)) return TFK(tfk_sdpa_split)(p, form, st);
   if (small && !g_sdpa_generic) {
     // 16 queries per wave (QT = 1) doubles the waves in flight; g_sdpa_qt: 0 = per-shape choice, 1 / 2 forced (TF_SDPA_QT)
     // (measured: 32x32 d80 22.5 -> 19.7 us, 16x16 d160 13.4 -> 10.6 us with 16-query waves; 64x64 d40 93.8 -> 118.7 us: only when
@@ -692,3 +553,4 @@ extern "C" int tf_sdpa_f16(
   if (HS <= 128) return launch_sdpa<128, 144>(p, st);
   return launch_sdpa<160, 176>(p, st);
 }
+#endif   // !TF_TU_SPLIT
