@@ -318,6 +318,18 @@ int tf_sdpa_f16(void* o, const void* q, const void* k, const void* v, int B, int
  * (other launches stay unsplit).  tf_sdpa_split_ks: the number of slices (1 or 2) a tf_sdpa_f16 launch of that shape takes under the current setting. */
 int tf_sdpa_force_split(int ks);
 int tf_sdpa_split_ks(int B, int NH, int Tq, int Tk, int HS, int causal);
+/* which kernel family a tf_sdpa_f16 / tf_sdpa_16 launch of that shape runs (the one fused launch behind attention/sdpa.py:53-77): the launcher's own
+ * rule, host code, no device needed.  A function of the arguments plus tf_sdpa_force_split and the TF_SDPA_* environment switches read at load; k_st /
+ * v_st are the K / V token strides in elements.  Returns a tfSdpaInstance, TF_E_ARG for arguments the launcher rejects, or TF_E_UNSUPPORTED (as the
+ * launch itself does) when the keys or values of one (batch, head) slice span 2 GiB or more: every kernel addresses a slice with 32-bit byte offsets. */
+typedef enum {
+  TF_SDPA_INST_GENERIC = 1,   /* k_sdpa<DQK, DV>: register-staged, any head size */
+  TF_SDPA_INST_DMA16 = 2,     /* k_sdpa_dma<HS, 1>: 16-query waves, 4 waves per block */
+  TF_SDPA_INST_DMA32 = 3,     /* k_sdpa_dma<HS, 2>: 32-query waves, 4 waves per block */
+  TF_SDPA_INST_DMA32_W8 = 4,  /* k_sdpa_dma<40 | 80, 2, 8>: 32-query waves, 8 waves per block */
+  TF_SDPA_INST_SPLIT = 5      /* k_sdpa_split: two key slices inside the block */
+} tfSdpaInstance;
+int tf_sdpa_instance(int dtype, int B, int NH, int Tq, int Tk, int HS, long long k_st, long long v_st, int causal);
 /* row softmax over (N, C) fp32 -- Device.softmax (storage/device.py:129-157; softmax_func.cu:22-113) */
 int tf_softmax_rows_f32(void* out, const void* inp, int N, int C, tfStream_t s);
 /* softmax step of the UNFUSED attention (attention/sdpa.py:63-75 as the reference runs it: scale * matmul, + mask (:67-68: bool ->

@@ -2,7 +2,7 @@
 One fused flash-style launch (tf_sdpa_f16); the (B,NH,Tq,Tk) score matrix never exists."""
 import numpy as np
 
-from ..native import hip
+from ..native import check, hip, lib
 from ..storage.tensor import DeviceArray, _sh, dtag
 
 
@@ -11,6 +11,19 @@ def sdpa_strided(o, q, k, v, B, NH, Tq, Tk, HS, qs, ks, vs, os_, causal=False):
     assert dtag(q.dtype) == dtag(k.dtype) == dtag(v.dtype) == dtag(o.dtype), "sdpa: q / k / v / o must hold the same 16-bit type"
     hip.tf_sdpa_16(dtag(q.dtype), o.ptr, q.ptr, k.ptr, v.ptr, B, NH, Tq, Tk, HS, *qs, *ks, *vs, *os_, 1 if causal else 0, _sh())
     return o
+
+
+SDPA_INSTANCES = {1: "generic", 2: "dma16", 3: "dma32", 4: "dma32_w8", 5: "split"}   # tfSdpaInstance of include/tinyfusers_hip.h
+
+
+def sdpa_instance(dtype, B, NH, Tq, Tk, HS, k_st=None, v_st=None, causal=False):
+    """The kernel family sdpa_strided's launch of that shape runs (tf_sdpa_instance: the launcher's own rule, no device needed); k_st / v_st: the
+    K / V token strides in elements (default: contiguous rows).  A shape the launch would refuse raises as the launch does."""
+    k_st, v_st = HS if k_st is None else k_st, HS if v_st is None else v_st
+    rc = lib.tf_sdpa_instance(dtag(dtype), B, NH, Tq, Tk, HS, k_st, v_st, 1 if causal else 0)
+    if rc not in SDPA_INSTANCES:
+        check(rc, "tf_sdpa_instance")
+    return SDPA_INSTANCES[rc]
 
 
 def _is_causal_mask(m, tq, tk):

@@ -466,6 +466,40 @@ static int sdpa_split_form(int B, int NH, int Tq, int Tk, int HS, int causal, bo
   const long long blocks2 = (long long)((Tq + 127) / 128) * NH * B;
   return blocks2 < 256 && blocks1 <= 256 ? form : 0;
 }
+// Which kernel family a launch runs (TF_SDPA_INST_* of include/tinyfusers_hip.h), from the shape and the K / V token strides alone; 0 = no kernel
+// can run it.  THE rule: tf_sdpa_f16 / tfk_sdpa_bf16 branch on this value and tf_sdpa_instance returns it.  *form: the SDPA_SPLIT_* of a split launch.
+enum { SDPA_INST_NONE = 0 };     // (not one of tfSdpaInstance's values)
+static int sdpa_instance(int B, int NH, int Tq, int Tk, int HS, long long k_st, long long v_st, int causal, int* form) {
+  // K/V offsets inside a (batch, head) slice must fit 32-bit byte offsets: the buffer offsets of the DMA kernels, and k_sdpa's own
+  // (unsigned)(key * k_st + col) * 2u under a 32-bit num_records
+  const bool small = ((long long)Tk * k_st + HS) * 2 < (1ll << 31) && ((long long)Tk * v_st + HS) * 2 < (1ll << 31);
+  *form = 0;
+  if (!small) return SDPA_INST_NONE;
+  if ((*form = sdpa_split_form(B, NH, Tq, Tk, HS, causal, small))) return TF_SDPA_INST_SPLIT;
+  if (g_sdpa_generic || (HS != 40 && HS != 64 && HS != 80 && HS != 128 && HS != 160)) return TF_SDPA_INST_GENERIC;
+  // 16 queries per wave (QT = 1) doubles the waves in flight; g_sdpa_qt: 0 = per-shape choice, 1 / 2 forced (TF_SDPA_QT)
+  // (measured: 32x32 d80 22.5 -> 19.7 us, 16x16 d160 13.4 -> 10.6 us with 16-query waves; 64x64 d40 93.8 -> 118.7 us: only when
+  // the 32-query grid would leave CUs without a block)
+  const long long blocks2 = (long long)((Tq + 127) / 128) * NH * B;
+  const bool narrow = g_sdpa_qt ? g_sdpa_qt == 1 : blocks2 < 256;
+  if (narrow) return TF_SDPA_INST_DMA16;
+  // eight waves per block (256 queries per K/V tile fetch) once that still gives every CU a block (measured: 64 x 64 d40, B 2: 86.9 -> 81.0 us
+  // with ONE eight-wave block per CU; 96 x 96, B 8: 1214 -> 1103 us)
+  const long long blocks8 = (long long)((Tq + 255) / 256) * NH * B;
+  const bool wide8 = g_sdpa_nw ? g_sdpa_nw == 8 : blocks8 >= 256;
+  return wide8 && (HS == 40 || HS == 80) ? TF_SDPA_INST_DMA32_W8 : TF_SDPA_INST_DMA32;
+}
+// the query behind tf_sdpa_instance, in this unit's element type (each unit asks its own copy of the rule: the one its launcher branches on)
+int tfk_sdpa_instance_bf16(int B, int NH, int Tq, int Tk, int HS, long long k_st, long long v_st, int causal);
+int TFK(tfk_sdpa_instance)(int B, int NH, int Tq, int Tk, int HS, long long k_st, long long v_st, int causal) {
+  int form;
+  return sdpa_instance(B, NH, Tq, Tk, HS, k_st, v_st, causal, &form);
+}
+static int sdpa_refuse(const char* who, int Tk, int HS, long long k_st, long long v_st) {
+  tf_set_error("%s: the keys / values of one (batch, head) slice span %lld / %lld bytes (Tk=%d, token strides %lld / %lld elements); every attention kernel "
+               "addresses a slice with 32-bit byte offsets (< 2 GiB)", who, ((long long)Tk * k_st + HS) * 2, ((long long)Tk * v_st + HS) * 2, Tk, k_st, v_st);
+  return TF_E_UNSUPPORTED;
+}
 #if !TF_TU_BF
 int g_sdpa_force_ks = 0;
 extern "C" int tf_sdpa_force_split(int ks) {
@@ -475,6 +509,14 @@ extern "C" int tf_sdpa_force_split(int ks) {
 }
 extern "C" int tf_sdpa_split_ks(int B, int NH, int Tq, int Tk, int HS, int causal) {
   return sdpa_split_form(B, NH, Tq, Tk, HS, causal, true) ? 2 : 1;
+}
+extern "C" int tf_sdpa_instance(int dtype, int B, int NH, int Tq, int Tk, int HS, long long k_st, long long v_st, int causal) {
+  TF_REQUIRE(dtype == TF_DTYPE_F16 || dtype == TF_DTYPE_BF16, "tf_sdpa_instance: dtype=%d (0 = float16, 1 = bfloat16)", dtype);
+  TF_REQUIRE(B >= 1 && NH >= 1 && Tq >= 1 && Tk >= 1, "tf_sdpa_instance: bad sizes B=%d NH=%d Tq=%d Tk=%d", B, NH, Tq, Tk);
+  TF_REQUIRE(HS >= 8 && HS % 8 == 0 && HS <= 160, "tf_sdpa_instance: head size %d must be a multiple of 8 in [8, 160]", HS);
+  TF_REQUIRE(k_st % 8 == 0 && v_st % 8 == 0, "tf_sdpa_instance: k / v strides must be multiples of 8 elements (16-B rows)");
+  const int inst = dtype == TF_DTYPE_BF16 ? tfk_sdpa_instance_bf16(B, NH, Tq, Tk, HS, k_st, v_st, causal) : tfk_sdpa_instance(B, NH, Tq, Tk, HS, k_st, v_st, causal);
+  return inst ? inst : sdpa_refuse("tf_sdpa_instance", Tk, HS, k_st, v_st);
 }
 #endif
 
@@ -512,35 +554,27 @@ extern "C" int tf_sdpa_f16(
   p.scale_log2e = (1.0f / sqrtf((float)HS)) * 1.4426950408889634f;
   p.causal = causal;
   p.dbg = g_sdpa_dbg;
+  // the instance is decided (and a slice no kernel can address refused) before anything touches the device
+  int form;
+  const int inst = sdpa_instance(B, NH, Tq, Tk, HS, k_st, v_st, causal, &form);
+  if (inst == SDPA_INST_NONE) return sdpa_refuse("tf_sdpa_f16", Tk, HS, k_st, v_st);
   hipStream_t st = tf_hs(s);
   TfProfScope prof_(TF_PROF_FAM_SDPA, 4.0 * B * NH * (double)Tq * Tk * HS, st);      // (FLOPs = 4 B NH Tq Tk d)
-  // K/V offsets inside a (batch, head) slice must fit the 32-bit buffer offsets of the DMA kernels
-  const bool small = ((long long)Tk * k_st + HS) * 2 < (1ll << 31) && ((long long)Tk * v_st + HS) * 2 < (1ll << 31);
-  if (const int form = sdpa_split_form(B, NH, Tq, Tk, HS, causal, small)) return TFK(tfk_sdpa_split)(p, form, st);
-  if (small && !g_sdpa_generic) {
-    // 16 queries per wave (QT = 1) doubles the waves in flight; g_sdpa_qt: 0 = per-shape choice, 1 / 2 forced (TF_SDPA_QT)
-    // (measured: 32x32 d80 22.5 -> 19.7 us, 16x16 d160 13.4 -> 10.6 us with 16-query waves; 64x64 d40 93.8 -> 118.7 us: only when
-    // the 32-query grid would leave CUs without a block)
-    const long long blocks2 = (long long)((Tq + 127) / 128) * NH * B;
-    const bool narrow = g_sdpa_qt ? g_sdpa_qt == 1 : blocks2 < 256;
-    if (narrow) {
-      if (HS == 40) return launch_sdpa_dma<40, 1>(p, st);
-      if (HS == 64) return launch_sdpa_dma<64, 1>(p, st);
-      if (HS == 80) return launch_sdpa_dma<80, 1>(p, st);
-      if (HS == 128) return launch_sdpa_dma<128, 1>(p, st);
-      if (HS == 160) return launch_sdpa_dma<160, 1>(p, st);
-    }
-    // eight waves per block (256 queries per K/V tile fetch) once that still gives every CU a block (measured: 64 x 64 d40, B 2: 86.9 -> 81.0 us
-    // with ONE eight-wave block per CU; 96 x 96, B 8: 1214 -> 1103 us)
-    const long long blocks8 = (long long)((Tq + 255) / 256) * NH * B;
-    const bool wide8 = g_sdpa_nw ? g_sdpa_nw == 8 : blocks8 >= 256;
-    if (HS == 40 && wide8) return launch_sdpa_dma<40, 2, 8>(p, st);
-    if (HS == 80 && wide8) return launch_sdpa_dma<80, 2, 8>(p, st);
+  if (inst == TF_SDPA_INST_SPLIT) return TFK(tfk_sdpa_split)(p, form, st);
+  if (inst == TF_SDPA_INST_DMA16) {
+    if (HS == 40) return launch_sdpa_dma<40, 1>(p, st);
+    if (HS == 64) return launch_sdpa_dma<64, 1>(p, st);
+    if (HS == 80) return launch_sdpa_dma<80, 1>(p, st);
+    if (HS == 128) return launch_sdpa_dma<128, 1>(p, st);
+    return launch_sdpa_dma<160, 1>(p, st);
+  }
+  if (inst == TF_SDPA_INST_DMA32_W8) return HS == 40 ? launch_sdpa_dma<40, 2, 8>(p, st) : launch_sdpa_dma<80, 2, 8>(p, st);
+  if (inst == TF_SDPA_INST_DMA32) {
     if (HS == 40) return launch_sdpa_dma<40, 2>(p, st);
     if (HS == 64) return launch_sdpa_dma<64, 2>(p, st);
     if (HS == 80) return launch_sdpa_dma<80, 2>(p, st);
     if (HS == 128) return launch_sdpa_dma<128, 2>(p, st);
-    if (HS == 160) return launch_sdpa_dma<160, 2>(p, st);
+    return launch_sdpa_dma<160, 2>(p, st);
   }
   // (DQK, DV) = (HS rounded up to 32, HS + 1 rounded up to 16): the V tile always has room for the ones column
   if (HS <= 32) return launch_sdpa<32, 48>(p, st);
