@@ -373,6 +373,22 @@ int tf_group_norm_apply_cat_f16(void* y, const void* x, const void* x2, const vo
                                 int silu, tfStream_t s);
 /* LayerNorm over the last dim (ff/layer_norm.py:8-32, :34-49; semantics = F.layer_norm, tests/layer_norm.py:38) */
 int tf_layer_norm_f16(void* y, const void* x, const void* gamma, const void* beta, int rows, int C, float eps, tfStream_t s);
+/* which kernel a tf_layer_norm_f16 / _bf16 / _fp8 / _mx8 launch of (rows, C) runs (the launches behind ff/layer_norm.py:8-49): the launcher's own
+ * rule, host code, no device needed.  Returns a tfLayerNormInstance, or TF_E_ARG for sizes the launcher rejects. */
+typedef enum {
+  TF_LN_INST_LPR64 = 1,       /* k_layer_norm<64>: one wave per row */
+  TF_LN_INST_LPR8 = 2,        /* k_layer_norm<8>: 8 rows per wave */
+  TF_LN_INST_LPR16 = 3,       /* k_layer_norm<16>: 4 rows per wave */
+  TF_LN_INST_LPR32 = 4,       /* k_layer_norm<32>: 2 rows per wave */
+  TF_LN_INST_ANY_WAVE = 5,    /* k_layer_norm_any<true>: any row length, one wave per row */
+  TF_LN_INST_ANY_BLOCK = 6    /* k_layer_norm_any<false>: any row length, one block per row */
+} tfLayerNormInstance;
+int tf_layer_norm_instance(int rows, int C);
+/* the launch geometry of a GroupNorm of (N, HW, C) (the launches behind ff/group_norm.py:3-21), as tf_group_norm_f16 / _bf16 and the apply entries
+ * compute it: *rpb pixel rows per block sweep, the statistics pass in *chunks chunks of *pix_per_chunk pixels per image, the apply pass in
+ * *apply_blocks units of 4 * rpb pixels per image, *nbatch of them to a block (the launch has ceil(apply_blocks / nbatch) blocks per image).
+ * Host code, no device needed; TF_E_ARG for sizes the launchers reject. */
+int tf_group_norm_geometry(int N, int HW, int C, int* rpb, int* chunks, int* pix_per_chunk, int* apply_blocks, int* nbatch);
 
 /* ---- bfloat16 forms ---------------------------------------------------------------------------
  * The reference's op tests run every case in bfloat16 as well as float16 (tests/group_norm.py:12-19 and

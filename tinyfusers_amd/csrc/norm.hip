@@ -386,6 +386,18 @@ static int gn_batches(int ablocks, int N) {
   return nb;
 }
 
+// Which kernel a LayerNorm launch of (rows, C) runs.  THE rule: layer_norm_impl branches on this value and tf_layer_norm_instance returns it.
+// C not a multiple of 8, or beyond what k_layer_norm keeps in registers: a wave per row while the row is short, a block per row beyond.
+// Otherwise few rows: one wave per row (most waves in flight); many rows: several rows per wave (more loads per lane).
+static int ln_instance(int rows, int C) {
+  if (C % 8 != 0 || C > 64 * 8 * LN_MAXV) return C <= 4096 ? TF_LN_INST_ANY_WAVE : TF_LN_INST_ANY_BLOCK;
+  const int cv = C / 8;
+  if (rows < 8192 || cv > 32 * LN_MAXV) return TF_LN_INST_LPR64;
+  if (cv <= 8 * LN_MAXV) return TF_LN_INST_LPR8;
+  if (cv <= 16 * LN_MAXV) return TF_LN_INST_LPR16;
+  return TF_LN_INST_LPR32;
+}
+
 template <typename T>
 static int layer_norm_impl(void* y, const void* x, const void* gamma, const void* beta, int rows, int C, float eps, int out8, tfStream_t s) {
   TF_REQUIRE(y && x && rows >= 0, "tf_layer_norm_f16: null tensor");
@@ -393,24 +405,23 @@ static int layer_norm_impl(void* y, const void* x, const void* gamma, const void
   TF_REQUIRE(C > 0, "tf_layer_norm_f16: C=%d", C);
   if (rows == 0) return TF_OK;
   TfProfScope prof_(TF_PROF_FAM_LAYER_NORM, (double)rows * C * (2.0 + (out8 ? 1.0 : 2.0)), tf_hs(s));
-  if (C % 8 != 0 || C > 64 * 8 * LN_MAXV) {
-    // any row length: a wave per row while the row is short, a block per row beyond
-    if (C <= 4096) hipLaunchKernelGGL((k_layer_norm_any<true, T>), dim3(ceil_div(rows, 4)), dim3(256), 0, tf_hs(s), (T*)y, (const T*)x,
-                                      (const T*)gamma, (const T*)beta, rows, (long long)C, eps);
-    else hipLaunchKernelGGL((k_layer_norm_any<false, T>), dim3(rows), dim3(256), 0, tf_hs(s), (T*)y, (const T*)x, (const T*)gamma,
-                            (const T*)beta, rows, (long long)C, eps);
-    TF_LAUNCH_CHECK();
-    return TF_OK;
-  }
-  int cv = C / 8;
 #define LN_LAUNCH(LPR_)                                                                                                            \
   hipLaunchKernelGGL((k_layer_norm<LPR_, T>), dim3(ceil_div(rows, 4 * (64 / LPR_))), dim3(256), 0, tf_hs(s), (T*)y, (const T*)x, \
                      (const T*)gamma, (const T*)beta, rows, C, eps, out8)
-  // few rows: one wave per row (most waves in flight); many rows: several rows per wave (more loads per lane)
-  if (rows < 8192 || cv > 32 * LN_MAXV) LN_LAUNCH(64);
-  else if (cv <= 8 * LN_MAXV) LN_LAUNCH(8);
-  else if (cv <= 16 * LN_MAXV) LN_LAUNCH(16);
-  else LN_LAUNCH(32);
+  switch (ln_instance(rows, C)) {
+    case TF_LN_INST_ANY_WAVE:
+      hipLaunchKernelGGL((k_layer_norm_any<true, T>), dim3(ceil_div(rows, 4)), dim3(256), 0, tf_hs(s), (T*)y, (const T*)x,
+                         (const T*)gamma, (const T*)beta, rows, (long long)C, eps);
+      break;
+    case TF_LN_INST_ANY_BLOCK:
+      hipLaunchKernelGGL((k_layer_norm_any<false, T>), dim3(rows), dim3(256), 0, tf_hs(s), (T*)y, (const T*)x, (const T*)gamma,
+                         (const T*)beta, rows, (long long)C, eps);
+      break;
+    case TF_LN_INST_LPR64: LN_LAUNCH(64); break;
+    case TF_LN_INST_LPR8: LN_LAUNCH(8); break;
+    case TF_LN_INST_LPR16: LN_LAUNCH(16); break;
+    default: LN_LAUNCH(32); break;
+  }
 #undef LN_LAUNCH
   TF_LAUNCH_CHECK();
   return TF_OK;
@@ -596,6 +607,20 @@ int tf_layer_norm_fp8(void* y8, const void* x, const void* gamma, const void* be
 int tf_layer_norm_mx8(void* y_mx, const void* x, const void* gamma, const void* beta, int rows, int C, float eps, tfStream_t s) {
   TF_REQUIRE(C > 0 && C % 32 == 0 && C <= 64 * 8 * LN_MAXV, "tf_layer_norm_mx8: C=%d must be a multiple of 32 and <= %d", C, 64 * 8 * LN_MAXV);
   return layer_norm_impl<half_t>(y_mx, x, gamma, beta, rows, C, eps, 2, s);
+}
+
+/* the launch forms, for tests that mean to run a given one (host code, no device needed) */
+int tf_layer_norm_instance(int rows, int C) {
+  TF_REQUIRE(rows >= 0 && C > 0, "tf_layer_norm_instance: rows=%d C=%d", rows, C);
+  return ln_instance(rows, C);
+}
+int tf_group_norm_geometry(int N, int HW, int C, int* rpb, int* chunks, int* pix_per_chunk, int* apply_blocks, int* nbatch) {
+  TF_REQUIRE(rpb && chunks && pix_per_chunk && apply_blocks && nbatch, "tf_group_norm_geometry: null out-argument");
+  TF_REQUIRE(N >= 1 && N <= 65535 && HW >= 1 && C > 0 && C % 8 == 0 && C / 8 <= 1024, "tf_group_norm_geometry: N=%d HW=%d C=%d out of range", N, HW, C);
+  int CV, threads, appb;
+  gn_geometry(HW, C, N, &CV, rpb, &threads, chunks, pix_per_chunk, apply_blocks, &appb);
+  *nbatch = gn_batches(*apply_blocks, N);
+  return TF_OK;
 }
 
 }  // extern "C"
