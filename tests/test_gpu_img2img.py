@@ -388,6 +388,29 @@ def test_inpaint_and_mask_arguments_are_checked(tf):
         sd.start(seed=SEED, init_latent=x0, mask=np.ones((2, 64, 64), np.uint8))
 
 
+def test_a_refused_start_changes_nothing_of_the_run_in_progress(tf):
+    """start() checks every argument before it writes: refused in the middle of a schedule it leaves seed, cursor, latent and the inpainting
+    buffers alone, and run() finishes the schedule as if the refused calls had not been made."""
+    from tinyfusers_amd.variants import samplers as S
+    W, ctx, unc, x0 = _tiny()
+    sch = S.DPMSolverPP2M().schedule(4)
+    m = np.zeros((2, 1, 16, 16), np.float32); m[..., :8] = 1.0
+    sd, lat = _model(tf, W, unc, ctx, sch, inpaint=True)
+    sd.start(seed=3, init_latent=x0, mask=m)
+    sd.run(7.5); sd.synchronize()
+    want = lat.numpy().copy()
+    sd.start(seed=3, init_latent=x0, mask=m)
+    sd.step_sampler(0, 7.5)
+    for bad in (dict(init_latent=x0[:1]),                                                       # a wrong shape
+                dict(init_latent=tf.DeviceArray.from_numpy(x0, np.float16, "row")),              # a device array that is not fp32
+                dict(init_latent=x0, mask=np.ones((2, 64, 64), np.uint8)),                       # a mask of another latent size
+                dict(init_image=np.zeros((2, 64, 64, 3), np.uint8))):                            # an image that encodes to (2,4,8,8)
+        with pytest.raises(ValueError):
+            sd.start(seed=SEED, **bad)
+    sd.run(7.5); sd.synchronize()                                 # continues from step 1, with seed 3
+    assert np.array_equal(lat.numpy(), want)
+
+
 # ---- 7. SD-1.5 shapes ------------------------------------------------------------------------------------------------------------------
 def test_sd15_img2img_and_inpainting_at_512(tf):
     import oracle

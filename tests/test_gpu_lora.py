@@ -299,6 +299,17 @@ def test_compile_then_set_adapters_recaptures_and_two_adapters_meet_the_oracle_a
     print(f"merged weights of {len(paths)} modules vs float64: worst err / bound = {worst:.3f} (bound 1)")
 
 
+def test_a_refused_start_after_a_recapture_does_not_count_as_a_start(tf):
+    from tinyfusers_amd.variants.samplers import UnsupportedSamplerConfig
+    sd, lat, _ = _model(tf)
+    sd.start(seed=SEED)
+    sd.set_adapters(["A"])                                                 # re-captured: the start's state is gone
+    with pytest.raises(ValueError, match="shape"):
+        sd.start(seed=SEED, init_latent=np.zeros((1, 4, 16, 16), np.float32))
+    with pytest.raises(UnsupportedSamplerConfig, match="start"):
+        sd.run(G)
+
+
 def test_weights_alone_and_removal_are_exact(tf):
     _, _, a = _merged_then_compiled(tf)
     sd, lat, _ = _model(tf)

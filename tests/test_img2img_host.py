@@ -1,6 +1,7 @@
 """Host checks of image-to-image and inpainting (no GPU): the ``strength`` schedules of Sampler.schedule (a suffix of the full walk with its
 coefficient table rebuilt on the truncated walk), StableDiffusion.latent_mask, the uint8 -> fp16 formula of tf_image_from_u8_f16, and the
-header block of csrc/img2img.hip (test_abi checks that the library exports what the header declares)."""
+header block of csrc/img2img.hip (test_abi checks that the library exports what the header declares), and what a model that was never compiled
+answers."""
 import math
 import os
 import re
@@ -154,3 +155,18 @@ def test_header_declares_the_img2img_entries_with_their_citations():
     names = set(re.findall(r"\b(tf_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", block, flags=re.S)))
     assert {"tf_image_from_u8_f16", "tf_means_to_latent_f32", "tf_noise_to_level_f32", "tf_cfg_sampler_step_masked_f32",
             "tf_cfg_sampler_step_masked_bf16"} <= names
+
+
+# ---- 5. a model that was never compiled -----------------------------------------------------------------------------------------------
+def test_a_model_that_was_never_compiled_names_compile_in_every_refusal():
+    from tinyfusers_amd.variants.samplers import UnsupportedSamplerConfig
+    from tinyfusers_amd.variants.sd import StableDiffusion
+    from tinyfusers_amd.vision.unet import TINY
+    sd = StableDiffusion(TINY)
+    x = np.zeros((1, 4, 8, 8), np.float32)
+    for exc, call in ((RuntimeError, lambda: sd.step(981.0, 0.5, 0.6, 7.5)), (RuntimeError, lambda: sd.set_latent(x)),
+                      (RuntimeError, lambda: sd.set_context(x, x)), (RuntimeError, sd.synchronize),
+                      (UnsupportedSamplerConfig, lambda: sd.start(seed=1)), (UnsupportedSamplerConfig, lambda: sd.run(7.5)),
+                      (UnsupportedSamplerConfig, lambda: sd.step_sampler(0, 7.5))):
+        with pytest.raises(exc, match="compile"):
+            call()

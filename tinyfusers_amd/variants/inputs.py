@@ -1,0 +1,106 @@
+"""Argument checks of the StableDiffusion sampler object (variants/sd.py) that need no model state: each takes what it checks and, for
+the words of its message, the method or argument it serves; each returns the checked value or raises.  The module does not import the
+native library, so nothing here can launch or write -- sd.py's ``compile`` and ``start`` run these first and touch the device afterwards."""
+import numpy as np
+
+from ..storage.tensor import DeviceArray
+from .samplers import Schedule, UnsupportedSamplerConfig
+
+CONCAT_CHANNELS = {"inpaint": 5, "edit": 4}        # conditioning channels behind the 4 latent ones: [mask | masked-image latent], [image latent]
+
+
+def repaint_mask(mask, who, latent_ok=False):
+    """An image-resolution mask (B,H,W) -- bool, uint8 or float; >= 0.5 (uint8: nonzero) means repaint -- as a bool array.  With ``latent_ok`` a
+    float (B,1,h,w) array is a latent mask already and comes back as fp32 (4-D) once its values are checked to lie in [0, 1]."""
+    m = np.asarray(mask)
+    if m.dtype != np.bool_ and m.dtype != np.uint8 and m.dtype.kind != "f":
+        raise TypeError(f"StableDiffusion.{who}: bool, uint8 or float masks, got {m.dtype}")
+    if m.dtype.kind == "f" and not (np.isfinite(m).all() and (m >= 0).all() and (m <= 1).all()):
+        raise ValueError(f"StableDiffusion.{who}: float mask values must lie in [0, 1]")
+    if latent_ok and m.ndim == 4:
+        if m.shape[1] != 1 or m.dtype.kind != "f":
+            raise ValueError(f"StableDiffusion.{who}: a latent-size mask is float (B,1,h,w), got {m.dtype} {m.shape}")
+        return np.ascontiguousarray(m, dtype=np.float32)
+    if m.ndim != 3 or m.shape[0] < 1 or m.shape[1] < 8 or m.shape[2] < 8 or m.shape[1] % 8 or m.shape[2] % 8:
+        raise ValueError(f"StableDiffusion.{who}: takes (B,H,W) with H and W multiples of 8"
+                         + (" (or a float (B,1,h,w) latent mask)" if latent_ok else "") + f", got {m.shape}")
+    return (m != 0) if m.dtype == np.uint8 else (m >= 0.5)
+
+
+def u8_image(image, rule, hw=None, batches=None):
+    """A uint8 (B,H,W,3) image batch, host (comes back contiguous) or device, with -- where given -- the size ``hw`` and a batch in ``batches``:
+    -> (image, its shape), or ValueError(``rule``, got <dtype> <shape>)."""
+    if not isinstance(image, DeviceArray):
+        image = np.ascontiguousarray(image)
+    ish = tuple(int(v) for v in image.shape)
+    if np.dtype(image.dtype) != np.uint8 or len(ish) != 4 or ish[3] != 3 or (hw is not None and ish[1:3] != tuple(hw)) \
+            or (batches is not None and ish[0] not in batches):
+        raise ValueError(f"{rule}, got {np.dtype(image.dtype)} {ish}")
+    return image, ish
+
+
+def fp32_nchw(x, shape, name):
+    """start()'s array arguments that are copied as they are: a device array must be fp32 NCHW of exactly ``shape`` and comes back itself; anything
+    else becomes a contiguous fp32 host array, which must have that shape."""
+    if isinstance(x, DeviceArray):
+        if x.shape != shape or x.dtype != np.float32 or x.layout != "row":
+            raise ValueError(f"StableDiffusion.start: a device {name} must be an fp32 NCHW {shape} array, got {x}")
+        return x
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.shape != shape:
+        raise ValueError(f"StableDiffusion.start: {name} must have the shape {shape}, got {x.shape}")
+    return x
+
+
+def control_scales(control_scale, n_res):
+    """start(control_scale=) -> the 16 fp32 words of the scale buffer (one per residual; 16: whole 4-word writes): all ones when not given."""
+    scales = np.ones((16,), np.float32)
+    if control_scale is not None:
+        sc = np.asarray(control_scale, dtype=np.float32)
+        if sc.ndim > 1 or (sc.ndim == 1 and sc.shape[0] != n_res):
+            raise ValueError(f"StableDiffusion.start: control_scale= takes one float or {n_res} (one per residual), got shape {sc.shape}")
+        if not np.isfinite(sc).all():
+            raise ValueError(f"StableDiffusion.start: control_scale={control_scale}")
+        scales[:n_res] = sc
+    return scales
+
+
+def check_compile(cin, has_control_net, config, latent, sampler, inpaint, concat, control):
+    """compile()'s refusals, before any device work: ``cin`` the UNet's in_channels, ``config`` the package's config module."""
+    def refuse(exc, text):
+        raise exc(f"StableDiffusion.compile: {text}")
+    if concat not in (None, "inpaint", "edit"):
+        refuse(ValueError, f"concat= takes None, 'inpaint' or 'edit', got {concat!r}")
+    if control:
+        if not has_control_net:
+            refuse(ValueError, "control=True needs a ControlNet: attach_control(ControlNet(cfg)) first")
+        if sampler is None:
+            refuse(ValueError, "control=True needs a sampler schedule (sampler=<Schedule>)")
+        if concat is not None:
+            refuse(ValueError, f"control=True and concat={concat!r} together (a ControlNet on a concat-conditioned model) are not supported")
+        if config.cfg_parallel:
+            refuse(UnsupportedSamplerConfig, "a controlled model has no two-chain CFG form (TF_CFG_PARALLEL)")
+        if config.dtype == "fp8":
+            refuse(UnsupportedSamplerConfig, "control=True runs in the fp16 and the bf16 step, not under the fp8 policy (config.set_dtype('fp8'))")
+    if concat is None and cin != 4:
+        refuse(ValueError, f"a UNet with in_channels={cin} is concat-conditioned: pass concat='inpaint' (9 channels) or concat='edit' (8)")
+    if concat is not None:
+        if sampler is None:
+            refuse(ValueError, f"concat={concat!r} needs a sampler schedule (sampler=<Schedule>)")
+        if cin != 4 + CONCAT_CHANNELS[concat]:
+            refuse(ValueError, f"concat={concat!r} needs a UNet with in_channels={4 + CONCAT_CHANNELS[concat]}, this one has {cin}")
+        if inpaint:
+            refuse(ValueError, "concat= and inpaint=True together (the latent blend on top of a concat-conditioned model) are not supported")
+        if config.cfg_parallel:
+            refuse(UnsupportedSamplerConfig, "a concat-conditioned model has no two-chain CFG form (TF_CFG_PARALLEL)")
+        if latent.shape[1] != 4:
+            refuse(ValueError, f"the latent of a concat-conditioned model has 4 channels, got {latent.shape}")
+    if config.is_bf16() and (config.parallel_branches or config.cfg_parallel):
+        refuse(RuntimeError, "the bfloat16 step has no parallel-branch / two-chain CFG form (TF_PARALLEL_BRANCHES / TF_CFG_PARALLEL are fp16-only experiments)")
+    if inpaint and sampler is None:
+        refuse(ValueError, "inpaint=True needs a sampler schedule (sampler=<Schedule>)")
+    if sampler is not None:
+        if not isinstance(sampler, Schedule):
+            refuse(TypeError, "sampler= takes a Schedule (e.g. DPMSolverPP2M().schedule(20))")
+        if config.cfg_parallel:
+            refuse(UnsupportedSamplerConfig, "a sampler schedule has no two-chain CFG form (TF_CFG_PARALLEL is an fp16-only experiment)")

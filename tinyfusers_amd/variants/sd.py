@@ -16,6 +16,12 @@ A ControlNet (vision/controlnet.py; ``attach_control``, ``compile(..., control=T
 runs inside the same captured step: its residuals enter the UNet's skip connections through one launch (tf_control_add_16).
 LoRA adapters (storage/lora.py; ``load_lora``, ``set_adapters``, ``adapters``, ``unload_lora``) are merged on the device into fresh weight buffers
 (tf_lora_merge_16, one launch per touched module, from the kept base weight); a compiled model re-captures its step.
+
+How the object is laid out.  Everything ``compile`` / ``start`` / ``set_context`` / ``set_adapters`` keep on the model is declared, with its
+"not compiled" value, in ``_reset_state``: ``__init__`` runs all of it, ``compile`` the per-compile part, so a re-compile with other flags drops the
+buffers of the modes it no longer uses and nothing probes for a name.  ``compile`` is refuse -> reset / remember -> allocate the mode buffers ->
+hoist -> warm up -> capture; ``start`` checks all three argument groups (control, conditioning, latent) and only then writes; ``step`` and
+``step_sampler`` share ``_advance``.  The argument checks that need no model state live in variants/inputs.py, which cannot reach the device.
 """
 import ctypes
 from collections import namedtuple
@@ -26,7 +32,8 @@ from .. import config
 from ..native import hip
 from ..storage.tensor import Branch, DeviceArray, Stream, _sh, asarray, bfloat16, dtag, pool, use_stream
 from ..vision.unet import SD15, SD15_EDIT, SD15_INPAINT, StepParams, UNetModel
-from .samplers import Schedule, UnsupportedSamplerConfig, get_alphas_cumprod  # noqa: F401  (get_alphas_cumprod: variants/sd.py:61-65, re-exported)
+from . import inputs
+from .samplers import UnsupportedSamplerConfig, get_alphas_cumprod  # noqa: F401  (get_alphas_cumprod: variants/sd.py:61-65, re-exported)
 
 
 def _seed_words(seed):
@@ -35,11 +42,19 @@ def _seed_words(seed):
     return seed & 0xFFFFFFFF, seed >> 32
 
 
-_CONCAT_CHANNELS = {"inpaint": 5, "edit": 4}       # conditioning channels behind the 4 latent ones: [mask | masked-image latent], [image latent]
-
-
 def _scalar(v):
     return float(np.asarray(v.numpy() if isinstance(v, DeviceArray) else v, dtype=np.float32).reshape(-1)[0])
+
+
+def _step_dtype():
+    """The 16-bit type of the step's activations (config.is_bf16())."""
+    return bfloat16 if config.is_bf16() else np.float16
+
+
+def _entry16(stem, other):
+    """The library entry ``<stem>_bf16`` in the bfloat16 step, else ``<stem>_<other>`` (its float16 twin: "f16", or "f32" where the entry is
+    named after the fp32 latent it updates)."""
+    return getattr(hip, f"{stem}_{'bf16' if config.is_bf16() else other}")
 
 
 class StableDiffusion:
@@ -55,9 +70,29 @@ class StableDiffusion:
             self.cond_stage_model = namedtuple("CondStageModel", ["transformer"])(
                 transformer=namedtuple("Transformer", ["text_model"])(text_model=CLIPTextTransformer(init=init)))
         self.control_model = None        # a ControlNet (vision/controlnet.py), under the LDM checkpoint's name: attach_control sets it
-        self._params = None
-        self._graph = None
-        self._lora = None                # storage/lora.py::LoraRegistry, made by the first load_lora
+        self._reset_state(everything=True)
+
+    def _reset_state(self, everything=False):
+        """Every attribute compile / start / set_context / set_adapters keep on the model, at its "not compiled" value.  ``compile`` runs the
+        per-compile part, which lets go of the previous compile's buffers; the graph, its blocks and ``_keep`` are not touched there -- ``_capture``
+        releases them in the order set_adapters relies on -- nor are the parameter block (a DDIM re-compile keeps its own) and the adapters."""
+        if everything:
+            self._params = None                  # StepParams: the 4 step scalars; a sampler's block adds row, seed, image offset
+            self._graph = self._graph_blocks = self._keep = None     # the captured step, the pool blocks it owns, what its nodes reference
+            self._lora = None                    # storage/lora.py::LoraRegistry, made by the first load_lora
+        self._compile_args = None                # compile's arguments (set_adapters captures the step again)
+        self._needs_start = False                # set_adapters re-captured: the previous start's state did not survive
+        self._stream = None                      # the sampler stream; None: never compiled
+        self._latent = self._unc = self._ctx = self._ctx2 = None     # the caller's latent and contexts; the private stacked context
+        self._sched, self._inpaint, self._concat, self._control, self._groups = None, False, None, False, 2      # the mode
+        self._coeffs = self._x0_hist = None      # sampler: coefficient table, fp32 x0 history
+        self._x0_init = self._mask = None        # inpaint=True: the clean latent and the (B,1,h,w) mask
+        self._cond = self._edit = None           # concat=: the conditioning channels; [0] g_I of the three-branch update
+        self._hint_emb = self._control_scales = None                 # control=True
+        self._seed, self._image_offset, self._cursor = (0, 0), 0, 0  # what start() sets, step_sampler advances
+        self._kv_all = self._kv_key = self._ckv_all = self._emb_cur = self._emb_key = self._keep_row = None     # hoisted K|V and time-embedding row
+        self._emb_rows = {}
+        self._ctx_tmp = self._kv_tmp = self._start_keep = self._cond_keep = self._control_keep = None   # referenced until their kernels have run
 
     def attach_control(self, net):
         """Give the model a ControlNet (vision/controlnet.py) built for the UNet's configuration: ``compile(..., control=True)`` then captures
@@ -97,7 +132,7 @@ class StableDiffusion:
         b, c, h, w = latent.shape
         x_prev = DeviceArray.empty(latent.shape, np.float32, "row")
         hip.tf_memcpy_async(x_prev.ptr, latent.ptr, latent.nbytes, 3, _sh())
-        (hip.tf_cfg_ddim_step_bf16 if config.is_bf16() else hip.tf_cfg_ddim_step_f32)(x_prev.ptr, out.ptr, sp.dev.ptr, b, c, h, w, _sh())
+        _entry16("tf_cfg_ddim_step", "f32")(x_prev.ptr, out.ptr, sp.dev.ptr, b, c, h, w, _sh())
         return x_prev
 
     def decode(self, x):
@@ -133,26 +168,32 @@ class StableDiffusion:
         (B,4,H/8,W/8) -- the inverse of decode's 1/0.18215 (variants/sd.py:49).  uint8 -> x/127.5 - 1 (tf_image_from_u8_f16) -> Encoder +
         quant_conv, means only (AutoencoderKL.encode) -> tf_means_to_latent_f32.  Asynchronous, on the current stream."""
         fsm = self._encoder_side("encode_image")
-        if isinstance(images, DeviceArray):
-            dev = images
-        else:
-            images = np.asarray(images)
-            dev = None
-        if np.dtype(images.dtype) != np.uint8 or len(images.shape) != 4 or images.shape[3] != 3:
-            raise ValueError(f"StableDiffusion.encode_image: takes uint8 (B,H,W,3) images, got {np.dtype(images.dtype)} {tuple(images.shape)}")
-        b, h, w, _ = (int(v) for v in images.shape)
+        images, (b, h, w, _) = inputs.u8_image(images, "StableDiffusion.encode_image: takes uint8 (B,H,W,3) images")
         why = self.encoder_size_error(h, w)
         if b < 1 or why:
             raise ValueError(f"StableDiffusion.encode_image: {why or 'an empty batch'}")
-        if dev is None:
-            dev = DeviceArray.from_numpy(np.ascontiguousarray(images), np.uint8, "row")
-        x = DeviceArray.empty((b, 3, h, w), np.float16, "nhwc")          # NHWC: the (B,H,W,3) element order of the uint8 image
-        hip.tf_image_from_u8_f16(x.ptr, dev.ptr, x.size, _sh())
-        means = fsm.encode(x)                                            # (B,4,H/8,W/8) fp16 NHWC
+        means, keep = self._encode_u8(fsm, images)                       # (B,4,H/8,W/8) fp16 NHWC
         x0 = DeviceArray.empty(means.shape, np.float32, "row")
         hip.tf_means_to_latent_f32(x0.ptr, means.ptr, b, means.shape[2], means.shape[3], _sh())
-        x0._base = (dev, x, means)                                       # (referenced until the kernels have run)
+        x0._base = keep                                                  # (referenced until the kernels have run)
         return x0
+
+    @staticmethod
+    def _encode_u8(fsm, image, m8=None):
+        """A checked uint8 (B,H,W,3) image, host or device -> x / 127.5 - 1 in fp16 NHWC (tf_image_from_u8_f16; with ``m8``, a host uint8 (B,H,W)
+        mask, tf_image_from_u8_masked_f16 sets the pixels where it is 1 to 0) -> the means of ``fsm.encode``, on the current stream.  Returns
+        (means, what must stay referenced until the kernels have run)."""
+        dev = image if isinstance(image, DeviceArray) else DeviceArray.from_numpy(image, np.uint8, "row")
+        b, h, w, _ = dev.shape
+        x = DeviceArray.empty((b, 3, h, w), np.float16, "nhwc")          # NHWC: the (B,H,W,3) element order of the uint8 image
+        if m8 is None:
+            dm8 = None
+            hip.tf_image_from_u8_f16(x.ptr, dev.ptr, x.size, _sh())
+        else:
+            dm8 = DeviceArray.from_numpy(m8, np.uint8, "row")
+            hip.tf_image_from_u8_masked_f16(x.ptr, dev.ptr, dm8.ptr, b, h, w, _sh())
+        means = fsm.encode(x)
+        return means, (dev, x, dm8, means)
 
     def _encoder_side(self, who):
         """first_stage_model with a filled encoder, or the RuntimeError ``who`` raises."""
@@ -170,33 +211,17 @@ class StableDiffusion:
         """Host helper: an inpainting mask at image resolution (B,H,W) -- bool, uint8 or float, >= 0.5 (uint8: nonzero) means repaint -- to the
         latent mask (B,1,H/8,W/8) fp32 the masked step reads, by the maximum over each 8x8 block (a latent pixel is repainted when any of its
         image pixels is).  A float (B,1,h,w) array is a latent mask already: it passes through once its values are checked to lie in [0, 1]."""
-        m = np.asarray(mask)
-        if m.dtype != np.bool_ and m.dtype != np.uint8 and m.dtype.kind != "f":
-            raise TypeError(f"StableDiffusion.latent_mask: bool, uint8 or float masks, got {m.dtype}")
-        if m.dtype.kind == "f" and not (np.isfinite(m).all() and (m >= 0).all() and (m <= 1).all()):
-            raise ValueError("StableDiffusion.latent_mask: float mask values must lie in [0, 1]")
-        if m.ndim == 4:
-            if m.shape[1] != 1 or m.dtype.kind != "f":
-                raise ValueError(f"StableDiffusion.latent_mask: a latent-size mask is float (B,1,h,w), got {m.dtype} {m.shape}")
-            return np.ascontiguousarray(m, dtype=np.float32)
-        if m.ndim != 3 or m.shape[0] < 1 or m.shape[1] < 8 or m.shape[2] < 8 or m.shape[1] % 8 or m.shape[2] % 8:
-            raise ValueError(f"StableDiffusion.latent_mask: takes (B,H,W) with H and W multiples of 8 (or a float (B,1,h,w) latent mask), got {m.shape}")
-        b, h, w = m.shape
-        rep = (m != 0) if m.dtype == np.uint8 else (m >= 0.5)
+        rep = inputs.repaint_mask(mask, "latent_mask", latent_ok=True)
+        if rep.ndim == 4:
+            return rep
+        b, h, w = rep.shape
         return rep.reshape(b, 1, h // 8, 8, w // 8, 8).any(axis=(3, 5)).astype(np.float32)
 
     @staticmethod
     def concat_mask_u8(mask):
         """Host helper: an inpainting mask at image resolution (B,H,W) -- bool, uint8 or float, latent_mask's repaint convention (>= 0.5, uint8:
         nonzero) -- binarised to uint8 (B,H,W), 1 = repaint: what tf_image_from_u8_masked_f16 reads to blank the masked image."""
-        m = np.asarray(mask)
-        if m.dtype != np.bool_ and m.dtype != np.uint8 and m.dtype.kind != "f":
-            raise TypeError(f"StableDiffusion.concat_mask: bool, uint8 or float masks, got {m.dtype}")
-        if m.dtype.kind == "f" and not (np.isfinite(m).all() and (m >= 0).all() and (m <= 1).all()):
-            raise ValueError("StableDiffusion.concat_mask: float mask values must lie in [0, 1]")
-        if m.ndim != 3 or m.shape[0] < 1 or m.shape[1] < 8 or m.shape[2] < 8 or m.shape[1] % 8 or m.shape[2] % 8:
-            raise ValueError(f"StableDiffusion.concat_mask: takes (B,H,W) with H and W multiples of 8, got {m.shape}")
-        return np.ascontiguousarray((m != 0) if m.dtype == np.uint8 else (m >= 0.5) if m.dtype.kind == "f" else m, dtype=np.uint8)
+        return np.ascontiguousarray(inputs.repaint_mask(mask, "concat_mask"), dtype=np.uint8)
 
     @staticmethod
     def concat_mask(mask):
@@ -217,8 +242,8 @@ class StableDiffusion:
     def _cfg_duplicate(latent):
         """variants/sd.py:31: the latent for both halves of the CFG pair, in the step's 16-bit type (NHWC)."""
         b, c, h, w = latent.shape
-        x2 = DeviceArray.empty((2 * b, c, h, w), bfloat16 if config.is_bf16() else np.float16, "nhwc")
-        (hip.tf_cfg_duplicate_bf16 if config.is_bf16() else hip.tf_cfg_duplicate_f16)(x2.ptr, latent.ptr, b, c, h, w, _sh())
+        x2 = DeviceArray.empty((2 * b, c, h, w), _step_dtype(), "nhwc")
+        _entry16("tf_cfg_duplicate", "f16")(x2.ptr, latent.ptr, b, c, h, w, _sh())
         return x2
 
     def _cfg_concat(self):
@@ -226,9 +251,8 @@ class StableDiffusion:
         model's first group (bit 0 of drop_bits) reads zeros in place of the conditioning."""
         b, c, h, w = self._latent.shape
         cc = self._cond.shape[1]
-        x = DeviceArray.empty((self._groups * b, c + cc, h, w), bfloat16 if config.is_bf16() else np.float16, "nhwc")
-        (hip.tf_cfg_concat_bf16 if config.is_bf16() else hip.tf_cfg_concat_f16)(
-            x.ptr, self._latent.ptr, self._cond.ptr, b, c, cc, h, w, self._groups, 0b001 if self._concat == "edit" else 0, _sh())
+        x = DeviceArray.empty((self._groups * b, c + cc, h, w), _step_dtype(), "nhwc")
+        _entry16("tf_cfg_concat", "f16")(x.ptr, self._latent.ptr, self._cond.ptr, b, c, cc, h, w, self._groups, 0b001 if self._concat == "edit" else 0, _sh())
         return x
 
     @staticmethod
@@ -252,6 +276,7 @@ class StableDiffusion:
     def set_latent(self, x):
         """Start a new image: host noise (B,4,H,W) -> the latent buffer the compiled step updates in place.  Ordered after
         every step already queued (the sampler stream is drained first)."""
+        self._require_compiled("set_latent")
         self.synchronize()
         self._latent.copy_from_numpy(x)
         self._needs_start = False
@@ -306,204 +331,200 @@ class StableDiffusion:
         (the latent blend lives in the sampler tail); not with ``concat=``, TF_CFG_PARALLEL or the fp8 policy.
 
         The arguments are remembered: ``set_adapters`` (LoRA) on a compiled model swaps weight handles and calls ``compile`` again with the same ones."""
-        cin = self.model.diffusion_model.cfg.in_channels
-        if concat not in (None, "inpaint", "edit"):
-            raise ValueError(f"StableDiffusion.compile: concat= takes None, 'inpaint' or 'edit', got {concat!r}")
-        if control:
-            if self.control_model is None:
-                raise ValueError("StableDiffusion.compile: control=True needs a ControlNet: attach_control(ControlNet(cfg)) first")
-            if sampler is None:
-                raise ValueError("StableDiffusion.compile: control=True needs a sampler schedule (sampler=<Schedule>)")
-            if concat is not None:
-                raise ValueError(f"StableDiffusion.compile: control=True and concat={concat!r} together (a ControlNet on a concat-conditioned model) are not supported")
-            if config.cfg_parallel:
-                raise UnsupportedSamplerConfig("StableDiffusion.compile: a controlled model has no two-chain CFG form (TF_CFG_PARALLEL)")
-            if config.dtype == "fp8":
-                raise UnsupportedSamplerConfig("StableDiffusion.compile: control=True runs in the fp16 and the bf16 step, not under the fp8 policy (config.set_dtype('fp8'))")
-        if concat is None and cin != 4:
-            raise ValueError(f"StableDiffusion.compile: a UNet with in_channels={cin} is concat-conditioned: pass concat='inpaint' (9 channels) or concat='edit' (8)")
-        if concat is not None:
-            if sampler is None:
-                raise ValueError(f"StableDiffusion.compile: concat={concat!r} needs a sampler schedule (sampler=<Schedule>)")
-            if cin != 4 + _CONCAT_CHANNELS[concat]:
-                raise ValueError(f"StableDiffusion.compile: concat={concat!r} needs a UNet with in_channels={4 + _CONCAT_CHANNELS[concat]}, this one has {cin}")
-            if inpaint:
-                raise ValueError("StableDiffusion.compile: concat= and inpaint=True together (the latent blend on top of a concat-conditioned model) are not supported")
-            if config.cfg_parallel:
-                raise UnsupportedSamplerConfig("StableDiffusion.compile: a concat-conditioned model has no two-chain CFG form (TF_CFG_PARALLEL)")
-            if latent.shape[1] != 4:
-                raise ValueError(f"StableDiffusion.compile: the latent of a concat-conditioned model has 4 channels, got {latent.shape}")
-        if config.is_bf16() and (config.parallel_branches or config.cfg_parallel):
-            raise RuntimeError("StableDiffusion.compile: the bfloat16 step has no parallel-branch / two-chain CFG form (TF_PARALLEL_BRANCHES / TF_CFG_PARALLEL are fp16-only experiments)")
-        if inpaint and sampler is None:
-            raise ValueError("StableDiffusion.compile: inpaint=True needs a sampler schedule (sampler=<Schedule>)")
+        inputs.check_compile(self.model.diffusion_model.cfg.in_channels, self.control_model is not None, config, latent, sampler, inpaint, concat, control)
         if sampler is not None:
-            if not isinstance(sampler, Schedule):
-                raise TypeError("StableDiffusion.compile: sampler= takes a Schedule (e.g. DPMSolverPP2M().schedule(20))")
-            if config.cfg_parallel:
-                raise UnsupportedSamplerConfig("StableDiffusion.compile: a sampler schedule has no two-chain CFG form (TF_CFG_PARALLEL is an fp16-only experiment)")
             timesteps = sampler.timesteps
+        self._reset_state()
         self._compile_args = dict(unconditional_context=unconditional_context, context=context, latent=latent, warmup=warmup, timesteps=timesteps,
-                                  sampler=sampler, inpaint=inpaint, concat=concat, control=control)       # (set_adapters captures the step again)
-        self._needs_start = False
+                                  sampler=sampler, inpaint=inpaint, concat=concat, control=control)
         self._stream = stream or Stream()
         self._latent, self._unc, self._ctx = latent, unconditional_context, context
         self._sched, self._inpaint, self._concat, self._control = sampler, bool(inpaint), concat, bool(control)
         self._groups = 3 if concat == "edit" else 2
         if sampler is not None:
             with use_stream(self._stream):
-                self._params = StepParams.__new__(StepParams)          # the sampler block: the 4 step scalars + row, seed, image offset
-                self._params.dev = DeviceArray.zeros((8,), np.float32, "row")
-                self._coeffs = DeviceArray.from_numpy(np.asarray(sampler.coeffs, np.float32), np.float32, "row")
-                self._x0_hist = DeviceArray.zeros(latent.shape, np.float32, "row")
-                if inpaint:
-                    b, _, h, w = latent.shape
-                    self._x0_init = DeviceArray.zeros(latent.shape, np.float32, "row")
-                    self._mask = DeviceArray.from_numpy(np.ones((b, 1, h, w), np.float32), np.float32, "row")
-                if concat is not None:
-                    b, _, h, w = latent.shape
-                    self._cond = DeviceArray.zeros((b, _CONCAT_CHANNELS[concat], h, w), np.float32, "row")
-                    self._edit = DeviceArray.zeros((4,), np.float32, "row")      # [0] g_I, the image guidance of the three-branch update
-                    hip.tf_set_step_params(self._edit.ptr, 1.5, 0.0, 0.0, 0.0, _sh())
-                if control:
-                    b, _, h, w = latent.shape
-                    self._hint_emb = DeviceArray.zeros((self._groups * b, self.control_model.cfg.model_channels, h, w),
-                                                       bfloat16 if config.is_bf16() else np.float16, "nhwc")
-                    self._control_scales = DeviceArray.from_numpy(np.ones((16,), np.float32), np.float32, "row")     # one per residual; 16: whole 4-word writes
-            self._seed, self._image_offset, self._cursor = (0, 0), 0, 0
+                self._alloc_sampler_buffers()
         sp = self._step_params()
-        unet = self.model.diffusion_model
         with use_stream(self._stream):
-            self._ctx2 = self._stack_context(unconditional_context, context, self._groups)
-            self._kv_all, self._kv_key, self._emb_cur, self._emb_rows, self._emb_key, self._ckv_all = None, None, None, {}, None, None
-            if config.hoist_step_invariants and not config.cfg_parallel:
-                self._kv_all, self._kv_key = unet.context_kv(self._ctx2), self._weights_key()
-                if control:
-                    self._ckv_all = self.control_model.context_kv(self._ctx2)
-                row = self._time_row(sp.set(981.0))
-                self._emb_cur = DeviceArray.empty(row.shape, row.dtype, "row")       # what the captured step reads (fp16, or bfloat16 bits in the bf16 step)
-                assert self._emb_cur.nbytes % 16 == 0
-                hip.tf_memcpy_async(self._emb_cur.ptr, row.ptr, row.nbytes, 3, _sh())   # (the warm-up steps below run at t = 981)
-                self._keep_row = row
-                for t in (timesteps if timesteps is not None else ()):
-                    self._emb_row(float(t))
-            saved = DeviceArray.empty(latent.shape, np.float32, "row")
-            hip.tf_memcpy_async(saved.ptr, latent.ptr, latent.nbytes, 3, _sh())
-            for _ in range(warmup):                 # warms the pool and builds the lazily packed weights
-                if sampler is not None:
-                    hip.tf_set_sampler_params(sp.dev.ptr, 981.0, 0.5, 0.6, 7.5, 0, 0, 0, 0, None, None, 0, _sh())
-                else:
-                    sp.set(981.0, 0.5, 0.6, 7.5)
-                self._eager_step(sp)
-            hip.tf_memcpy_async(latent.ptr, saved.ptr, latent.nbytes, 3, _sh())
-            self._stream.synchronize()
-            if getattr(self, "_graph_blocks", None):          # a previous graph of this model: its buffers go back to the pool
-                hip.tf_graph_destroy(self._graph)
-                pool().disown(self._graph_blocks)
-                self._graph, self._graph_blocks = None, None
-            pool().begin_capture()
-            g, ok = ctypes.c_void_p(), False
-            try:
-                hip.tf_graph_begin_capture(self._stream.handle)
-                self._eager_step(sp)
-                hip.tf_graph_end_capture(self._stream.handle, ctypes.byref(g))
-                ok = True
-            finally:
-                blocks = pool().end_capture()    # every block the captured step touches now belongs to the graph
-                if not ok:
-                    # an op raised inside the capture (pool frozen, untuned shape, ...): leave capture mode so that the stream
-                    # stays usable, and give the blocks back -- there is no graph to own them
-                    hip.tf_graph_abort_capture(self._stream.handle)
-                    self._keep = None
-                    pool().disown(blocks)
-            self._graph, self._graph_blocks = g, blocks
+            self._hoist(sp, timesteps)
+            self._warm_up(sp, warmup)
+            self._capture(sp)
         return self
 
-    def _eager_step(self, sp):
-        b, c, h, w = self._latent.shape
-        concat = getattr(self, "_concat", None)
-        x2 = self._cfg_concat() if concat else self._cfg_duplicate(self._latent)
-        unet = self.model.diffusion_model
-        if config.cfg_parallel:
-            # the unconditional and the conditional half of the CFG pair (variants/sd.py:31-32) as two independent UNet chains: one runs
-            # as a side branch of the step (its own stream / graph branch), so the launch gaps and partly filled grids of one chain are
-            # covered by the other; what both share (time embedding, context K|V) is computed once in front of the fork
-            emb, emb_all, kv_all = unet.step_shared(sp, self._ctx2)
-            half = lambda a, i: a.view((b,) + a.shape[1:], a.layout, i * b * (a.size // a.shape[0])) if a is not None else None
-            br = Branch()
-            with br:
-                out_u = unet(half(x2, 0), sp, None, shared=(emb, emb_all, half(kv_all, 0)))
-            out_c = unet(half(x2, 1), sp, None, shared=(emb, emb_all, half(kv_all, 1)))
-            br.join()
-            hip.tf_cfg_ddim_step2_f32(self._latent.ptr, out_u.ptr, out_c.ptr, sp.dev.ptr, b, c, h, w, _sh())
-            self._keep = (x2, out_u, out_c, emb, emb_all, kv_all)
+    def _alloc_sampler_buffers(self):
+        """What a sampler schedule and its modes (inpaint, concat, control) own, on the current stream."""
+        b, _, h, w = shape = self._latent.shape
+        self._params = StepParams(DeviceArray.zeros((8,), np.float32, "row"))      # the sampler block: the 4 step scalars + row, seed, image offset
+        self._coeffs = DeviceArray.from_numpy(np.asarray(self._sched.coeffs, np.float32), np.float32, "row")
+        self._x0_hist = DeviceArray.zeros(shape, np.float32, "row")
+        if self._inpaint:
+            self._x0_init = DeviceArray.zeros(shape, np.float32, "row")
+            self._mask = DeviceArray.from_numpy(np.ones((b, 1, h, w), np.float32), np.float32, "row")
+        if self._concat is not None:
+            self._cond = DeviceArray.zeros((b, inputs.CONCAT_CHANNELS[self._concat], h, w), np.float32, "row")
+            self._edit = DeviceArray.zeros((4,), np.float32, "row")      # [0] g_I, the image guidance of the three-branch update
+            hip.tf_set_step_params(self._edit.ptr, 1.5, 0.0, 0.0, 0.0, _sh())
+        if self._control:
+            self._hint_emb = DeviceArray.zeros((self._groups * b, self.control_model.cfg.model_channels, h, w), _step_dtype(), "nhwc")
+            self._control_scales = DeviceArray.from_numpy(np.ones((16,), np.float32), np.float32, "row")     # one per residual; 16: whole 4-word writes
+
+    def _hoist(self, sp, timesteps):
+        """The private stacked context and -- config.hoist_step_invariants -- what depends on it or on the timestep alone: the K|V projections and
+        the buffer ``_emb_cur`` the captured step reads its time-embedding row from, with the rows of ``timesteps`` computed up front."""
+        self._ctx2 = self._stack_context(self._unc, self._ctx, self._groups)
+        if not config.hoist_step_invariants or config.cfg_parallel:
             return
-        if getattr(self, "_control", False):
-            # the UNet's encoder, then the ControlNet on the same stacked latent, then the seam (UNetModel.__call__ calls `residuals` behind its
-            # middle block); each model reads its own view of the hoisted row [UNet's | ControlNet's]
-            cn, scales = self.control_model, self._control_scales
-            if getattr(self, "_emb_cur", None) is not None:
-                nu = self._emb_cur.shape[1] - cn._prepare()["emb_w"].shape[0]
-                row_u, row_c = self._emb_cur.view((1, nu), "row"), self._emb_cur.view((1, self._emb_cur.shape[1] - nu), "row", nu)
-                residuals = lambda: cn(x2, self._hint_emb, sp, self._ctx2, shared=(None, row_c, self._ckv_all))
-                out = unet(x2, sp, self._ctx2, shared=(None, row_u, self._kv_all), control=(residuals, scales))
+        self._kv_all, self._kv_key = self.model.diffusion_model.context_kv(self._ctx2), self._weights_key()
+        if self._control:
+            self._ckv_all = self.control_model.context_kv(self._ctx2)
+        row = self._time_row(sp.set(981.0))
+        self._emb_cur = DeviceArray.empty(row.shape, row.dtype, "row")       # what the captured step reads (fp16, or bfloat16 bits in the bf16 step)
+        assert self._emb_cur.nbytes % 16 == 0
+        hip.tf_memcpy_async(self._emb_cur.ptr, row.ptr, row.nbytes, 3, _sh())   # (the warm-up steps run at t = 981)
+        self._keep_row = row
+        for t in (timesteps if timesteps is not None else ()):
+            self._emb_row(float(t))
+
+    def _warm_up(self, sp, warmup):
+        """``warmup`` eager steps at t = 981 on a latent that is put back afterwards: they warm the pool and build the lazily packed weights."""
+        latent = self._latent
+        saved = DeviceArray.empty(latent.shape, np.float32, "row")
+        hip.tf_memcpy_async(saved.ptr, latent.ptr, latent.nbytes, 3, _sh())
+        for _ in range(warmup):
+            if self._sched is not None:
+                hip.tf_set_sampler_params(sp.dev.ptr, 981.0, 0.5, 0.6, 7.5, 0, 0, 0, 0, None, None, 0, _sh())
             else:
-                out = unet(x2, sp, self._ctx2, control=(lambda: cn(x2, self._hint_emb, sp, self._ctx2), scales))
-        elif getattr(self, "_emb_cur", None) is not None:
-            out = unet(x2, sp, self._ctx2, shared=(None, self._emb_cur, self._kv_all))     # (step() has put this timestep's row into _emb_cur)
-        else:
-            out = unet(x2, sp, self._ctx2)
-        if concat == "edit":
-            (hip.tf_cfg3_sampler_step_bf16 if config.is_bf16() else hip.tf_cfg3_sampler_step_f32)(
-                self._latent.ptr, out.ptr, self._x0_hist.ptr, sp.dev.ptr, self._coeffs.ptr, len(self._sched.timesteps), self._edit.ptr, b, c, h, w, _sh())
-        elif getattr(self, "_inpaint", False):
-            (hip.tf_cfg_sampler_step_masked_bf16 if config.is_bf16() else hip.tf_cfg_sampler_step_masked_f32)(
-                self._latent.ptr, out.ptr, self._x0_hist.ptr, sp.dev.ptr, self._coeffs.ptr, len(self._sched.timesteps), self._x0_init.ptr, self._mask.ptr,
-                b, c, h, w, _sh())
-        elif getattr(self, "_sched", None) is not None:
-            (hip.tf_cfg_sampler_step_bf16 if config.is_bf16() else hip.tf_cfg_sampler_step_f32)(
-                self._latent.ptr, out.ptr, self._x0_hist.ptr, sp.dev.ptr, self._coeffs.ptr, len(self._sched.timesteps), b, c, h, w, _sh())
-        else:
-            (hip.tf_cfg_ddim_step_bf16 if config.is_bf16() else hip.tf_cfg_ddim_step_f32)(self._latent.ptr, out.ptr, sp.dev.ptr, b, c, h, w, _sh())
-        self._keep = (x2, out)      # graph nodes reference these blocks: keep them out of the pool
+                sp.set(981.0, 0.5, 0.6, 7.5)
+            self._eager_step(sp)
+        hip.tf_memcpy_async(latent.ptr, saved.ptr, latent.nbytes, 3, _sh())
+        self._stream.synchronize()
+
+    def _capture(self, sp):
+        """Capture one ``_eager_step`` on the (drained) sampler stream into the graph ``step`` replays."""
+        if self._graph_blocks:          # a previous graph of this model: its buffers go back to the pool
+            hip.tf_graph_destroy(self._graph)
+            pool().disown(self._graph_blocks)
+            self._graph, self._graph_blocks = None, None
+        pool().begin_capture()
+        g, ok = ctypes.c_void_p(), False
+        try:
+            hip.tf_graph_begin_capture(self._stream.handle)
+            self._eager_step(sp)
+            hip.tf_graph_end_capture(self._stream.handle, ctypes.byref(g))
+            ok = True
+        finally:
+            blocks = pool().end_capture()    # every block the captured step touches now belongs to the graph
+            if not ok:
+                # an op raised inside the capture (pool frozen, untuned shape, ...): leave capture mode so that the stream
+                # stays usable, and give the blocks back -- there is no graph to own them
+                hip.tf_graph_abort_capture(self._stream.handle)
+                self._keep = None
+                pool().disown(blocks)
+        self._graph, self._graph_blocks = g, blocks
+
+    def _eager_step(self, sp):
+        """One step, launch by launch -- what ``_capture`` records: the stacked input, the UNet, the tail that updates the latent."""
+        x2 = self._cfg_concat() if self._concat else self._cfg_duplicate(self._latent)
+        outs = self._unet_two_chains(x2, sp) if config.cfg_parallel else (self._unet(x2, sp),)
+        self._tail(sp, *outs[:2])
+        self._keep = (x2,) + outs       # graph nodes reference these blocks: keep them out of the pool
+
+    def _unet(self, x2, sp):
+        """The UNet's output for the stacked input: plain, from the hoisted row and K|V, or controlled."""
+        unet, cn, row, ctx = self.model.diffusion_model, self.control_model, self._emb_cur, self._ctx2
+        if not self._control:
+            return unet(x2, sp, ctx, shared=None if row is None else (None, row, self._kv_all))     # (step() has put this timestep's row into _emb_cur)
+        # the UNet's encoder, then the ControlNet on the same stacked latent, then the seam (UNetModel.__call__ calls `residuals` behind its
+        # middle block); each model reads its own view of the hoisted row [UNet's | ControlNet's]
+        shared_u = shared_c = None
+        if row is not None:
+            nu = row.shape[1] - cn._prepare()["emb_w"].shape[0]
+            shared_u = (None, row.view((1, nu), "row"), self._kv_all)
+            shared_c = (None, row.view((1, row.shape[1] - nu), "row", nu), self._ckv_all)
+        residuals = lambda: cn(x2, self._hint_emb, sp, ctx, shared=shared_c)
+        return unet(x2, sp, ctx, shared=shared_u, control=(residuals, self._control_scales))
+
+    def _unet_two_chains(self, x2, sp):
+        """config.cfg_parallel: the unconditional and the conditional half of the CFG pair (variants/sd.py:31-32) as two independent UNet chains: one
+        runs as a side branch of the step (its own stream / graph branch), so the launch gaps and partly filled grids of one chain are covered by
+        the other; what both share (time embedding, context K|V) is computed once in front of the fork.  -> (out_u, out_c, the shared arrays...)."""
+        unet, b = self.model.diffusion_model, self._latent.shape[0]
+        emb, emb_all, kv_all = unet.step_shared(sp, self._ctx2)
+        half = lambda a, i: a.view((b,) + a.shape[1:], a.layout, i * b * (a.size // a.shape[0])) if a is not None else None
+        br = Branch()
+        with br:
+            out_u = unet(half(x2, 0), sp, None, shared=(emb, emb_all, half(kv_all, 0)))
+        out_c = unet(half(x2, 1), sp, None, shared=(emb, emb_all, half(kv_all, 1)))
+        br.join()
+        return out_u, out_c, emb, emb_all, kv_all
+
+    def _tail(self, sp, out, out_c=None):
+        """The step's last launch, by mode: CFG combine + the DDIM update (from two chains: tf_cfg_ddim_step2_f32), or the sampler update of the
+        schedule's row -- three-branch for an edit model, masked for inpaint=True."""
+        lat, (b, c, h, w) = self._latent, self._latent.shape
+        if out_c is not None:
+            return hip.tf_cfg_ddim_step2_f32(lat.ptr, out.ptr, out_c.ptr, sp.dev.ptr, b, c, h, w, _sh())
+        if self._sched is None:
+            return _entry16("tf_cfg_ddim_step", "f32")(lat.ptr, out.ptr, sp.dev.ptr, b, c, h, w, _sh())
+        stem, extra = ("tf_cfg3_sampler_step", (self._edit.ptr,)) if self._concat == "edit" else \
+                      ("tf_cfg_sampler_step_masked", (self._x0_init.ptr, self._mask.ptr)) if self._inpaint else ("tf_cfg_sampler_step", ())
+        _entry16(stem, "f32")(lat.ptr, out.ptr, self._x0_hist.ptr, sp.dev.ptr, self._coeffs.ptr, len(self._sched.timesteps), *extra, b, c, h, w, _sh())
+
+    def _advance(self, timestep, eager, set_params):
+        """What ``step`` and ``step_sampler`` share, on the sampler stream: the parameter launch ``set_params(dst, src, nbytes)`` -- hoisted, it also
+        copies this timestep's cached row (src) into ``_emb_cur`` (dst); (None, None, 0) otherwise -- then one graph replay, or the eager step.
+        The stream switch is un-ordered on purpose: an event edge between two graph launches costs 0.2 ms per step (measured, tools/ab3.sh), and
+        consecutive steps are ordered by the stream itself."""
+        with use_stream(self._stream, ordered=False):
+            if self._emb_cur is not None:
+                row = self._hoisted_row(timestep)
+                set_params(self._emb_cur.ptr, row.ptr, row.nbytes)
+            else:
+                set_params(None, None, 0)
+            if eager or self._graph is None:
+                self._eager_step(self._params)
+            else:
+                hip.tf_graph_launch(self._graph, self._stream.handle)
 
     def step(self, timestep, a_t, a_prev, guidance, eager=False):
-        """One denoising step on the sampler stream, asynchronous.  The stream switch is un-ordered on purpose: an event
-        edge between two graph launches costs 0.2 ms per step (measured, tools/ab3.sh), and consecutive steps are ordered by
-        the stream itself.  Work on other streams that touches the latent goes through set_latent() / synchronize().
+        """One denoising step on the sampler stream, asynchronous (``_advance``).  Work on other streams that touches the latent goes through
+        set_latent() / synchronize().
         After a ``set_adapters`` that changed a weight of a compiled model, ``set_latent`` must come first (UnsupportedSamplerConfig otherwise)."""
-        if getattr(self, "_sched", None) is not None:
+        self._require_compiled("step")
+        if self._sched is not None:
             raise UnsupportedSamplerConfig("StableDiffusion.step: this model was compiled with a sampler schedule -- drive it with start() / run() / step_sampler()")
         self._require_started("step")
         sp = self._params
-        with use_stream(self._stream, ordered=False):
-            if getattr(self, "_emb_cur", None) is not None:
-                row = self._hoisted_row(timestep)
-                hip.tf_set_step_params_copy(sp.dev.ptr, float(timestep), float(a_t), float(a_prev), float(guidance), self._emb_cur.ptr, row.ptr, row.nbytes, _sh())
-            else:
+
+        def set_params(dst, src, nbytes):
+            if dst is None:
                 sp.set(timestep, a_t, a_prev, guidance)
-            if eager or self._graph is None:
-                self._eager_step(sp)
             else:
-                hip.tf_graph_launch(self._graph, self._stream.handle)
+                hip.tf_set_step_params_copy(sp.dev.ptr, float(timestep), float(a_t), float(a_prev), float(guidance), dst, src, nbytes, _sh())
+        self._advance(timestep, eager, set_params)
 
     def _hoisted_row(self, timestep):
         """The cached time-embedding row of this timestep for the replay's parameter launch; refreshes the hoisted K|V first if a weight changed."""
         key = self._weights_key()
-        if getattr(self, "_kv_all", None) is not None and self._kv_key != key:
+        if self._kv_all is not None and self._kv_key != key:
             # a to_k / to_v (or any hoisted) weight was replaced since compile(): the K|V projection the graph reads is stale -- refresh it in place
             self._kv_tmp, self._kv_key = self._refresh_kv(), key
         return self._emb_row(float(timestep), key)     # (computed on this stream the first time a timestep is seen)
 
     # -- sampler schedules (compile(..., sampler=Schedule)) -----------------------------------------------------------------------
+    def _require_compiled(self, what):
+        if self._stream is None:
+            raise RuntimeError(f"StableDiffusion.{what}: compile() first -- this model has no compiled step, sampler stream or latent yet")
+
     def _require_started(self, what):
-        if getattr(self, "_needs_start", False):
+        if self._needs_start:
             raise UnsupportedSamplerConfig(f"StableDiffusion.{what}: set_adapters captured the step again and the previous start's state (latent, mask, "
                                            "conditioning, hint, cursor) did not survive -- call start() (or set_latent(), for the DDIM step) first")
 
     def _require_sampler(self, what):
-        if getattr(self, "_sched", None) is None:
-            raise UnsupportedSamplerConfig(f"StableDiffusion.{what}: compile(..., sampler=<Schedule>) first (this model runs the DDIM step())")
+        if self._sched is None:
+            raise UnsupportedSamplerConfig(f"StableDiffusion.{what}: compile(..., sampler=<Schedule>) first (this model "
+                                           + ("was never compiled)" if self._stream is None else "runs the DDIM step())"))
         return self._sched
 
     def start(self, seed=None, noise=None, image_offset=0, init_image=None, init_latent=None, mask=None, cond_image=None, cond_mask=None,
@@ -533,17 +554,18 @@ class StableDiffusion:
         self._require_sampler("start")
         ctrl = self._check_control(control_image, control_hint, control_scale)
         cond = self._check_cond(cond_image, cond_mask, cond_latent, image_guidance)
-        latent = self._start_latent(seed, noise, image_offset, init_image, init_latent, mask)
+        latent = self._check_latent(seed, noise, image_offset, init_image, init_latent, mask)
+        self._write_latent(*latent)                # every check has passed: from here on the model changes
         if cond is not None:
             self._write_cond(*cond)
         if ctrl is not None:
             self._write_control(*ctrl)
-        return latent
+        return self._latent
 
     def _check_control(self, control_image, control_hint, control_scale):
         """start()'s ControlNet arguments, checked against the compiled model before anything changes: None for a model without control=True, else
         (device or host uint8 image or None, host float hint or None, the 16 fp32 scale words)."""
-        if not getattr(self, "_control", False):
+        if not self._control:
             if any(v is not None for v in (control_image, control_hint, control_scale)):
                 raise ValueError("StableDiffusion.start: control_image=, control_hint= and control_scale= need a model compiled with control=True")
             return None
@@ -552,23 +574,10 @@ class StableDiffusion:
         if control_image is not None and control_hint is not None:
             raise ValueError("StableDiffusion.start: pass control_image= or control_hint=, not both")
         b, _, h, w = self._latent.shape
-        n_res = len(self.control_model.input_blocks) + 1
-        scales = np.ones((16,), np.float32)
-        if control_scale is not None:
-            sc = np.asarray(control_scale, dtype=np.float32)
-            if sc.ndim > 1 or (sc.ndim == 1 and sc.shape[0] != n_res):
-                raise ValueError(f"StableDiffusion.start: control_scale= takes one float or {n_res} (one per residual), got shape {sc.shape}")
-            if not np.isfinite(sc).all():
-                raise ValueError(f"StableDiffusion.start: control_scale={control_scale}")
-            scales[:n_res] = sc
+        scales = inputs.control_scales(control_scale, len(self.control_model.input_blocks) + 1)
         if control_image is not None:
-            if not isinstance(control_image, DeviceArray):
-                control_image = np.ascontiguousarray(control_image)
-            ish = tuple(int(v) for v in control_image.shape)
-            if np.dtype(control_image.dtype) != np.uint8 or len(ish) != 4 or ish[0] not in (1, b) or ish[1:] != (8 * h, 8 * w, 3):
-                raise ValueError(f"StableDiffusion.start: control_image must be uint8 {(b, 8 * h, 8 * w, 3)} (or one image for all) for the compiled latent, "
-                                 f"got {np.dtype(control_image.dtype)} {ish}")
-            return control_image, None, scales
+            rule = f"StableDiffusion.start: control_image must be uint8 {(b, 8 * h, 8 * w, 3)} (or one image for all) for the compiled latent"
+            return inputs.u8_image(control_image, rule, (8 * h, 8 * w), (1, b))[0], None, scales
         if isinstance(control_hint, DeviceArray):
             raise TypeError("StableDiffusion.start: control_hint= takes a host array (a device image goes through control_image=)")
         hint = np.ascontiguousarray(control_hint, dtype=np.float32)
@@ -605,8 +614,10 @@ class StableDiffusion:
                         hip.tf_memcpy_async(self._hint_emb.ptr + (g * b + k) * per, emb.ptr, per, 3, _sh())
             self._control_keep = (dev, x, emb)                           # (referenced until the kernels have run)
 
-    def _start_latent(self, seed, noise, image_offset, init_image, init_latent, mask):
-        """start()'s latent side: text-to-image, image-to-image and the latent-blend inpainting buffers."""
+    def _check_latent(self, seed, noise, image_offset, init_image, init_latent, mask):
+        """start()'s latent arguments -- text-to-image, image-to-image, the latent-blend inpainting buffers -- checked against the compiled model
+        before anything changes: (seed words, image offset, host noise or None, checked init_image or None, x0 as a device or fp32 host array or
+        None, the inpainting mask as a device or fp32 host array or None)."""
         init = init_image if init_image is not None else init_latent
         if init_image is not None and init_latent is not None:
             raise ValueError("StableDiffusion.start: pass init_image= or init_latent=, not both")
@@ -616,61 +627,73 @@ class StableDiffusion:
             raise ValueError("StableDiffusion.start: pass seed= (device noise) or noise= (a host array)")
         if int(image_offset) < 0:
             raise ValueError(f"StableDiffusion.start: image_offset must be >= 0, got {image_offset}")
-        inpaint = getattr(self, "_inpaint", False)
-        if mask is not None and not inpaint:
+        if mask is not None and not self._inpaint:
             raise ValueError("StableDiffusion.start: mask= needs a model compiled with inpaint=True")
-        if inpaint and init is None:
+        if self._inpaint and init is None:
             raise ValueError("StableDiffusion.start: an inpainting model starts from init_image= or init_latent=")
-        self._seed, self._image_offset, self._cursor = _seed_words(0 if seed is None else seed), int(image_offset), 0
-        self._needs_start = False
-        if init is None:
-            if noise is not None:
-                return self.set_latent(noise)
-            self.synchronize()
-            b = self._latent.shape[0]
-            with use_stream(self._stream):
-                hip.tf_randn_f32(self._latent.ptr, b, self._latent.size // b, self._seed[0], self._seed[1], self._image_offset, 0, 0, _sh())
-            return self._latent
-        b = self._latent.shape[0]
-        lat_mask = None
-        if inpaint:
-            lat_mask = self._mask_for_start(mask)
-        if init_latent is not None and isinstance(init_latent, DeviceArray):
-            if init_latent.shape != self._latent.shape or init_latent.dtype != np.float32 or init_latent.layout != "row":
-                raise ValueError(f"StableDiffusion.start: init_latent must be an fp32 NCHW {self._latent.shape} array, got {init_latent}")
-            hip.tf_stream_sync(_sh())                                  # (made on the caller's stream)
+        shape = self._latent.shape
+        if noise is not None:
+            noise = np.asarray(noise)
+            if noise.shape != shape:
+                raise ValueError(f"StableDiffusion.start: noise must have the latent's shape {shape}, got {noise.shape}")
+        if init_image is not None:
+            init_image = self._check_encodable(init_image, "init_image")
         elif init_latent is not None:
-            x0h = np.asarray(init_latent)
-            if x0h.shape != self._latent.shape:
-                raise ValueError(f"StableDiffusion.start: init_latent must have the latent's shape {self._latent.shape}, got {x0h.shape}")
-        else:
-            init_image = init_image if isinstance(init_image, DeviceArray) else np.asarray(init_image)
-            ish = tuple(int(v) for v in init_image.shape)
-            if len(ish) != 4 or (ish[0], 4, ish[1] // 8, ish[2] // 8) != self._latent.shape:
-                raise ValueError(f"StableDiffusion.start: init_image {ish} does not encode to the compiled latent {self._latent.shape}")
+            init_latent = inputs.fp32_nchw(init_latent, shape, "init_latent")
+        if self._inpaint:
+            if mask is None:
+                mask = np.ones(self._mask.shape, np.float32)
+            else:        # a device fp32 (B,1,h,w) array as it is; anything else through latent_mask
+                mask = inputs.fp32_nchw(mask if isinstance(mask, DeviceArray) else self.latent_mask(mask), self._mask.shape, "mask (at latent size)")
+        return _seed_words(0 if seed is None else seed), int(image_offset), noise, init_image, init_latent, mask
+
+    def _check_encodable(self, image, name):
+        """start()'s images that go through the VAE encoder: uint8, host or device, of the compiled latent's batch and 8x its size, on a model whose
+        encoder holds weights and can take that size.  -> the image (host: contiguous)."""
+        b, _, h, w = self._latent.shape
+        rule = f"StableDiffusion.start: {name} must be uint8 {(b, 8 * h, 8 * w, 3)} for the compiled latent"
+        image, _ = inputs.u8_image(image, rule, (8 * h, 8 * w), (b,))
+        self._encoder_side("start")
+        why = self.encoder_size_error(8 * h, 8 * w)
+        if why:
+            raise ValueError(f"StableDiffusion.start: {name}: {why}")
+        return image
+
+    def _write_latent(self, seed, image_offset, noise, init_image, x0, mask):
+        """Rewind the schedule and set the latent (and the inpainting buffers) on the sampler stream, behind every step already queued."""
+        self._seed, self._image_offset, self._cursor = seed, image_offset, 0
+        self._needs_start = False
+        b = self._latent.shape[0]
+        if init_image is None and x0 is None:
+            if noise is not None:
+                self.set_latent(noise)
+                return
+            self.synchronize()
+            with use_stream(self._stream):
+                hip.tf_randn_f32(self._latent.ptr, b, self._latent.size // b, seed[0], seed[1], image_offset, 0, 0, _sh())
+            return
+        for made_by_caller in (mask, x0):
+            if isinstance(made_by_caller, DeviceArray):
+                hip.tf_stream_sync(_sh())                              # (made on the caller's stream)
         self.synchronize()
         with use_stream(self._stream):
             if init_image is not None:
                 x0 = self.encode_image(init_image)
-            elif isinstance(init_latent, DeviceArray):
-                x0 = init_latent
-            else:
-                x0 = DeviceArray.from_numpy(np.ascontiguousarray(x0h, dtype=np.float32), np.float32, "row")
-            if inpaint:
+            elif not isinstance(x0, DeviceArray):
+                x0 = DeviceArray.from_numpy(x0, np.float32, "row")
+            if self._inpaint:
                 hip.tf_memcpy_async(self._x0_init.ptr, x0.ptr, x0.nbytes, 3, _sh())
-                if isinstance(lat_mask, DeviceArray):
-                    hip.tf_memcpy_async(self._mask.ptr, lat_mask.ptr, lat_mask.nbytes, 3, _sh())
+                if isinstance(mask, DeviceArray):
+                    hip.tf_memcpy_async(self._mask.ptr, mask.ptr, mask.nbytes, 3, _sh())
                 else:
-                    self._mask.copy_from_numpy(lat_mask)
-            hip.tf_noise_to_level_f32(self._latent.ptr, x0.ptr, b, self._latent.size // b, float(self._sched.alphas[0]), self._seed[0], self._seed[1],
-                                      self._image_offset, _sh())
+                    self._mask.copy_from_numpy(mask)
+            hip.tf_noise_to_level_f32(self._latent.ptr, x0.ptr, b, self._latent.size // b, float(self._sched.alphas[0]), seed[0], seed[1], image_offset, _sh())
             self._start_keep = x0                                       # (referenced until the kernels have run)
-        return self._latent
 
     def _check_cond(self, cond_image, cond_mask, cond_latent, image_guidance):
         """start()'s conditioning arguments, checked against the compiled model before anything changes: None for a model without concat=, else
         (image or None, uint8 image-size mask or None, latent mask or None, cond_latent or None, g_I or None), host arrays converted."""
-        concat = getattr(self, "_concat", None)
+        concat = self._concat
         if concat is None:
             if any(v is not None for v in (cond_image, cond_mask, cond_latent, image_guidance)):
                 raise ValueError("StableDiffusion.start: cond_image=, cond_mask=, cond_latent= and image_guidance= need a model compiled with concat=")
@@ -688,33 +711,17 @@ class StableDiffusion:
                 raise ValueError(f"StableDiffusion.start: image_guidance={image_guidance}")
         if cond_mask is not None and (concat != "inpaint" or cond_image is None):
             raise ValueError("StableDiffusion.start: cond_mask= goes with cond_image= on a model compiled with concat='inpaint' (a cond_latent carries its mask channel)")
-        shape = self._cond.shape
         if cond_latent is not None:
-            if isinstance(cond_latent, DeviceArray):
-                if cond_latent.shape != shape or cond_latent.dtype != np.float32 or cond_latent.layout != "row":
-                    raise ValueError(f"StableDiffusion.start: a device cond_latent must be an fp32 NCHW {shape} array, got {cond_latent}")
-            else:
-                cond_latent = np.ascontiguousarray(cond_latent, dtype=np.float32)
-                if cond_latent.shape != shape:
-                    raise ValueError(f"StableDiffusion.start: cond_latent must have the shape {shape}, got {cond_latent.shape}")
-            return None, None, None, cond_latent, image_guidance
-        self._encoder_side("start")
-        if not isinstance(cond_image, DeviceArray):
-            cond_image = np.ascontiguousarray(cond_image)
-        ish = tuple(int(v) for v in cond_image.shape)
-        if np.dtype(cond_image.dtype) != np.uint8 or len(ish) != 4 or ish[3] != 3 or (ish[0], ish[1], ish[2]) != (shape[0], 8 * shape[2], 8 * shape[3]):
-            raise ValueError(f"StableDiffusion.start: cond_image must be uint8 {(shape[0], 8 * shape[2], 8 * shape[3], 3)} for the compiled latent, "
-                             f"got {np.dtype(cond_image.dtype)} {ish}")
-        why = self.encoder_size_error(ish[1], ish[2])
-        if why:
-            raise ValueError(f"StableDiffusion.start: cond_image: {why}")
+            return None, None, None, inputs.fp32_nchw(cond_latent, self._cond.shape, "cond_latent"), image_guidance
+        self._encoder_side("start")                # (a model without an encoder says so before the image is looked at)
+        cond_image = self._check_encodable(cond_image, "cond_image")
         m8 = lat_mask = None
         if concat == "inpaint":
             if cond_mask is None:
                 raise ValueError("StableDiffusion.start: an inpainting checkpoint's cond_image= needs cond_mask= (the region to repaint)")
             m8 = self.concat_mask_u8(cond_mask)
-            if m8.shape != ish[:3]:
-                raise ValueError(f"StableDiffusion.start: cond_mask is {m8.shape}, the cond_image needs {ish[:3]}")
+            if m8.shape != cond_image.shape[:3]:
+                raise ValueError(f"StableDiffusion.start: cond_mask is {m8.shape}, the cond_image needs {tuple(cond_image.shape[:3])}")
             lat_mask = self.concat_mask(m8)
         return cond_image, m8, lat_mask, None, image_guidance
 
@@ -734,37 +741,15 @@ class StableDiffusion:
             if cond_latent is not None:
                 self._cond.copy_from_numpy(cond_latent)
                 return
-            fsm = self.first_stage_model
-            dev = image if isinstance(image, DeviceArray) else DeviceArray.from_numpy(image, np.uint8, "row")
-            x = DeviceArray.empty((b, 3, 8 * h, 8 * w), np.float16, "nhwc")      # NHWC: the (B,H,W,3) element order of the uint8 image
             if m8 is None:                                                   # edit: the unscaled mode of the posterior
-                hip.tf_image_from_u8_f16(x.ptr, dev.ptr, x.size, _sh())
-                means = fsm.encode(x)
+                means, self._cond_keep = self._encode_u8(self.first_stage_model, image)
                 hip.tf_means_to_cond_f32(self._cond.ptr, means.ptr, b, h, w, 1.0, 0, cc, _sh())
-                self._cond_keep = (dev, x, means)                            # (referenced until the kernels have run)
                 return
-            dm8 = DeviceArray.from_numpy(m8, np.uint8, "row")
             dlm = DeviceArray.from_numpy(lat_mask, np.float32, "row")
-            hip.tf_image_from_u8_masked_f16(x.ptr, dev.ptr, dm8.ptr, b, 8 * h, 8 * w, _sh())
-            means = fsm.encode(x)
+            means, keep = self._encode_u8(self.first_stage_model, image, m8)
             hip.tf_memcpy_2d_async(self._cond.ptr, cc * h * w * 4, dlm.ptr, h * w * 4, h * w * 4, b, _sh())     # channel 0: the latent mask
             hip.tf_means_to_cond_f32(self._cond.ptr, means.ptr, b, h, w, 0.18215, 1, cc, _sh())
-            self._cond_keep = (dev, x, means, dm8, dlm)
-
-    def _mask_for_start(self, mask):
-        """The inpainting mask start() writes: all ones without one; a device fp32 (B,1,h,w) array as it is; anything else through latent_mask."""
-        shape = self._mask.shape
-        if mask is None:
-            return np.ones(shape, np.float32)
-        if isinstance(mask, DeviceArray):
-            if mask.shape != shape or mask.dtype != np.float32 or mask.layout != "row":
-                raise ValueError(f"StableDiffusion.start: a device mask must be fp32 {shape}, got {mask}")
-            hip.tf_stream_sync(_sh())                                  # (made on the caller's stream)
-            return mask
-        m = self.latent_mask(mask)
-        if m.shape != shape:
-            raise ValueError(f"StableDiffusion.start: the mask is {m.shape} at latent size, the compiled latent needs {shape}")
-        return m
+            self._cond_keep = keep + (dlm,)                                  # (referenced until the kernels have run)
 
     def step_sampler(self, i, guidance, eager=False):
         """Step i of the compiled schedule (asynchronous, on the sampler stream): one parameter launch (timestep scalars, schedule row, seed and
@@ -776,18 +761,9 @@ class StableDiffusion:
         if not 0 <= i < n:
             raise IndexError(f"StableDiffusion.step_sampler: step {i} outside the schedule's {n} steps")
         t = sched.timesteps[i]
-        with use_stream(self._stream, ordered=False):
-            if getattr(self, "_emb_cur", None) is not None:
-                row = self._hoisted_row(t)
-                dst, src, nbytes = self._emb_cur.ptr, row.ptr, row.nbytes
-            else:
-                dst, src, nbytes = None, None, 0
-            hip.tf_set_sampler_params(self._params.dev.ptr, float(t), float(sched.alphas[i]), float(sched.alphas_prev[i]), float(guidance), i,
-                                      self._seed[0], self._seed[1], self._image_offset, dst, src, nbytes, _sh())
-            if eager or self._graph is None:
-                self._eager_step(self._params)
-            else:
-                hip.tf_graph_launch(self._graph, self._stream.handle)
+        self._advance(t, eager, lambda dst, src, nbytes: hip.tf_set_sampler_params(
+            self._params.dev.ptr, float(t), float(sched.alphas[i]), float(sched.alphas_prev[i]), float(guidance), i, self._seed[0], self._seed[1],
+            self._image_offset, dst, src, nbytes, _sh()))
         self._cursor = i + 1
 
     def run(self, guidance, eager=False):
@@ -815,13 +791,13 @@ class StableDiffusion:
     def _weights_key(self):
         """weights_key() of everything the hoisted tables were computed from: the UNet and, in a controlled model, the ControlNet."""
         key = self.model.diffusion_model.weights_key()
-        return key + self.control_model.weights_key() if getattr(self, "_control", False) else key
+        return key + self.control_model.weights_key() if self._control else key
 
     def _time_row(self, params):
         """The hoisted time-embedding row of one timestep: the UNet's, and behind it in the same buffer a controlled model's ControlNet's -- one
         copy in the parameter launch hands both to the replay."""
         row = self.model.diffusion_model.time_embedding_all(params)[1]
-        if not getattr(self, "_control", False):
+        if not self._control:
             return row
         crow = self.control_model.time_embedding_all(params)[1]
         both = DeviceArray.empty((1, row.shape[1] + crow.shape[1]), row.dtype, "row")
@@ -836,7 +812,7 @@ class StableDiffusion:
         kv = self.model.diffusion_model.context_kv(self._ctx2)
         hip.tf_memcpy_async(self._kv_all.ptr, kv.ptr, kv.nbytes, 3, _sh())
         ckv = None
-        if getattr(self, "_ckv_all", None) is not None:
+        if self._ckv_all is not None:
             ckv = self.control_model.context_kv(self._ctx2)
             hip.tf_memcpy_async(self._ckv_all.ptr, ckv.ptr, ckv.nbytes, 3, _sh())
         return kv, ckv
@@ -844,16 +820,18 @@ class StableDiffusion:
     def set_context(self, unconditional_context, context):
         """New prompts for the compiled step: refresh the stacked context in place (the captured graph reads these buffers) and the
         cross-attention K|V projection that was hoisted out of the step.  Ordered on the sampler stream."""
+        self._require_compiled("set_context")
         with use_stream(self._stream):
-            new = self._stack_context(unconditional_context, context, getattr(self, "_groups", 2))       # (in the step's 16-bit type)
+            new = self._stack_context(unconditional_context, context, self._groups)       # (in the step's 16-bit type)
             assert new.nbytes == self._ctx2.nbytes, "set_context: the contexts must have the shape the step was compiled for"
             hip.tf_memcpy_async(self._ctx2.ptr, new.ptr, new.nbytes, 3, _sh())
             self._ctx_tmp = new                                    # (referenced until the copy has run)
-            if getattr(self, "_kv_all", None) is not None:
+            if self._kv_all is not None:
                 self._kv_tmp, self._kv_key = self._refresh_kv(), self._weights_key()   # (referenced until the copies have run)
         self._unc, self._ctx = unconditional_context, context
 
     def synchronize(self):
+        self._require_compiled("synchronize")
         self._stream.synchronize()
 
     # -- LoRA adapters (storage/lora.py) ---------------------------------------------------------------------------------------------------------
@@ -894,7 +872,7 @@ class StableDiffusion:
             raise TypeError("StableDiffusion.set_adapters: names is a list of adapter names")
         reg = self._lora if self._lora is not None else L.LoraRegistry()
         plan, active = L.plan_adapters(reg.loaded, names, weights, text_encoder_weights)
-        compiled = getattr(self, "_graph", None) is not None and getattr(self, "_compile_args", None) is not None
+        compiled = self._graph is not None and self._compile_args is not None
         if compiled:
             self.synchronize()
         hip.tf_stream_sync(_sh())

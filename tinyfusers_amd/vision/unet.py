@@ -67,11 +67,14 @@ class Downsample:
 
 class StepParams:
     """Device-resident per-step scalars [timestep, a_t, a_prev, guidance] (fp32).  ``set`` is a 1-thread kernel
-    whose arguments carry the values, so it is stream-ordered with the step graph that reads them."""
+    whose arguments carry the values, so it is stream-ordered with the step graph that reads them.  ``StepParams(dev)`` wraps an existing
+    device array that starts with these four words (a sampler's parameter block, a caller's timestep array) and writes nothing."""
 
-    def __init__(self):
-        self.dev = DeviceArray.empty((4,), np.float32, "row")
-        self.set(0.0)
+    def __init__(self, dev=None):
+        self.dev = dev
+        if dev is None:
+            self.dev = DeviceArray.empty((4,), np.float32, "row")
+            self.set(0.0)
 
     def set(self, timestep, a_t=1.0, a_prev=1.0, guidance=1.0):
         hip.tf_set_step_params(self.dev.ptr, float(timestep), float(a_t), float(a_prev), float(guidance), _sh())
@@ -82,9 +85,7 @@ def _as_params(timesteps):
     if isinstance(timesteps, StepParams):
         return timesteps
     if isinstance(timesteps, DeviceArray):
-        sp = StepParams.__new__(StepParams)
-        sp.dev = timesteps
-        return sp
+        return StepParams(timesteps)
     t = float(np.asarray(timesteps, dtype=np.float32).reshape(-1)[0])
     return StepParams().set(t)
 
