@@ -272,6 +272,13 @@ int tf_conv2d_gn_f16(void* y, const void* x, const void* x2, const void* w, cons
 size_t tf_conv2d_fused_workspace(int N, int H, int W, int C1, int C2, int Cout, int R, int S, int stride, int pad, int upsample,
                                  int C3, int C4);
 size_t tf_conv2d_gn_partial_bytes(int N, int groups);
+/* read-only query (host code, no device work): 1 where k_igemm_patch -- the patch variant tf_gemm_debug(128) asks for -- takes the bm x bn tile of
+ * this conv (vision/conv2d.py:9-28), 0 where such a launch runs the deep ring instead: the launcher's own rule, so a test can tell which ran */
+int tf_conv2d_patch_admits(int N, int H, int W, int C1, int C2, int Cout, int R, int S, int stride, int pad, int upsample, int C3, int C4, int bm, int bn);
+/* read-only query (host code): the form of k_igemm -- 0 deep ring, 1 wide ring, 3 all-8 ring: the variant numbers of tf_prof_dump -- that the
+ * bm x bn tile runs when tf_gemm_debug asked for `variant`; a form the tile does not have quietly runs the deep ring (128 x 160 and 256 x 128 have
+ * no wide ring, 256 x 128 and channel counts off the 64 grid no all-8 ring).  The launcher's own rule; 10001 for a tile or variant k_igemm has not */
+int tf_gemm_ring_form(int bm, int bn, int variant, int channels_on_64_grid);
 /* cublasSgemm_v2 / cublasSgemmBatched (native/cublas/ops.py:22-53) as linear_cublas / gemm_batch call them
  * (ff/linear.py:58-61, :98-101): fp32, column-major, C = alpha op(A) op(B) + beta C; transa/transb 0 = N, 1 = T, 2 = C
  * (the cublasOperation_t numbers, native/cublas/ops.py:55-58).  alpha / beta are passed by value (the reference passes

@@ -29,6 +29,29 @@ def test_header_symbols_exported(native):
         assert hasattr(dll, n), f"{n} declared in the header but not exported by the library"
 
 
+def test_patch_query_answers_with_the_launchers_rule(native):
+    """tf_conv2d_patch_admits (host code): what lets a test tell k_igemm_patch from the deep ring it silently gives way to -- 3 x 3 / stride 1 /
+    pad 1 on the 64-channel grid, W a power of two inside the tile, tiles {64, 128} x {128, 160}."""
+    q = native.lib.tf_conv2d_patch_admits
+    assert q(2, 16, 16, 64, 0, 320, 3, 3, 1, 1, 0, 0, 0, 64, 128) == 1 and q(2, 16, 16, 64, 64, 320, 3, 3, 1, 1, 0, 64, 0, 128, 160) == 1
+    for bad in [(2, 16, 16, 64, 0, 320, 1, 1, 1, 0, 0, 0, 0, 64, 128), (2, 16, 16, 64, 0, 320, 3, 3, 1, 1, 0, 0, 0, 64, 64), (2, 10, 10, 64, 0, 320, 3, 3, 1, 1, 0, 0, 0, 64, 128),
+                (2, 16, 16, 72, 0, 320, 3, 3, 1, 1, 0, 0, 0, 64, 128), (2, 16, 16, 64, 0, 320, 3, 3, 2, 1, 0, 0, 0, 64, 128), (2, 16, 16, 64, 0, 320, 3, 3, 1, 1, 1, 0, 0, 64, 128),
+                (0, 16, 16, 64, 0, 320, 3, 3, 1, 1, 0, 0, 0, 64, 128), (2, 256, 256, 64, 0, 320, 3, 3, 1, 1, 0, 0, 0, 64, 128)]:
+        assert q(*bad) == 0, bad
+
+
+def test_ring_form_query_answers_with_the_launchers_rule(native):
+    """tf_gemm_ring_form (host code): the k_igemm form a tile runs for an asked variant -- no wide ring on 128 x 160 and 256 x 128, no all-8 ring
+    on 256 x 128 or off the 64-channel grid; what a tile has not runs the deep ring."""
+    q = native.lib.tf_gemm_ring_form
+    for bm in (64, 128):
+        for bn in (64, 128, 160):
+            assert q(bm, bn, 0, 1) == 0 and q(bm, bn, 3, 1) == 3 and q(bm, bn, 3, 0) == 0
+            assert q(bm, bn, 1, 1) == q(bm, bn, 1, 0) == (0 if (bm, bn) == (128, 160) else 1)
+    assert [q(256, 128, v, 1) for v in (0, 1, 3)] == [0, 0, 0]
+    assert q(256, 160, 0, 1) == 10001 and q(64, 64, 2, 1) == 10001 and b"tf_gemm_ring_form" in native.lib.tf_last_error()
+
+
 def test_every_entry_cites_the_reference():
     hdr = open(os.path.join(ROOT, "include", "tinyfusers_hip.h")).read()
     # each block of prototypes is preceded by a comment naming the reference file:line it replaces

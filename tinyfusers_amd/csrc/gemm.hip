@@ -461,6 +461,19 @@ int tf_conv2d_gn_supported(int N, int H, int W, int C1, int C2, int Cout, int R,
   return gi_any_ok(p) ? 1 : 0;
 }
 
+int tf_conv2d_patch_admits(int N, int H, int W, int C1, int C2, int Cout, int R, int S, int stride, int pad, int upsample, int C3, int C4, int bm, int bn) {
+  if (N < 1 || C1 < 1 || C2 < 0 || C3 < 0 || C4 < 0 || Cout < 1 || R != S) return 0;
+  GemmP p;
+  if (conv_shape(p, EL_16, {N, H, W, C1, C2, Cout, R, S, stride, pad, upsample, C3, C4})) return 0;
+  return patch_admits(p, bm, bn) ? 1 : 0;
+}
+
+int tf_gemm_ring_form(int bm, int bn, int variant, int channels_on_64_grid) {
+  TF_REQUIRE(((bm == 64 || bm == 128) && (bn == 64 || bn == 128 || bn == 160)) || (bm == 256 && bn == 128), "tf_gemm_ring_form: k_igemm has no %dx%d tile", bm, bn);
+  TF_REQUIRE(variant == V_RING || variant == V_WIDE || variant == V_ALL8, "tf_gemm_ring_form: variant=%d is not a k_igemm form (0, 1, 3)", variant);
+  return igemm_ring_form(bm, bn, variant == V_WIDE, variant == V_ALL8, !channels_on_64_grid);
+}
+
 int tf_conv2d_gn_16(int dtype, void* y, const void* x, const void* x2, const void* w, const void* bias, const void* bias_nc, long long bias_nc_stride,
                     const void* residual, int N, int H, int W, int C1, int C2, int Cout, int R, int S, int stride, int pad, int upsample,
                     void* workspace, size_t workspace_bytes, const void* x3, const void* x4, int C3, int C4, void* gn_partial,

@@ -704,6 +704,16 @@ __device__ __forceinline__ void dma2(i4v rsrc, unsigned voffset_bytes, unsigned 
 
 // ---- shared by the launchers (one translation unit per kernel family) and the host code of gemm.hip -------------------------------
 #define TF_PATCH_PPW 9     // patch pieces per loader wave at most (33 pieces: BM = 128, W = 64)
+// The form of k_igemm a launch of the bm x bn tile runs when the deep ring (0), the wide ring (1) or the all-8 ring (3: the `variant` numbers of
+// gemm_family.h) was asked for: the all-8 ring exists for channel counts on the 64 grid, the wide ring for every tile but 128 x 160 (its epilogue
+// scratch leaves one block per CU) and 256 x 128, which has the deep ring only; what does not exist runs the deep ring.  launch_cfg dispatches on
+// it and tf_gemm_ring_form answers with it.
+constexpr bool igemm_wide_ok(int bm, int bn) { return !(bm == 128 && bn == 160) && bm != 256; }
+static inline int igemm_ring_form(int bm, int bn, bool wide, bool all8, bool generic) {
+  if (bm == 256) return 0;
+  if (all8 && !generic) return 3;
+  return wide && igemm_wide_ok(bm, bn) ? 1 : 0;
+}
 static inline bool gemm_generic(const GemmP& p) { return (p.C1 % 64) != 0 || (p.C2 % 64) != 0 || (p.C3 % 64) != 0 || (p.C4 % 64) != 0; }
 static inline int gi_table_bytes(const GemmP& p) { return p.gi_part ? (p.gi_G + p.C) * 8 : 0; }
 // LDS of a k_igemm<bm, bn> launch without the gi table (ring or epilogue scratch, whichever is larger)

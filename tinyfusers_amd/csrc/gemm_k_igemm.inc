@@ -37,8 +37,10 @@ static int launch_cfg3(const GemmP& p, hipStream_t st) {
 }
 template <int BM, int BN, bool WIDE_OK>
 static int launch_cfg(const GemmP& p, hipStream_t st, bool wide, bool all8 = false) {
+  static_assert(WIDE_OK == igemm_wide_ok(BM, BN), "the instantiated wide forms and igemm_wide_ok disagree");
   bool generic = gemm_generic(p);
-  if (all8 && !generic) return launch_cfg3<BM, BN, false, false, true>(p, st);
-  if (WIDE_OK && wide) return generic ? launch_cfg3<BM, BN, true, WIDE_OK>(p, st) : launch_cfg3<BM, BN, false, WIDE_OK>(p, st);
+  const int form = igemm_ring_form(BM, BN, wide, all8, generic);     // (gemm_common.h: the rule tf_gemm_ring_form answers with)
+  if (form == 3) return launch_cfg3<BM, BN, false, false, true>(p, st);
+  if (WIDE_OK && form == 1) return generic ? launch_cfg3<BM, BN, true, WIDE_OK>(p, st) : launch_cfg3<BM, BN, false, WIDE_OK>(p, st);
   return generic ? launch_cfg3<BM, BN, true, false>(p, st) : launch_cfg3<BM, BN, false, false>(p, st);
 }
