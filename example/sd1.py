@@ -14,6 +14,7 @@ BASELINE config 3: full 50-step sampler, batch 1, end-to-end img/s.
     python -m example.sd1 --steps 20 --sampler dpmpp2m --concat edit --cond-image x.npy [--image-guidance 1.5]   # InstructPix2Pix (8 channels)
     python -m example.sd1 --steps 20 --sampler dpmpp2m --control-image edges.npy [--control-ckpt control_v11p_sd15_canny.safetensors] [--control-scale 1.0]   # ControlNet
     python -m example.sd1 --steps 20 --sampler dpmpp2m --lora style.safetensors:0.8 --lora lcm.safetensors:1:0   # LoRA adapters, FILE[:w[:w_te]], merged on the device
+    python -m example.sd1 --steps 4 --sampler lcm --no-cfg --lora lcm.safetensors:1:0   # few-step sampling: the LCM sampler on the guidance-free single-branch step
 With --ckpt the configuration is read off the checkpoint's conv_in (4, 9 or 8 input channels); --concat picks it on synthetic weights.
 """
 import argparse
@@ -35,8 +36,11 @@ if __name__ == "__main__":
     ap.add_argument("--ckpt", default="", help="LDM checkpoint (.ckpt torch zip or .safetensors); default: synthetic weights")
     ap.add_argument("--vocab", default="", help="local bpe_simple_vocab_16e6.txt.gz for the prompt; default: seeded token ids")
     ap.add_argument("--prompt", default="a horse sized cat eating a bagel")
-    ap.add_argument("--sampler", choices=["ddim", "ddim-eta", "dpmpp2m", "euler-a"], default=None,
+    ap.add_argument("--sampler", choices=["ddim", "ddim-eta", "dpmpp2m", "euler-a", "lcm"], default=None,
                     help="run a sampler schedule (variants/samplers.py) with device-side noise from --seed; default: the reference's DDIM loop")
+    ap.add_argument("--no-cfg", action="store_true",
+                    help="with --sampler: the guidance-free step (compile(..., cfg=False)): one guidance branch, --guidance is not used and the unconditional "
+                         "prompt is not encoded -- how an LCM / LCM-LoRA samples (guidance 1)")
     ap.add_argument("--eta", type=float, default=None, help="noise scale of ddim-eta (default 1) and euler-a (default 1)")
     ap.add_argument("--init-image", default="", help="image-to-image from this (H,W,3) uint8 image: .npy, or .png / .jpg through PIL")
     ap.add_argument("--strength", type=float, default=None, help="with --init-image: the part of the schedule that runs, in (0, 1] (default 0.6)")
@@ -71,6 +75,10 @@ if __name__ == "__main__":
         if ws is None or not parts[0]:
             ap.error(f"--lora {spec}: expected FILE[:w[:w_te]]")
         loras.append((":".join(parts[:cut]), ws[0] if ws else 1.0, ws[1] if len(ws) > 1 else (ws[0] if ws else 1.0)))
+    if args.no_cfg and not args.sampler:
+        ap.error("--no-cfg needs --sampler")
+    if args.no_cfg and args.concat == "edit":
+        ap.error("--no-cfg on an InstructPix2Pix checkpoint is not supported (its update is defined by three guidance branches)")
     if (args.control_ckpt or args.control_scale is not None) and not args.control_image:
         ap.error("--control-ckpt and --control-scale need --control-image")
     if args.control_image and not args.sampler:
@@ -112,6 +120,8 @@ if __name__ == "__main__":
             ap.error(f"{what} runs with --sampler")
         if not args.cond_image or (concat == "inpaint" and not args.cond_mask):
             ap.error(f"{what} needs --cond-image" + (" and --cond-mask" if concat == "inpaint" else "") + ": its UNet reads them at every step")
+        if args.no_cfg and concat == "edit":
+            ap.error("--no-cfg on an InstructPix2Pix checkpoint is not supported (its update is defined by three guidance branches)")
         if args.mask:
             ap.error("--mask (the latent blend) on top of a concat-conditioned checkpoint is not supported; use --cond-mask")
     if concat and args.control_image:
@@ -163,9 +173,10 @@ if __name__ == "__main__":
     T.hip.tf_stream_sync(None)
     t0 = time.perf_counter()
     context = text_model(prompt)
-    unconditional_context = text_model(empty)
+    unconditional_context = None if args.no_cfg else text_model(empty)       # (the guidance-free step reads the prompt alone)
     T.hip.tf_stream_sync(None)
-    print(f"CLIP context: {context.shape}, unconditional CLIP context: {unconditional_context.shape}  ({1e3 * (time.perf_counter() - t0):.2f} ms for both)")
+    print(f"CLIP context: {context.shape}, " + ("no unconditional context (--no-cfg)" if args.no_cfg else f"unconditional CLIP context: {unconditional_context.shape}")
+          + f"  ({1e3 * (time.perf_counter() - t0):.2f} ms)")
     timesteps = list(range(1, 1000, 1000 // args.steps))
     alphas = model.alphas_cumprod[timesteps]
     alphas_prev = np.concatenate((np.array([1.0]), alphas[:-1])).astype(np.float32)
@@ -220,7 +231,8 @@ if __name__ == "__main__":
         schedule = make(args.sampler, args.eta).schedule(args.steps, strength=strength)
         print(f"sampler {schedule.sampler}: {len(schedule.timesteps)} steps, timesteps {schedule.timesteps[0]} .. {schedule.timesteps[-1]}"
               + (f" (strength {strength}{', inpainting' if mask is not None else ''})" if init_image is not None else ""))
-        model.compile(unconditional_context, context, latent, sampler=schedule, inpaint=mask is not None, concat=concat, control=bool(args.control_image))
+        model.compile(unconditional_context, context, latent, sampler=schedule, inpaint=mask is not None, concat=concat, control=bool(args.control_image),
+                      cfg=not args.no_cfg)
     else:
         model.compile(unconditional_context, context, latent)
     times = []
@@ -240,7 +252,7 @@ if __name__ == "__main__":
             model.set_latent(synth_normal(args.seed + n, "sd.latent", (1, 4, 64, 64)))
         t0 = time.perf_counter()
         if args.sampler:
-            model.run(args.guidance)
+            model.run(None if args.no_cfg else args.guidance)
         else:
             for index, timestep in list(enumerate(timesteps))[::-1]:
                 model.step(timestep, alphas[index], alphas_prev[index], args.guidance)

@@ -545,6 +545,24 @@ int tf_cfg_sampler_step_masked_f32(void* latent, const void* eps2, void* x0_hist
 int tf_cfg_sampler_step_masked_bf16(void* latent, const void* eps2, void* x0_hist, const void* step_params, const void* coeffs, int rows, const void* x0_init,
                                     const void* mask, int B, int C, int H, int W, tfStream_t s);
 
+/* ---- the guidance-free step (csrc/single.hip; variants/sd.py compile(..., cfg=False)): ONE guidance group instead of the CFG pair of
+ * variants/sd.py:31 and :44 -- what a consistency model (LCM, LCM-LoRA) samples with at guidance 1, where e = e_u + 1 (e_c - e_u) = e_c and
+ * the unconditional half of every launch is thrown away.  The opening and the closing launch of the captured step; the UNet between them
+ * runs on B images against the context alone. */
+/* latent (B,C,H,W) f32 NCHW [, cond (B,Cc,H,W) f32 NCHW] -> x (B, H, W, C+Cc) 16-bit NHWC: ONE guidance group.  cond == NULL iff Cc == 0.
+ * The latent channels are rounded exactly as tf_cfg_duplicate_* / tf_cfg_concat_* round them: x is their group 0, bit for bit. */
+int tf_latent_stack1_f16(void* x_out, const void* latent, const void* cond, int B, int C, int Cc, int H, int W, tfStream_t s);
+int tf_latent_stack1_bf16(void* x_out, const void* latent, const void* cond, int B, int C, int Cc, int H, int W, tfStream_t s);
+/* tf_cfg_sampler_step_* (variants/sd.py:14-25) without the CFG combine: e = eps (B,C,H,W NHWC 16-bit, ONE branch); then its expressions in its
+ * order: x0 = (x - sqrt(1-a_t) e)/sqrt(a_t); x' = c_x x + c_0 x0 + c_1 x0_prev + c_n z (tag 1, step = row); x0_prev <- x0.
+ * x0_init and mask both NULL: that is all.  Both set: then the blend of tf_cfg_sampler_step_masked_*
+ * (x' <- m x' + (1-m)(sqrt(a_s) x0_init + sqrt(1-a_s) z2), tag 2, always drawn).  Exactly one of them NULL: TF_E_ARG, bad arguments.
+ * x0_hist is read only when c_1 != 0, the tag-1 noise drawn only when c_n != 0; step_params[3] (guidance) is not read. */
+int tf_sampler_step1_f32(void* latent, const void* eps, void* x0_hist, const void* step_params, const void* coeffs, int rows, const void* x0_init, const void* mask,
+                         int B, int C, int H, int W, tfStream_t s);
+int tf_sampler_step1_bf16(void* latent, const void* eps, void* x0_hist, const void* step_params, const void* coeffs, int rows, const void* x0_init, const void* mask,
+                          int B, int C, int H, int W, tfStream_t s);
+
 /* ---- LoRA adapters (csrc/lora.hip; storage/lora.py, variants/sd.py:set_adapters): the reference has no adapters -- its weights come from
  * update_state alone (storage/checkpoint.py).  Every weight is a row matrix (N, Kd) of 16-bit elements: a Linear (out, in), a conv in KRSC
  * storage (K, R S C); an adapter of it is up (N, r) and down (r, Kd). */

@@ -65,10 +65,19 @@ def control_scales(control_scale, n_res):
     return scales
 
 
-def check_compile(cin, has_control_net, config, latent, sampler, inpaint, concat, control):
+def check_compile(cin, has_control_net, config, latent, sampler, inpaint, concat, control, cfg=True):
     """compile()'s refusals, before any device work: ``cin`` the UNet's in_channels, ``config`` the package's config module."""
     def refuse(exc, text):
         raise exc(f"StableDiffusion.compile: {text}")
+    if not cfg:
+        if sampler is None:
+            refuse(ValueError, "cfg=False needs a sampler schedule (sampler=<Schedule>): the reference-shaped step() keeps its CFG form")
+        if concat == "edit":
+            refuse(ValueError, "cfg=False and concat='edit' together are not supported (the InstructPix2Pix update is defined by its three guidance branches)")
+        if config.cfg_parallel:
+            refuse(UnsupportedSamplerConfig, "cfg=False has one guidance branch, so no two-chain CFG form (TF_CFG_PARALLEL)")
+        if config.dtype == "fp8":
+            refuse(UnsupportedSamplerConfig, "cfg=False runs in the fp16 and the bf16 step, not under the fp8 policy (config.set_dtype('fp8'))")
     if concat not in (None, "inpaint", "edit"):
         refuse(ValueError, f"concat= takes None, 'inpaint' or 'edit', got {concat!r}")
     if control:

@@ -13,6 +13,9 @@ once; the device kernel (tf_cfg_sampler_step_*, csrc/sampler.hip) is the same fo
   * EulerAncestral(eta) -- k-diffusion's sample_euler_ancestral (sigma_up / sigma_down) with sigma = sqrt((1 - a) / a), x_k = x / sqrt(a).
   * DPMSolverPP2M()    -- Lu et al. 2022, DPM-Solver++ Algorithm 2 (multistep, lambda = log(alpha / sigma)); the first step and a
                           step into sigma = 0 (a_s = 1, lambda = inf) are first order.
+  * LCM()              -- Luo et al. 2023, latent consistency models, multistep consistency sampling (Algorithm 3): the boundary-scaled
+                          x0 prediction is re-noised to the next level at every step.  Its scalings depend on the timestep, not on
+                          alpha-bar alone, and it walks its own timesteps (``Sampler.walk`` / ``Sampler.table`` are the two hooks).
 
 ``Sampler.schedule(steps)`` walks the reference's timesteps (example/sd1.py:54-57: range(1, 1000, 1000 // steps), high to low, a_prev = 1
 after the last step) and returns a ``Schedule`` that ``StableDiffusion.compile(..., sampler=...)`` captures; ``schedule(steps, strength=s)``
@@ -106,6 +109,35 @@ def dpmpp_2m_coefficients(alphas_cumprod):
     return out
 
 
+def lcm_timesteps(steps, original_steps=50):
+    """The walk of the multistep consistency sampler: ``steps`` of the ``original_steps`` timesteps the model was distilled on, k = N_TRAIN //
+    original_steps apart: t_i = k (original_steps - floor(i original_steps / steps)) - 1 -- with the defaults 999 - 20 floor(50 i / steps)."""
+    steps, original_steps = int(steps), int(original_steps)
+    if not 1 <= original_steps <= N_TRAIN:
+        raise ValueError(f"samplers: original_steps must lie in [1, {N_TRAIN}], got {original_steps}")
+    if not 1 <= steps <= original_steps:
+        raise ValueError(f"samplers: an LCM walk takes 1 to original_steps = {original_steps} steps, got {steps}")
+    k = N_TRAIN // original_steps
+    return [k * (original_steps - (i * original_steps) // steps) - 1 for i in range(steps)]
+
+
+def lcm_coefficients(alphas_cumprod, timesteps, timestep_scaling=10.0, sigma_data=0.5):
+    """(n, 4) float64 table of the multistep consistency sampler for the n steps of an alpha-bar sequence (walk order) at ``timesteps``.
+    With s = timestep_scaling t and sd = sigma_data: c_skip = sd^2 / (s^2 + sd^2), c_out = s / sqrt(s^2 + sd^2) (the boundary condition
+    f(x, 0) = x), denoised = c_skip x + c_out x0, x' = sqrt(a_s) denoised + sqrt(1 - a_s) z -- fresh noise at every step but the last."""
+    a = _abar(alphas_cumprod)
+    t = np.asarray(timesteps, dtype=np.float64).reshape(-1)
+    if t.size != a.size - 1:
+        raise ValueError(f"samplers: {t.size} timesteps for the {a.size - 1} steps of the alpha-bar sequence")
+    timestep_scaling, sigma_data = float(timestep_scaling), float(sigma_data)
+    if not (np.isfinite(timestep_scaling) and timestep_scaling > 0.0 and np.isfinite(sigma_data) and sigma_data > 0.0):
+        raise ValueError(f"samplers: timestep_scaling and sigma_data must be finite and > 0, got {timestep_scaling}, {sigma_data}")
+    s, sd2 = timestep_scaling * t, sigma_data * sigma_data
+    c_skip, c_out = sd2 / (s * s + sd2), s / np.sqrt(s * s + sd2)
+    a_s = a[1:]
+    return np.stack([np.sqrt(a_s) * c_skip, np.sqrt(a_s) * c_out, np.zeros_like(a_s), np.sqrt(1.0 - a_s)], axis=1)
+
+
 def get_alphas_cumprod(beta_start=0.00085, beta_end=0.0120, n_training_steps=N_TRAIN):
     """variants/sd.py:61-65 (host fp32: a 1000-entry table, not device work)."""
     betas = np.linspace(beta_start ** 0.5, beta_end ** 0.5, n_training_steps, dtype=np.float32) ** 2
@@ -149,14 +181,23 @@ class Sampler:
     def coefficients(self, alphas_cumprod):
         raise NotImplementedError
 
+    def walk(self, steps):
+        """The timesteps this sampler walks by default for ``steps`` steps (high to low): example/sd1.py:54's."""
+        return default_timesteps(steps)
+
+    def table(self, alphas_cumprod, timesteps):
+        """The coefficient table of the kept walk: ``coefficients`` of its alpha-bar sequence; a sampler whose update depends on the timestep
+        itself (LCM) reads ``timesteps`` too."""
+        return self.coefficients(alphas_cumprod)
+
     def schedule(self, steps=None, timesteps=None, alphas_cumprod=None, strength=1.0):
-        """The walk: timesteps (default example/sd1.py:54-57's for ``steps``), the alpha-bar pairs (a_prev = 1 after the last step) and the
+        """The walk: timesteps (default ``walk(steps)``: example/sd1.py:54-57's, LCM its own), the alpha-bar pairs (a_prev = 1 after the last step) and the
         coefficient table.  ``alphas_cumprod``: the 1000-entry training table (default variants/sd.py:61-65's, fp32 like the reference's).
         ``strength`` in (0, 1]: image-to-image (SDEdit) keeps the last max(1, floor(n strength)) steps of the n-step walk, and the table is
         built on that truncated walk (DPM-Solver++(2M)'s first kept step is first order).  An img2img run starts at level ``alphas[0]``."""
         strength = _check_strength(strength)
         if timesteps is None:
-            timesteps = default_timesteps(self.default_steps if steps is None else steps)
+            timesteps = self.walk(self.default_steps if steps is None else steps)
         elif steps is not None and int(steps) != len(timesteps):
             raise ValueError("samplers: pass steps or timesteps, not both")
         ts = _check_timesteps(timesteps)
@@ -164,7 +205,7 @@ class Sampler:
         walk = np.concatenate([ac[ts], [1.0]])
         first = len(ts) - max(1, math.floor(len(ts) * strength))
         ts, walk = ts[first:], walk[first:]
-        return Schedule(self, ts, walk[:-1].copy(), walk[1:].copy(), self.coefficients(walk))
+        return Schedule(self, ts, walk[:-1].copy(), walk[1:].copy(), self.table(walk, ts))
 
     def __repr__(self):
         return f"{type(self).__name__}({', '.join(f'{k}={v}' for k, v in vars(self).items())})"
@@ -200,8 +241,29 @@ class DPMSolverPP2M(Sampler):
         return dpmpp_2m_coefficients(alphas_cumprod)
 
 
+class LCM(Sampler):
+    name = "lcm"
+    default_steps = 4
+    stochastic = True
+
+    def __init__(self, original_steps=50, timestep_scaling=10.0, sigma_data=0.5):
+        self.original_steps = int(original_steps)
+        self.timestep_scaling, self.sigma_data = float(timestep_scaling), float(sigma_data)
+        lcm_timesteps(1, self.original_steps)                           # (checks original_steps)
+        lcm_coefficients([0.5, 1.0], [1], self.timestep_scaling, self.sigma_data)     # (checks the two scalings)
+
+    def walk(self, steps):
+        return lcm_timesteps(steps, self.original_steps)
+
+    def coefficients(self, alphas_cumprod, timesteps):
+        return lcm_coefficients(alphas_cumprod, timesteps, self.timestep_scaling, self.sigma_data)
+
+    def table(self, alphas_cumprod, timesteps):
+        return self.coefficients(alphas_cumprod, timesteps)
+
+
 def make(name, eta=None):
-    """example/sd1.py's --sampler names: ddim, ddim-eta, dpmpp2m, euler-a."""
+    """example/sd1.py's --sampler names: ddim, ddim-eta, dpmpp2m, euler-a, lcm."""
     if name == "ddim":
         return DDIM(0.0 if eta is None else eta)
     if name == "ddim-eta":
@@ -210,4 +272,6 @@ def make(name, eta=None):
         return EulerAncestral(1.0 if eta is None else eta)
     if name == "dpmpp2m":
         return DPMSolverPP2M()
-    raise ValueError(f"unknown sampler {name!r} (ddim, ddim-eta, dpmpp2m, euler-a)")
+    if name == "lcm":
+        return LCM()
+    raise ValueError(f"unknown sampler {name!r} (ddim, ddim-eta, dpmpp2m, euler-a, lcm)")

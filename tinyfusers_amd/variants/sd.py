@@ -16,6 +16,8 @@ A ControlNet (vision/controlnet.py; ``attach_control``, ``compile(..., control=T
 runs inside the same captured step: its residuals enter the UNet's skip connections through one launch (tf_control_add_16).
 LoRA adapters (storage/lora.py; ``load_lora``, ``set_adapters``, ``adapters``, ``unload_lora``) are merged on the device into fresh weight buffers
 (tf_lora_merge_16, one launch per touched module, from the kept base weight); a compiled model re-captures its step.
+``compile(..., cfg=False)`` is the guidance-free step of few-step samplers (samplers.LCM with an LCM-LoRA): ONE guidance group -- the UNet runs
+on B images against the context alone, between tf_latent_stack1_* and tf_sampler_step1_* (csrc/single.hip).
 
 How the object is laid out.  Everything ``compile`` / ``start`` / ``set_context`` / ``set_adapters`` keep on the model is declared, with its
 "not compiled" value, in ``_reset_state``: ``__init__`` runs all of it, ``compile`` the per-compile part, so a re-compile with other flags drops the
@@ -246,6 +248,15 @@ class StableDiffusion:
         _entry16("tf_cfg_duplicate", "f16")(x2.ptr, latent.ptr, b, c, h, w, _sh())
         return x2
 
+    def _latent_stack1(self):
+        """variants/sd.py:31 for the guidance-free step (cfg=False): the latent once -- with the conditioning channels of concat="inpaint" behind
+        it -- NHWC in the step's 16-bit type."""
+        b, c, h, w = self._latent.shape
+        cc = self._cond.shape[1] if self._cond is not None else 0
+        x = DeviceArray.empty((b, c + cc, h, w), _step_dtype(), "nhwc")
+        _entry16("tf_latent_stack1", "f16")(x.ptr, self._latent.ptr, self._cond.ptr if cc else None, b, c, cc, h, w, _sh())
+        return x
+
     def _cfg_concat(self):
         """variants/sd.py:31 for a concat-conditioned UNet: [latent | cond] for every guidance group, NHWC in the step's 16-bit type; an edit
         model's first group (bit 0 of drop_bits) reads zeros in place of the conditioning."""
@@ -257,7 +268,7 @@ class StableDiffusion:
 
     @staticmethod
     def _stack_context(unconditional_context, context, groups=2):
-        """[unc ; ctx], or for the three guidance branches of an edit model [unc ; unc ; ctx]."""
+        """[unc ; ctx], or for the three guidance branches of an edit model [unc ; unc ; ctx]; one group (cfg=False): ctx alone, unc is not read."""
         b, t, d = context.shape
         ctx = DeviceArray.empty((groups * b, t, d), context.dtype, "row")
         for g in range(groups):
@@ -293,7 +304,8 @@ class StableDiffusion:
         return out
 
     # -- whole-step HIP graph ------------------------------------------------------------------------
-    def compile(self, unconditional_context, context, latent, stream=None, warmup=2, timesteps=None, sampler=None, inpaint=False, concat=None, control=False):
+    def compile(self, unconditional_context, context, latent, stream=None, warmup=2, timesteps=None, sampler=None, inpaint=False, concat=None, control=False,
+                cfg=True):
         """Capture one denoising step for these (static) buffers into a HIP graph.  Afterwards
         ``step(timestep, a_t, a_prev, guidance)`` updates ``latent`` in place with one graph launch.
 
@@ -330,17 +342,25 @@ class StableDiffusion:
         projection; its time-embedding row travels behind the UNet's in the one buffer the parameter launch copies.  Combines with ``inpaint=True``
         (the latent blend lives in the sampler tail); not with ``concat=``, TF_CFG_PARALLEL or the fp8 policy.
 
+        ``cfg=False`` (with a sampler only): the guidance-free step of a consistency model (samplers.LCM with an LCM-LoRA merged in), which samples at
+        guidance 1 where e = e_u + 1 (e_c - e_u) = e_c.  ONE guidance group: the captured step opens with tf_latent_stack1_* (the conditioning channels
+        of concat="inpaint" behind the latent), runs the UNet -- and a ControlNet, its hint embedding one group -- on B images against ``context`` alone,
+        hoisted K|V included, and ends in tf_sampler_step1_* (its masked form for inpaint=True): the launch count of the CFG step, half the rows in every
+        launch.  ``unconditional_context`` may be None here and in ``set_context`` (it is ignored if given); ``run`` / ``step_sampler`` take guidance
+        None or 1.0 and raise ValueError for anything else.  Not with concat="edit", TF_CFG_PARALLEL or the fp8 policy.  cfg=True with an LCM schedule
+        runs the two-branch step with that table (LCM-LoRA at guidance 1-2).
+
         The arguments are remembered: ``set_adapters`` (LoRA) on a compiled model swaps weight handles and calls ``compile`` again with the same ones."""
-        inputs.check_compile(self.model.diffusion_model.cfg.in_channels, self.control_model is not None, config, latent, sampler, inpaint, concat, control)
+        inputs.check_compile(self.model.diffusion_model.cfg.in_channels, self.control_model is not None, config, latent, sampler, inpaint, concat, control, cfg)
         if sampler is not None:
             timesteps = sampler.timesteps
         self._reset_state()
         self._compile_args = dict(unconditional_context=unconditional_context, context=context, latent=latent, warmup=warmup, timesteps=timesteps,
-                                  sampler=sampler, inpaint=inpaint, concat=concat, control=control)
+                                  sampler=sampler, inpaint=inpaint, concat=concat, control=control, cfg=cfg)
         self._stream = stream or Stream()
         self._latent, self._unc, self._ctx = latent, unconditional_context, context
         self._sched, self._inpaint, self._concat, self._control = sampler, bool(inpaint), concat, bool(control)
-        self._groups = 3 if concat == "edit" else 2
+        self._groups = 3 if concat == "edit" else 2 if cfg else 1
         if sampler is not None:
             with use_stream(self._stream):
                 self._alloc_sampler_buffers()
@@ -424,7 +444,7 @@ class StableDiffusion:
 
     def _eager_step(self, sp):
         """One step, launch by launch -- what ``_capture`` records: the stacked input, the UNet, the tail that updates the latent."""
-        x2 = self._cfg_concat() if self._concat else self._cfg_duplicate(self._latent)
+        x2 = self._latent_stack1() if self._groups == 1 else self._cfg_concat() if self._concat else self._cfg_duplicate(self._latent)
         outs = self._unet_two_chains(x2, sp) if config.cfg_parallel else (self._unet(x2, sp),)
         self._tail(sp, *outs[:2])
         self._keep = (x2,) + outs       # graph nodes reference these blocks: keep them out of the pool
@@ -460,12 +480,15 @@ class StableDiffusion:
 
     def _tail(self, sp, out, out_c=None):
         """The step's last launch, by mode: CFG combine + the DDIM update (from two chains: tf_cfg_ddim_step2_f32), or the sampler update of the
-        schedule's row -- three-branch for an edit model, masked for inpaint=True."""
+        schedule's row -- three-branch for an edit model, masked for inpaint=True, single-branch (tf_sampler_step1_*, both forms) for cfg=False."""
         lat, (b, c, h, w) = self._latent, self._latent.shape
         if out_c is not None:
             return hip.tf_cfg_ddim_step2_f32(lat.ptr, out.ptr, out_c.ptr, sp.dev.ptr, b, c, h, w, _sh())
         if self._sched is None:
             return _entry16("tf_cfg_ddim_step", "f32")(lat.ptr, out.ptr, sp.dev.ptr, b, c, h, w, _sh())
+        if self._groups == 1:
+            extra = (self._x0_init.ptr, self._mask.ptr) if self._inpaint else (None, None)
+            return _entry16("tf_sampler_step1", "f32")(lat.ptr, out.ptr, self._x0_hist.ptr, sp.dev.ptr, self._coeffs.ptr, len(self._sched.timesteps), *extra, b, c, h, w, _sh())
         stem, extra = ("tf_cfg3_sampler_step", (self._edit.ptr,)) if self._concat == "edit" else \
                       ("tf_cfg_sampler_step_masked", (self._x0_init.ptr, self._mask.ptr)) if self._inpaint else ("tf_cfg_sampler_step", ())
         _entry16(stem, "f32")(lat.ptr, out.ptr, self._x0_hist.ptr, sp.dev.ptr, self._coeffs.ptr, len(self._sched.timesteps), *extra, b, c, h, w, _sh())
@@ -751,10 +774,22 @@ class StableDiffusion:
             hip.tf_means_to_cond_f32(self._cond.ptr, means.ptr, b, h, w, 0.18215, 1, cc, _sh())
             self._cond_keep = keep + (dlm,)                                  # (referenced until the kernels have run)
 
-    def step_sampler(self, i, guidance, eager=False):
+    def _guidance(self, guidance, what):
+        """The guidance scale of ``run`` / ``step_sampler`` as a float; a model compiled with cfg=False takes None or 1.0 only."""
+        if self._groups != 1:
+            if guidance is None:
+                raise TypeError(f"StableDiffusion.{what}: a model compiled with cfg=True needs its guidance scale")
+            return float(guidance)
+        if guidance is not None and float(guidance) != 1.0:
+            raise ValueError(f"StableDiffusion.{what}: this model was compiled with cfg=False and has no guidance branch -- guidance is None or 1.0, got {guidance}")
+        return 1.0
+
+    def step_sampler(self, i, guidance=None, eager=False):
         """Step i of the compiled schedule (asynchronous, on the sampler stream): one parameter launch (timestep scalars, schedule row, seed and
-        -- hoisted -- the cached time-embedding row) and one graph replay, the same launches as ``step``."""
+        -- hoisted -- the cached time-embedding row) and one graph replay, the same launches as ``step``.  ``guidance``: the CFG scale; a model
+        compiled with cfg=False takes None or 1.0."""
         sched = self._require_sampler("step_sampler")
+        guidance = self._guidance(guidance, "step_sampler")
         self._require_started("step_sampler")
         n = len(sched.timesteps)
         i = int(i)
@@ -762,13 +797,14 @@ class StableDiffusion:
             raise IndexError(f"StableDiffusion.step_sampler: step {i} outside the schedule's {n} steps")
         t = sched.timesteps[i]
         self._advance(t, eager, lambda dst, src, nbytes: hip.tf_set_sampler_params(
-            self._params.dev.ptr, float(t), float(sched.alphas[i]), float(sched.alphas_prev[i]), float(guidance), i, self._seed[0], self._seed[1],
+            self._params.dev.ptr, float(t), float(sched.alphas[i]), float(sched.alphas_prev[i]), guidance, i, self._seed[0], self._seed[1],
             self._image_offset, dst, src, nbytes, _sh()))
         self._cursor = i + 1
 
-    def run(self, guidance, eager=False):
+    def run(self, guidance=None, eager=False):
         """Every remaining step of the schedule (all of them after ``start``); returns the latent (asynchronous: synchronize() to read it)."""
         sched = self._require_sampler("run")
+        guidance = self._guidance(guidance, "run")
         self._require_started("run")
         for i in range(self._cursor, len(sched.timesteps)):
             self.step_sampler(i, guidance, eager=eager)
@@ -819,7 +855,8 @@ class StableDiffusion:
 
     def set_context(self, unconditional_context, context):
         """New prompts for the compiled step: refresh the stacked context in place (the captured graph reads these buffers) and the
-        cross-attention K|V projection that was hoisted out of the step.  Ordered on the sampler stream."""
+        cross-attention K|V projection that was hoisted out of the step.  Ordered on the sampler stream.  A model compiled with cfg=False reads
+        ``context`` alone: ``unconditional_context`` may be None."""
         self._require_compiled("set_context")
         with use_stream(self._stream):
             new = self._stack_context(unconditional_context, context, self._groups)       # (in the step's 16-bit type)

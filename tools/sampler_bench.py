@@ -3,7 +3,7 @@
 tf_cfg_sampler_step_f32) against the DDIM step (tf_cfg_ddim_step_f32), 100 graph replays each, alternated over several rounds; and the
 config-3 end-to-end img/s (CLIP x2 -> steps -> VAE decode, batch 1) at 20 DPM++2M steps against 50 DDIM steps.
 
-    python tools/sampler_bench.py [--replays 100] [--rounds 5] [--images 3] [--dpm-steps 20] [--inpaint] [--concat inpaint|edit] [--control]
+    python tools/sampler_bench.py [--replays 100] [--rounds 5] [--images 3] [--dpm-steps 20] [--inpaint] [--concat inpaint|edit] [--control] [--lora] [--lcm]
 --inpaint adds the masked DPM++2M step (tf_cfg_sampler_step_masked_f32, a model compiled with inpaint=True on the same shape, half the
 latent repainted) to the alternation, and the VAE encoder's time for a 512^2 image (StableDiffusion.encode_image).
 --concat adds the DPM++2M step of a concat-conditioned UNet (SD15_INPAINT: 9 input channels, two CFG groups; SD15_EDIT: 8 input channels, three
@@ -16,6 +16,10 @@ alternation, the time of start(control_image=...) for a 512^2 hint (upload, x / 
 lora_merge_ms (one set_adapters on an uncompiled model, every launch, wall clock incl. the final sync), lora_merge_gb_s (base read + dst write
 over the launches' device time) next to add_16_gb_s, lora_recapture_ms (set_adapters on a compiled model minus the merge), lora_step_over_plain
 (the adapted DPM++2M step against the plain one) and host_merge_ms (the same merge in numpy float32 plus the upload).  No target is set for any.
+--lcm adds the guidance-free step (compile(..., cfg=False): one guidance group, UNet batch 1 instead of 2) to the alternation: the DPM++2M step with
+cfg=False (dpmpp2m_nocfg_step_ms) next to the cfg=True one of the same rounds, the LCM step in both modes (lcm_step_ms, lcm_nocfg_step_ms), the
+ratios with the rounds' own spread next to them, and the end-to-end img/s of 4 LCM steps with cfg=False (e2e_lcm4_nocfg: one CLIP pass, the
+sampler, the VAE decode) against the DPM++2M run.
 Prints one JSON line."""
 import argparse
 import contextlib
@@ -185,6 +189,7 @@ def main():
     ap.add_argument("--concat", choices=["inpaint", "edit"], default=None, help="also time the step of the 9-channel inpainting / 8-channel edit UNet against the plain one")
     ap.add_argument("--control", action="store_true", help="also time the ControlNet-conditioned step against the plain one, start(control_image=), and k_control_add")
     ap.add_argument("--lora", action="store_true", help="also time the LoRA merge (tf_lora_merge_16), the re-capture and the adapted step, for rank 16 and rank 128")
+    ap.add_argument("--lcm", action="store_true", help="also time the guidance-free step (cfg=False) against the CFG step for DPM++2M and LCM, and LCM-4 cfg=False end to end")
     args = ap.parse_args()
 
     import torch  # noqa: F401  (the weight arena is a torch allocation)
@@ -247,6 +252,17 @@ def main():
         ctl_m.attach_control(net).compile(unc, ctx, lat_e, sampler=dpm_sched, control=True)
         hint_img = np.random.default_rng(1).integers(0, 256, (1, 512, 512, 3), dtype=np.uint8)
         ctl_m.start(seed=1234, control_image=hint_img)
+    few = {}                                                               # --lcm: key -> (model, latent, schedule, guidance)
+    if args.lcm:
+        from tinyfusers_amd.variants.samplers import LCM
+        lcm_sched = LCM().schedule(4)
+        for key, sched, cfg_on in (("dpmpp2m_nocfg", dpm_sched, False), ("lcm", lcm_sched, True), ("lcm_nocfg", lcm_sched, False)):
+            m = StableDiffusion()
+            update_state(m.model.diffusion_model, state, "")
+            lat_f = m.latent_from_numpy(noise)
+            m.compile(unc if cfg_on else None, ctx, lat_f, sampler=sched, cfg=cfg_on)
+            m.start(seed=1234)
+            few[key] = (m, lat_f, sched, 7.5 if cfg_on else None)
     lat0 = T.DeviceArray.from_numpy(noise, np.float32, "row")
     ts, al, ap_ = ddim_sched.timesteps, ddim_sched.alphas, ddim_sched.alphas_prev
 
@@ -289,6 +305,18 @@ def main():
                 hip.tf_memcpy_async(lat_e.ptr, lat0.ptr, lat_e.nbytes, 3, ctl_m._stream.handle)
             ctl_m.step_sampler(i, 7.5)
 
+    def few_replays(key):
+        m, lat_f, sched, g = few[key]
+        k = len(sched.timesteps)
+
+        def replays(n):
+            for s in range(n):
+                i = s % k
+                if i == 0:
+                    hip.tf_memcpy_async(lat_f.ptr, lat0.ptr, lat_f.nbytes, 3, m._stream.handle)
+                m.step_sampler(i, g)
+        return replays
+
     def timed(model, fn, n):
         ev0, ev1, ms = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_float()
         hip.tf_event_create(ctypes.byref(ev0)); hip.tf_event_create(ctypes.byref(ev1))
@@ -313,6 +341,10 @@ def main():
     if args.control:
         ctl_replays(20)
         step_ms["dpmpp2m_control"] = []
+    few_fn = {k: few_replays(k) for k in few}
+    for k in few:
+        few_fn[k](20)
+        step_ms[k] = []
     for _ in range(args.rounds):
         step_ms["ddim"].append(timed(ddim_m, ddim_replays, args.replays))
         step_ms["dpmpp2m"].append(timed(dpm_m, dpm_replays, args.replays))
@@ -322,6 +354,8 @@ def main():
             step_ms[cat_key].append(timed(cat_m, cat_replays, args.replays))
         if args.control:
             step_ms["dpmpp2m_control"].append(timed(ctl_m, ctl_replays, args.replays))
+        for k in few:
+            step_ms[k].append(timed(few[k][0], few_fn[k], args.replays))
     med = {k: float(np.median(v)) for k, v in step_ms.items()}
     extra = {}
     if args.inpaint:
@@ -360,11 +394,20 @@ def main():
     if args.lora:
         extra.update(lora_bench(T, hip, timed, args, state, ddim_m, unc, ctx, noise, dpm_sched, dpm_m, dpm_replays, lat0))
 
-    def e2e(model, steps, sample):
+    if args.lcm:
+        spread = lambda k: (max(step_ms[k]) - min(step_ms[k])) / med[k]    # a run's own spread between rounds, relative to its median
+        for k in few:
+            assert np.isfinite(few[k][1].numpy()).all(), k
+        extra.update({"dpmpp2m_nocfg_step_ms": round(med["dpmpp2m_nocfg"], 4), "lcm_step_ms": round(med["lcm"], 4), "lcm_nocfg_step_ms": round(med["lcm_nocfg"], 4),
+                      "dpmpp2m_nocfg_over_cfg": round(med["dpmpp2m_nocfg"] / med["dpmpp2m"], 4), "lcm_nocfg_over_cfg": round(med["lcm_nocfg"] / med["lcm"], 4),
+                      "lcm_over_dpmpp2m": round(med["lcm"] / med["dpmpp2m"], 4),
+                      "round_spread": {k: round(spread(k), 4) for k in ("dpmpp2m", "dpmpp2m_nocfg", "lcm", "lcm_nocfg")}})
+
+    def e2e(model, steps, sample, uncond=True):
         recs = []
         for n in range(args.images + 1):
             t0 = time.perf_counter()
-            c, u = text_model(prompt), text_model(empty)
+            c, u = text_model(prompt), text_model(empty) if uncond else None      # (a cfg=False model encodes the prompt alone)
             hip.tf_stream_sync(None)
             t1 = time.perf_counter()
             model.set_context(u, c)
@@ -393,6 +436,14 @@ def main():
            "step_ms_per_round": {k: [round(x, 4) for x in v] for k, v in step_ms.items()},
            "e2e_ddim50": e2e(ddim_m, 50, ddim_sample), "e2e_dpmpp2m": e2e(dpm_m, len(dpm_sched.timesteps), dpm_sample)}
     out["e2e_speedup"] = round(out["e2e_dpmpp2m"]["img_per_s"] / out["e2e_ddim50"]["img_per_s"], 3)
+    if args.lcm:
+        lcm1_m = few["lcm_nocfg"][0]
+
+        def lcm_sample(n):
+            lcm1_m.start(seed=1234, image_offset=n)
+            lcm1_m.run()
+        out["e2e_lcm4_nocfg"] = e2e(lcm1_m, 4, lcm_sample, uncond=False)
+        out["e2e_lcm4_nocfg_over_dpmpp2m"] = round(out["e2e_lcm4_nocfg"]["img_per_s"] / out["e2e_dpmpp2m"]["img_per_s"], 3)
     print(json.dumps(out))
     del arena
 
