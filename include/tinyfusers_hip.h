@@ -165,6 +165,10 @@ int tf_prof_read_family(int family, double* ms, double* work, long long* launche
 /* element type of the split-K partial slabs a split GEMM hands to its reduce launch: 16 (default) = fp16 -- half the bytes of that seam,
  * accumulated in fp32 in split order by the reducer -- or 32 = fp32 (rounds 1-3) */
 int tf_gemm_splitk_partials(int bits);
+/* layout of the split-K partial slabs of the launches whose reduce also applies the GroupNorm (tf_conv2d_fused_norm_16 on k_igemm / k_igemm_patch,
+ * group width a multiple of 4): 1 (default) = group-major -- the (image, group) block one reducer block owns is one contiguous run per split, read
+ * 16 bytes per lane -- 0 = row-major M x N like every other split launch.  Same results bit for bit; the workspace size does not change */
+int tf_gemm_splitk_slab_layout(int group_major);
 /* test / tuning hook: force the GEMM tile (bm x bn in {256,128,64} x {256,160,128,64}) and split-K; 0,0,0 = heuristic */
 int tf_gemm_force_config(int bm, int bn, int splitk);
 /* per-shape choice of (tile, split-K, ring variant).  mode 1 (default): a shape that is not in the table is timed on its first eager

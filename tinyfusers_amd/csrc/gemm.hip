@@ -295,6 +295,12 @@ int tf_gemm_splitk_partials(int bits) {
   g_part16 = bits == 16;
   return TF_OK;
 }
+// layout of the split-K partial slabs of the launches k_splitk_reduce_gn_apply finishes: 1 = group-major (default), 0 = row-major like every other launch
+int tf_gemm_splitk_slab_layout(int group_major) {
+  TF_REQUIRE(group_major == 0 || group_major == 1, "tf_gemm_splitk_slab_layout: group_major=%d (0 or 1)", group_major);
+  g_slab_gm = group_major;
+  return TF_OK;
+}
 int tf_gemm_force_config(int bm, int bn, int splitk) { g_force_bm = bm; g_force_bn = bn; g_force_split = splitk; return TF_OK; }
 
 // ---- launch descriptors: a conv / linear entry gets its GemmP from one of the two builders below (linear_problem, conv_problem) and then sets

@@ -90,6 +90,12 @@ struct GemmP {
   // q k^T scores of the unfused attention path, which must not be rounded to fp16 before the softmax; NULL = off
   float* out32;
   int c4_chunk;         // k_gemm_c4: consecutive tiles a block takes before it strides on by gridDim chunks (launch_c4)
+  // the split-K partial slabs are GROUP-MAJOR (launch_one sets it where k_splitk_reduce_gn_apply finishes the launch and the kernel family's
+  // epilogue implements it: k_igemm / k_igemm_patch): element (m, n) of split z lives at z M N + ((img G + g) HoWo + r) cpg + (n - g cpg), img = m /
+  // HoWo, r = m - img HoWo, g = n / cpg (G = gn_G, cpg = gn_cpg, cpg % 4 == 0) -- the (image, group) block a reducer block owns is one contiguous run
+  // of HoWo cpg elements per split instead of cpg-wide pieces at row stride.  0: row-major M x N slabs.  dv_cpg_*: n / cpg without a divide
+  int slab_gm;
+  unsigned dv_cpg_mul, dv_cpg_shr;
 #if TF_IGEMM_STAMP
   unsigned long long* stamp;   // diagnostic build only (tools/igemm_stamp.py): [block][8] s_memrealtime phase stamps of k_igemm, never in the shipped library
 #endif
@@ -416,7 +422,7 @@ __device__ __forceinline__ void igemm_epilogue_prefetch(const GemmP& p, int m0, 
 // all 8 waves: wave (w4, half) stores rows [half*TM/2, (half+1)*TM/2) of consumer w4's tile
 // LB: bias and the time embedding (bias_nc) come from an fp32 LDS table `lb` the kernel filled for its tile ([0][BN]: bias, [1 + i][BN]:
 //   bias_nc of image lb_img0 + i, i < 2) instead of per-item global loads -- the only loads left in the epilogue are the residual's.
-template <int BM, int BN, int OUT8 = 0, bool BF = false, int KBMAX = 4, bool LB = false, bool PRE = false>     // PRE: the first batch of loads arrives in `pre` (igemm_epilogue_prefetch); OUT8: the output is stored as e4m3 -- 1: at scale 1 (k_igemm8), 2: block scaled (k_igemm_pp, GEGLU only: codes, then the E8M0 bytes behind the M x N/2 codes) -- a template parameter keeps it out of the fp16 kernels; BF: bias / residual / output are bfloat16; KBMAX: items whose loads are in flight together
+template <int BM, int BN, int OUT8 = 0, bool BF = false, int KBMAX = 4, bool LB = false, bool PRE = false, bool GM = false>     // GM: the split branch can write group-major slabs (GemmP::slab_gm; k_igemm / k_igemm_patch only -- no other kernel instantiates the hook); PRE: the first batch of loads arrives in `pre` (igemm_epilogue_prefetch); OUT8: the output is stored as e4m3 -- 1: at scale 1 (k_igemm8), 2: block scaled (k_igemm_pp, GEGLU only: codes, then the E8M0 bytes behind the M x N/2 codes) -- a template parameter keeps it out of the fp16 kernels; BF: bias / residual / output are bfloat16; KBMAX: items whose loads are in flight together
 __device__ __forceinline__ void igemm_epilogue(const GemmP& p, char* smem, int m0, int n0, int split, int w4, int half, int lane, const float* lb = nullptr, int lb_n0 = 0, int lb_m1 = 0,
                                                const EpiPre<BM, BN, KBMAX>& pre = EpiPre<BM, BN, KBMAX>()) {
   typedef typename std::conditional<BF, bf16_t, half_t>::type E;
@@ -574,17 +580,32 @@ __device__ __forceinline__ void igemm_epilogue(const GemmP& p, char* smem, int m
     if (m >= p.M || n >= p.N) continue;
     const float* r = sc + row * RS + c8 * 8;
     f4 v0 = *reinterpret_cast<const f4*>(r), v1 = *reinterpret_cast<const f4*>(r + 4);
-    const long long o = (long long)m * p.N + n;
+    long long o = (long long)m * p.N + n, o1 = o + 4;       // the item's two quads: row-major neighbours
+    bool one16 = true;                                      // ... that one 16-byte store covers (fp16 slabs)
+    if constexpr (GM) {
+      if (p.slab_gm) {                                      // group-major slab (N % 8 == 0, cpg % 4 == 0): a quad never straddles a group; an 8-wide item does where cpg % 8 != 0
+        // ((img G + g) HoWo + r) cpg + (n - g cpg) = m cpg + n + img HoWo (N - cpg) + g (HoWo - 1) cpg, in 32 bits (M N < 2^31: launch_one); the two
+        // products on the right are wave-uniform factors times a small quotient
+        const unsigned cpg = (unsigned)p.gn_cpg, ga = (unsigned)p.HoWo * ((unsigned)p.N - cpg), gb = ((unsigned)p.HoWo - 1u) * cpg;
+        const unsigned img = (unsigned)fast_div(m, p.dv_howo_mul, p.dv_howo_shr), g = (unsigned)fast_div(n, p.dv_cpg_mul, p.dv_cpg_shr);
+        const unsigned o32 = (unsigned)m * cpg + (unsigned)n + img * ga + g * gb;
+        o = o32; o1 = o32 + 4u;
+        one16 = (cpg & 7u) == 0;                            // (cpg % 8 != 0: the row's run starts on an 8-byte boundary only -- two 4-wide items)
+        if (!one16 && (unsigned)n + 4u - g * cpg >= cpg) o1 = o32 + 4u + gb;   // the second quad opens the next group: the same row of the next (image, group) block
+      }
+    }
     if (part && p.part16 && p.splitk > 1) {                 // fp16 slab (N % 8 == 0: one 16-byte store per item)
       // (a partial is a SUB-sum: it may exceed fp16's range where the full sum does not, and (half_t) does not saturate -- clamp, so that an
       // out-of-range partial costs accuracy, not an inf / NaN in y; the bfloat16 launches keep fp32 slabs: launch_one)
       h8 hv;
       for (int e = 0; e < 4; ++e) { hv[e] = (half_t)__builtin_fminf(__builtin_fmaxf(v0[e], -65504.0f), 65504.0f); hv[4 + e] = (half_t)__builtin_fminf(__builtin_fmaxf(v1[e], -65504.0f), 65504.0f); }
-      *reinterpret_cast<h8*>(reinterpret_cast<half_t*>(p.partial) + (long long)split * p.M * p.N + o) = hv;
+      half_t* hp = reinterpret_cast<half_t*>(p.partial) + (long long)split * p.M * p.N;
+      if (!GM || one16) *reinterpret_cast<h8*>(hp + o) = hv;
+      else { *reinterpret_cast<h4*>(hp + o) = (h4){hv[0], hv[1], hv[2], hv[3]}; *reinterpret_cast<h4*>(hp + o1) = (h4){hv[4], hv[5], hv[6], hv[7]}; }
       continue;
     }
     if (part) {
-      if (vec) { *reinterpret_cast<f4*>(part + o) = v0; *reinterpret_cast<f4*>(part + o + 4) = v1; }
+      if (vec) { *reinterpret_cast<f4*>(part + o) = v0; *reinterpret_cast<f4*>(part + o1) = v1; }
       else { for (int e = 0; e < 8 && n + e < p.N; ++e) part[o + e] = e < 4 ? v0[e] : v1[e - 4]; }
       continue;
     }

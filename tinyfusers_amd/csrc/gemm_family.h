@@ -20,6 +20,7 @@ enum Variant {
 struct TileCfg { int bm, bn, splitk; };
 
 static int g_part16 = 1;                                  // split-K partial slabs in fp16 (tf_gemm_splitk_partials: 16 / 32)
+static int g_slab_gm = 1;                                 // group-major split-K slabs where the fused reduce finishes the launch (tf_gemm_splitk_slab_layout: 0 / 1)
 static int g_pp_np = 0;                                    // test / tuning hook: 0 = default phases per K tile, 2 = one phase per k-step where the tile has both forms
 
 // GroupNorm statistics from the producing conv: limits shared by the host entry, the tuner and the launches
@@ -196,6 +197,12 @@ static int launch_one(GemmP p, TileCfg c, int variant, int order, void* workspac
   p.splitk = (p.ktiles + p.ktiles_per_split - 1) / p.ktiles_per_split;
   p.partial = (float*)workspace;
   p.part16 = (g_part16 && !p.bf16 && p.splitk > 1 && (p.N & 7) == 0) ? 1 : 0;     // 16-byte rows segments of halves; other widths -- and the bfloat16 launches, whose partials may leave fp16's range -- keep fp32 slabs
+  // group-major slabs (GemmP::slab_gm): where k_splitk_reduce_gn_apply finishes the launch, a quad never straddles a group, and the family's epilogue
+  // writes the layout -- k_igemm in its ring forms and k_igemm_patch (fp16 / bfloat16 operands).  Every other family and reducer: row-major
+  const bool gm_family = (variant == V_RING || variant == V_WIDE || variant == V_PATCH || variant == V_ALL8) && !p.fp8;
+  p.slab_gm = (g_slab_gm && p.splitk > 1 && gm_family && p.on_z && p.gn_part && (p.gn_cpg & 3) == 0 && (long long)p.M * p.N < (1LL << 31) &&
+               tfk_splitk_reduce_applies_gn(p.HoWo, p.N, p.gn_G)) ? 1 : 0;      // (M N < 2^31: the epilogue forms the offset inside a slab in 32 bits)
+  if (p.slab_gm) fast_div_magic((unsigned)p.gn_cpg, &p.dv_cpg_mul, &p.dv_cpg_shr);
   p.ntm = (p.M + c.bm - 1) / c.bm;
   p.ntn = (p.N + c.bn - 1) / c.bn;
   float* gn_part = p.gn_part;

@@ -330,7 +330,7 @@ __global__ void __launch_bounds__(512, WIDE ? 4 : 2) k_igemm(const GemmP p) {
     }
     __builtin_amdgcn_s_barrier();                         // barrier Y: the consumers' tiles are in the LDS scratch
     asm volatile("" ::: "memory");
-    igemm_epilogue<BM, BN, false, BF, 4, false, EPRE>(p, smem, m0, n0, split, w4, 1, lane, nullptr, 0, 0, epre);
+    igemm_epilogue<BM, BN, false, BF, 4, false, EPRE, true>(p, smem, m0, n0, split, w4, 1, lane, nullptr, 0, 0, epre);
     if (p.gn_part) igemm_gn_stats<BM, BN>(p, smem, m0, n0, w4, 1, lane);
 #if TF_IGEMM_STAMP
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -563,7 +563,7 @@ __global__ void __launch_bounds__(512, WIDE ? 4 : 2) k_igemm(const GemmP p) {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                           // barrier Y
   asm volatile("" ::: "memory");
-  igemm_epilogue<BM, BN, false, BF, 4, false, EPRE>(p, smem, m0, n0, split, w4, 0, lane, nullptr, 0, 0, epre);
+  igemm_epilogue<BM, BN, false, BF, 4, false, EPRE, true>(p, smem, m0, n0, split, w4, 0, lane, nullptr, 0, 0, epre);
   if (p.gn_part) igemm_gn_stats<BM, BN>(p, smem, m0, n0, w4, 0, lane);
 #if TF_IGEMM_STAMP
   IG_STAMP(stp2);

@@ -209,7 +209,7 @@ __global__ void __launch_bounds__(512, 2) k_igemm_patch(const GemmP p) {
     asm volatile("" ::: "memory");
     __builtin_amdgcn_s_barrier();                         // barrier Y: the consumers' tiles are in the LDS scratch
     asm volatile("" ::: "memory");
-    igemm_epilogue<BM, BN, 0, BF, 4, false, true>(p, smem, m0, n0, split, w4, 1, lane, nullptr, 0, 0, epre);
+    igemm_epilogue<BM, BN, 0, BF, 4, false, true, true>(p, smem, m0, n0, split, w4, 1, lane, nullptr, 0, 0, epre);
     if (p.gn_part) igemm_gn_stats<BM, BN>(p, smem, m0, n0, w4, 1, lane);
     return;
   }
@@ -307,6 +307,6 @@ __global__ void __launch_bounds__(512, 2) k_igemm_patch(const GemmP p) {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                           // barrier Y
   asm volatile("" ::: "memory");
-  igemm_epilogue<BM, BN, 0, BF, 4, false, true>(p, smem, m0, n0, split, w4, 0, lane, nullptr, 0, 0, epre);
+  igemm_epilogue<BM, BN, 0, BF, 4, false, true, true>(p, smem, m0, n0, split, w4, 0, lane, nullptr, 0, 0, epre);
   if (p.gn_part) igemm_gn_stats<BM, BN>(p, smem, m0, n0, w4, 0, lane);
 }

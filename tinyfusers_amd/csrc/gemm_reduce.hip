@@ -39,6 +39,27 @@ __device__ __forceinline__ f4 sum_partials(const PT* __restrict__ partial, long 
   if (sizeof(PT) == 2 && splitk > 8) return sum_partials_nb<PT, 16, VS>(partial, total, e0, splitk);
   return sum_partials_nb<PT, 8, VS>(partial, total, e0, splitk);
 }
+// Two neighbouring element quads of an fp16 slab with ONE 16-byte load per split (the group-major slabs of k_splitk_reduce_gn_apply: a wave
+// instruction covers 1 KiB = eight whole lines), each summed in split order exactly as sum_partials_nb sums one: the same adds in the same order.
+// At most 8 loads in flight: as many bytes as sum_partials' 16 of 8.
+template <int NB>
+__device__ __forceinline__ void sum_partials16_nb(const half_t* __restrict__ partial, long long total, long long e0, int splitk, f4& lo, f4& hi) {
+  for (int z0 = 0; z0 < splitk; z0 += NB) {
+    h8 u[NB];
+#pragma unroll
+    for (int i = 0; i < NB; ++i) u[i] = *reinterpret_cast<const h8*>(partial + (long long)min(z0 + i, splitk - 1) * total + e0);
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+      lo += z0 + i < splitk ? (f4){(float)u[i][0], (float)u[i][1], (float)u[i][2], (float)u[i][3]} : (f4){0.f, 0.f, 0.f, 0.f};
+      hi += z0 + i < splitk ? (f4){(float)u[i][4], (float)u[i][5], (float)u[i][6], (float)u[i][7]} : (f4){0.f, 0.f, 0.f, 0.f};
+    }
+  }
+}
+__device__ __forceinline__ void sum_partials16(const half_t* __restrict__ partial, long long total, long long e0, int splitk, f4& lo, f4& hi) {
+  if (splitk <= 2) return sum_partials16_nb<2>(partial, total, e0, splitk, lo, hi);
+  if (splitk <= 4) return sum_partials16_nb<4>(partial, total, e0, splitk, lo, hi);
+  return sum_partials16_nb<8>(partial, total, e0, splitk, lo, hi);
+}
 // split-K reduce + epilogue: y[m,n] = sum_z partial[z,m,n] + bias + bias_nc + residual   (N % 4 == 0 fast path)
 // BF: bias / bias_nc / residual / gamma / beta / y / z hold bfloat16 (containers as in gemm_common.h: e2f / f2e)
 template <typename PT, bool BF = false>
@@ -133,8 +154,13 @@ __global__ void __launch_bounds__(1024) k_splitk_reduce_gn(half_t* __restrict__ 
 // t % CV of rows t / CV + k * RPS (k < RGA_MAXR) in registers: partials summed in split order (8 loads in flight), + bias + bias_nc +
 // residual, rounded to fp16 (y, optional), per-channel sums in registers -> LDS -> fixed-order fold -> (mean, rstd) -> z = silu?(y a + b).
 // Also leaves the (sum, sum of squares) of every group as a one-chunk partial table, so y.gn stays available to later consumers.
+// GM (GemmP::slab_gm, gpb == 1): the slabs are group-major -- the block's partials are ONE run of HoWo cpg elements per split, and quad v of row
+// rl + k RPS is quad t + k RPS CV of that run: consecutive lanes, consecutive quads.  GM == 1 loads a quad per lane (fp32 slabs: 16 bytes).  GM == 2
+// (fp16 slabs; RPS CV and HoWo CV even): sweeps go in pairs (k, k + 1) -- the even lane of a lane pair loads 16 bytes = both lanes' quads of sweep k,
+// the odd lane both lanes' quads of sweep k + 1, each sums its two quads over the splits and the pair swaps one fp32 sum each way, so every lane
+// ends up with the very sums, added in the very order, it computes on its own under GM == 0 / 1: y, z and the table do not depend on GM.
 #define RGA_MAXR 8
-template <typename PT, bool BF = false>
+template <typename PT, bool BF = false, int GM = 0>
 __global__ void __launch_bounds__(1024) k_splitk_reduce_gn_apply(half_t* __restrict__ y, half_t* __restrict__ z, const PT* __restrict__ partial,
                                                                  const half_t* __restrict__ bias, const half_t* __restrict__ bias_nc,
                                                                  const half_t* __restrict__ residual, int M, int N, int HoWo, int splitk, long long bnc_stride,
@@ -159,15 +185,34 @@ __global__ void __launch_bounds__(1024) k_splitk_reduce_gn_apply(half_t* __restr
   }
   h4 out[RGA_MAXR];
   f4 cs = {0.f, 0.f, 0.f, 0.f}, cq = {0.f, 0.f, 0.f, 0.f};
+  const PT* const slab = partial + (long long)blockIdx.x * HoWo * cpg;   // GM: the block's run inside split 0's slab
+  const int S = RPS * CV;                                                  // GM: quads per sweep
+  f4 acc_next = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int k = 0; k < RGA_MAXR; ++k) {
     const int r = rl + k * RPS;
     out[k] = (h4){0, 0, 0, 0};
+    f4 acc_pair = acc_next;
+    if constexpr (GM == 2) {
+      if ((k & 1) == 0) {                                    // (outside every divergent branch: all 64 lanes take part in the swap)
+        const int odd = t & 1, q = (t - odd) + (k + odd) * S;
+        f4 lo = {0.f, 0.f, 0.f, 0.f}, hi = {0.f, 0.f, 0.f, 0.f};
+        if (act && q < HoWo * CV) sum_partials16(reinterpret_cast<const half_t*>(slab), total, 4LL * q, splitk, lo, hi);
+        const f4 send = odd ? lo : hi;
+        f4 recv;
+        for (int e = 0; e < 4; ++e) recv[e] = __shfl_xor(send[e], 1, 64);
+        acc_pair = odd ? recv : lo;
+        acc_next = odd ? hi : recv;
+      }
+    }
     if (act && r < HoWo) {
       const long long e0 = ((long long)img * HoWo + r) * N + n;
       h4 res = {0, 0, 0, 0};
       if (residual) res = *reinterpret_cast<const h4*>(residual + e0);
-      f4 acc = sum_partials<PT, false>(partial, total, e0, splitk);
+      f4 acc;
+      if constexpr (GM == 2) acc = acc_pair;
+      else if constexpr (GM == 1) acc = sum_partials<PT, false>(slab, total, 4LL * (t + k * S), splitk);
+      else acc = sum_partials<PT, false>(partial, total, e0, splitk);
       acc += bv;
       for (int e = 0; e < 4; ++e) acc[e] += e2f<BF>(bnc[e]);
       for (int e = 0; e < 4; ++e) acc[e] += e2f<BF>(res[e]);
@@ -272,14 +317,26 @@ int tfk_launch_splitk_reduce(const GemmP& p, hipStream_t st) {
       TF_HIP(hipFuncSetAttribute((const void*)k_splitk_reduce_gn_apply<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       TF_HIP(hipFuncSetAttribute((const void*)k_splitk_reduce_gn_apply<half_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       TF_HIP(hipFuncSetAttribute((const void*)k_splitk_reduce_gn_apply<float, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      TF_HIP(hipFuncSetAttribute((const void*)k_splitk_reduce_gn_apply<float, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      TF_HIP(hipFuncSetAttribute((const void*)k_splitk_reduce_gn_apply<half_t, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      TF_HIP(hipFuncSetAttribute((const void*)k_splitk_reduce_gn_apply<half_t, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      TF_HIP(hipFuncSetAttribute((const void*)k_splitk_reduce_gn_apply<float, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       attr_set = true;
     }
     const int nimg = p.M / p.HoWo;
-#define TF_RGA_LAUNCH(PT, BFV) hipLaunchKernelGGL((k_splitk_reduce_gn_apply<PT, BFV>), dim3(nimg * (p.gn_G / rg_gpb)), dim3(1024), rg_lds, st, p.y, p.on_z, (const PT*)p.partial, p.bias, p.bias_nc, \
+#define TF_RGA_LAUNCH(PT, BFV, GMV) hipLaunchKernelGGL((k_splitk_reduce_gn_apply<PT, BFV, GMV>), dim3(nimg * (p.gn_G / rg_gpb)), dim3(1024), rg_lds, st, p.y, p.on_z, (const PT*)p.partial, p.bias, p.bias_nc, \
                        p.residual, p.M, p.N, p.HoWo, p.splitk, p.bias_nc_stride, p.gn_part, p.gn_G, p.gn_cpg, rg_gpb, p.on_gamma, p.on_beta, p.on_eps, p.on_silu, rg_rps, rg_cv)
-    if (bf) TF_RGA_LAUNCH(float, true);
-    else if (p.part16) TF_RGA_LAUNCH(half_t, false);
-    else TF_RGA_LAUNCH(float, false);
+    if (p.slab_gm) {                                       // the layout the GEMM launch wrote (launch_one), never guessed here
+      if (rg_gpb != 1 || (p.gn_cpg & 3)) { tf_set_error("split-K reduce: group-major slabs with %d groups per block, group width %d", rg_gpb, p.gn_cpg); return TF_E_STATE; }
+      const bool pairs = ((rg_rps * rg_cv) & 1) == 0 && ((p.HoWo * rg_cv) & 1) == 0;   // 16-byte loads: every lane pair's two quads start on a 16-byte boundary
+      if (bf) TF_RGA_LAUNCH(float, true, 1);
+      else if (p.part16 && pairs) TF_RGA_LAUNCH(half_t, false, 2);
+      else if (p.part16) TF_RGA_LAUNCH(half_t, false, 1);
+      else TF_RGA_LAUNCH(float, false, 1);
+    }
+    else if (bf) TF_RGA_LAUNCH(float, true, 0);
+    else if (p.part16) TF_RGA_LAUNCH(half_t, false, 0);
+    else TF_RGA_LAUNCH(float, false, 0);
 #undef TF_RGA_LAUNCH
     TF_LAUNCH_CHECK();
     if (p.on_applied) *p.on_applied = 1;
