@@ -478,9 +478,12 @@ int tf_quick_gelu_f16(void* y, const void* x, long long n, tfStream_t s);
 int tf_embedding_f16(void* out, const void* table, const void* ids, const void* pos, long long n_tokens, int dim, int vocab,
                      int T, tfStream_t s);
 /* Debugging aid, no reference counterpart: *flag (device int) = 1 when the nbytes at x hold a non-finite f16 (is_f32 = 0) or f32
- * value.  Stream-ordered and capturable (tools/diag_graph.py instruments a whole step with it). */
+ * value.  Every element is looked at, the last one of an odd-length f16 array (nbytes % 4 == 2) included.  Stream-ordered and capturable
+ * (tools/diag_graph.py instruments a whole step with it). */
 int tf_debug_nonfinite(const void* x, long long nbytes, int is_f32, void* flag, tfStream_t s);
-int tf_debug_checksum(const void* x, long long nbytes, void* sum, tfStream_t s);   /* *sum (device u64) += weighted word checksum of x */
+/* Debugging aid: *sum (device u64) += sum over i of word_i * ((uint32(i) * 2654435761) | 1) mod 2^64 over the nbytes / 4 WHOLE 32-bit words at x
+ * (order independent).  Trailing nbytes % 4 bytes are not part of the sum: pad an odd-length fp16 array to a word before comparing checksums. */
+int tf_debug_checksum(const void* x, long long nbytes, void* sum, tfStream_t s);
 int tf_geglu_f16(void* y, const void* x, int rows, int C, tfStream_t s);          /* x (rows,2C) -> y (rows,C) */
 int tf_add_f16(void* y, const void* a, const void* b, long long n, tfStream_t s);
 int tf_add_bias_nc_f16(void* y, const void* x, const void* bias_nc, int N, int HW, int C, tfStream_t s);

@@ -157,7 +157,13 @@ __global__ void __launch_bounds__(EW_BLOCK) k_im2col(half_t* __restrict__ y, con
 
 __global__ void __launch_bounds__(EW_BLOCK) k_scale_cast_f32_f16(half_t* __restrict__ y, const float* __restrict__ x, float sc, long long n) {
   long long gs = (long long)gridDim.x * EW_BLOCK;
-  for (long long i = (long long)blockIdx.x * EW_BLOCK + threadIdx.x; i < n; i += gs) y[i] = (half_t)(x[i] * sc);
+  for (long long i = (long long)blockIdx.x * EW_BLOCK + threadIdx.x; i < n; i += gs) {
+    float p = x[i] * sc;
+    // keep the product a value of its own: folded into the conversion it becomes v_fma_mixlo_f16(x, sc, +0), and -0 + +0 = +0 loses the sign of a
+    // zero product (fp16(-0.0f * 1.0f) must be -0)
+    asm volatile("" : "+v"(p));
+    y[i] = (half_t)p;
+  }
 }
 __global__ void __launch_bounds__(EW_BLOCK) k_cast_f32_f16(half_t* __restrict__ y, const float* __restrict__ x, long long n) {
   long long gs = (long long)gridDim.x * EW_BLOCK;
@@ -432,14 +438,14 @@ int tf_timestep_embedding_bf16(void* out, const void* step_params, int dim, floa
   return TF_OK;
 }
 int tf_cfg_duplicate_bf16(void* x2b, const void* latent, int B, int C, int H, int W, tfStream_t s) {
-  TF_REQUIRE(x2b && latent && B > 0 && C > 0, "tf_cfg_duplicate_bf16: bad arguments");
+  TF_REQUIRE(x2b && latent && B > 0 && C > 0 && H >= 0 && W >= 0, "tf_cfg_duplicate_bf16: bad arguments");
   long long n = (long long)B * C * H * W;
   hipLaunchKernelGGL(k_cfg_duplicate<bf16_t>, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, tf_hs(s), (bf16_t*)x2b, (const float*)latent, B, C, H * W);
   TF_LAUNCH_CHECK();
   return TF_OK;
 }
 int tf_cfg_ddim_step_bf16(void* latent, const void* eps2, const void* params, int B, int C, int H, int W, tfStream_t s) {
-  TF_REQUIRE(latent && eps2 && params && B > 0 && C > 0, "tf_cfg_ddim_step_bf16: bad arguments");
+  TF_REQUIRE(latent && eps2 && params && B > 0 && C > 0 && H >= 0 && W >= 0, "tf_cfg_ddim_step_bf16: bad arguments");
   long long n = (long long)B * C * H * W;
   hipLaunchKernelGGL(k_cfg_ddim<bf16_t>, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, tf_hs(s), (float*)latent, (const bf16_t*)eps2, (const bf16_t*)nullptr, (const float*)params, B, C, H * W);
   TF_LAUNCH_CHECK();
@@ -456,8 +462,10 @@ int tf_embedding_f16(void* out, const void* table, const void* ids, const void* 
 }
 // Debugging aid (no reference counterpart): *flag = 1 when x holds a non-finite value.  Stream-ordered and capturable, so a
 // whole step (eager or graph replay) can be instrumented without a host sync (tools/diag_graph.py).
-__global__ void k_debug_nonfinite(const unsigned* __restrict__ x, long long nwords, int is_f32, int* flag) {
+// `tail_half`: the array ends in one more fp16 element behind its last whole word (an odd element count) -- thread 0 looks at it.
+__global__ void k_debug_nonfinite(const unsigned* __restrict__ x, long long nwords, int is_f32, int tail_half, int* flag) {
   bool bad = false;
+  if (tail_half && blockIdx.x == 0 && threadIdx.x == 0) bad = (reinterpret_cast<const unsigned short*>(x)[2 * nwords] & 0x7c00u) == 0x7c00u;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < nwords; i += (long long)gridDim.x * blockDim.x) {
     unsigned v = x[i];
     bad |= is_f32 ? ((v & 0x7f800000u) == 0x7f800000u) : (((v & 0x7c00u) == 0x7c00u) || ((v & 0x7c000000u) == 0x7c000000u));
@@ -482,8 +490,9 @@ int tf_debug_checksum(const void* x, long long nbytes, void* sum, tfStream_t s) 
 }
 int tf_debug_nonfinite(const void* x, long long nbytes, int is_f32, void* flag, tfStream_t s) {
   TF_REQUIRE(x && flag && nbytes >= 0, "tf_debug_nonfinite: bad arguments");
-  if (nbytes < 4) return TF_OK;
-  hipLaunchKernelGGL(k_debug_nonfinite, dim3(ew_grid(nbytes / 4)), dim3(256), 0, tf_hs(s), (const unsigned*)x, nbytes / 4, is_f32, (int*)flag);
+  const int tail_half = !is_f32 && (nbytes & 2);          // an odd fp16 count: the last element is half a word
+  if (nbytes < 4 && !tail_half) return TF_OK;
+  hipLaunchKernelGGL(k_debug_nonfinite, dim3(ew_grid(nbytes / 4)), dim3(256), 0, tf_hs(s), (const unsigned*)x, nbytes / 4, is_f32, tail_half, (int*)flag);
   TF_LAUNCH_CHECK();
   return TF_OK;
 }
@@ -495,29 +504,30 @@ int tf_geglu_f16(void* y, const void* x, int rows, int C, tfStream_t s) {
   return TF_OK;
 }
 int tf_add_bias_nc_f16(void* y, const void* x, const void* b, int N, int HW, int C, tfStream_t s) {
-  TF_REQUIRE(y && x && b && C % 8 == 0, "tf_add_bias_nc_f16: C=%d must be a multiple of 8", C);
-  if ((long long)N * HW == 0) return TF_OK;
+  TF_REQUIRE(y && x && b && N >= 0 && HW >= 0 && C >= 0 && C % 8 == 0, "tf_add_bias_nc_f16: N=%d HW=%d must not be negative, C=%d a multiple of 8", N, HW, C);
+  if ((long long)N * HW * C == 0) return TF_OK;
   hipLaunchKernelGGL(k_add_bias_nc, dim3(ew_grid((long long)N * HW * (C >> 3))), dim3(EW_BLOCK), 0, tf_hs(s), (half_t*)y, (const half_t*)x, (const half_t*)b, N, (long long)HW, C);
   TF_LAUNCH_CHECK();
   return TF_OK;
 }
 int tf_upsample2x_nhwc_f16(void* y, const void* x, int N, int H, int W, int C, tfStream_t s) {
-  TF_REQUIRE(y && x && C % 8 == 0, "tf_upsample2x_nhwc_f16: C=%d must be a multiple of 8", C);
-  if ((long long)N * H * W == 0) return TF_OK;
+  TF_REQUIRE(y && x && N >= 0 && H >= 0 && W >= 0 && C >= 0 && C % 8 == 0, "tf_upsample2x_nhwc_f16: N=%d H=%d W=%d must not be negative, C=%d a multiple of 8", N, H, W, C);
+  if ((long long)N * H * W * C == 0) return TF_OK;
   hipLaunchKernelGGL(k_upsample2x, dim3(ew_grid((long long)N * 4 * H * W * (C >> 3))), dim3(EW_BLOCK), 0, tf_hs(s), (half_t*)y, (const half_t*)x, N, H, W, C);
   TF_LAUNCH_CHECK();
   return TF_OK;
 }
 int tf_concat_channels_f16(void* y, const void* a, const void* b, long long rows, int Ca, int Cb, tfStream_t s) {
-  TF_REQUIRE(y && a && b && Ca % 8 == 0 && Cb % 8 == 0, "tf_concat_channels_f16: Ca=%d Cb=%d must be multiples of 8", Ca, Cb);
-  if (rows == 0) return TF_OK;
+  TF_REQUIRE(y && a && b && rows >= 0 && Ca >= 0 && Cb >= 0 && Ca % 8 == 0 && Cb % 8 == 0, "tf_concat_channels_f16: rows=%lld must not be negative, Ca=%d Cb=%d multiples of 8", rows, Ca, Cb);
+  if (rows == 0 || Ca + Cb == 0) return TF_OK;
   hipLaunchKernelGGL(k_concat, dim3(ew_grid(rows * ((Ca + Cb) >> 3))), dim3(EW_BLOCK), 0, tf_hs(s), (half_t*)y, (const half_t*)a, (const half_t*)b, rows, Ca, Cb);
   TF_LAUNCH_CHECK();
   return TF_OK;
 }
 int tf_im2col_rows_nhwc_f16(void* y, const void* x, int N, int H, int W, int C, int R, int S, int stride, int pad, int Kpad, int ho_begin, int ho_end,
                             tfStream_t s) {
-  TF_REQUIRE(y && x && Kpad >= R * S * C && stride >= 1, "tf_im2col_rows_nhwc_f16: Kpad=%d < R*S*C=%d", Kpad, R * S * C);
+  TF_REQUIRE(y && x && N >= 0 && H >= 1 && W >= 1 && C >= 1 && R >= 1 && S >= 1 && pad >= 0, "tf_im2col_rows_nhwc_f16: bad arguments (N=%d H=%d W=%d C=%d R=%d S=%d pad=%d)", N, H, W, C, R, S, pad);
+  TF_REQUIRE(Kpad >= R * S * C && stride >= 1, "tf_im2col_rows_nhwc_f16: Kpad=%d < R*S*C=%d", Kpad, R * S * C);
   int Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - S) / stride + 1;
   TF_REQUIRE(ho_begin >= 0 && ho_begin <= ho_end && ho_end <= Ho, "tf_im2col_rows_nhwc_f16: rows [%d, %d) outside [0, %d)", ho_begin, ho_end, Ho);
   long long total = (long long)N * (ho_end - ho_begin) * Wo * Kpad;
@@ -553,7 +563,7 @@ int tf_cast_f16_to_f32(void* dst, const void* src, long long n, tfStream_t s) {
   return TF_OK;
 }
 int tf_nchw_f32_to_nhwc_f16(void* dst, const void* src, int N, int C, int H, int W, tfStream_t s) {
-  TF_REQUIRE(dst && src && N >= 0 && C > 0 && N <= 65535, "tf_nchw_f32_to_nhwc_f16: bad arguments");
+  TF_REQUIRE(dst && src && N >= 0 && C > 0 && H >= 0 && W >= 0 && N <= 65535, "tf_nchw_f32_to_nhwc_f16: bad arguments");
   int HW = H * W;
   if ((long long)N * HW == 0) return TF_OK;
   hipLaunchKernelGGL(k_nchw_to_nhwc, dim3(ceil_div(HW, 32), ceil_div(C, 32), N), dim3(256), 0, tf_hs(s), (half_t*)dst, (const float*)src, C, HW);
@@ -561,7 +571,7 @@ int tf_nchw_f32_to_nhwc_f16(void* dst, const void* src, int N, int C, int H, int
   return TF_OK;
 }
 int tf_nhwc_f16_to_nchw_f32(void* dst, const void* src, int N, int C, int H, int W, tfStream_t s) {
-  TF_REQUIRE(dst && src && N >= 0 && C > 0 && N <= 65535, "tf_nhwc_f16_to_nchw_f32: bad arguments");
+  TF_REQUIRE(dst && src && N >= 0 && C > 0 && H >= 0 && W >= 0 && N <= 65535, "tf_nhwc_f16_to_nchw_f32: bad arguments");
   int HW = H * W;
   if ((long long)N * HW == 0) return TF_OK;
   hipLaunchKernelGGL(k_nhwc_to_nchw, dim3(ceil_div(HW, 32), ceil_div(C, 32), N), dim3(256), 0, tf_hs(s), (float*)dst, (const half_t*)src, C, HW);
@@ -569,7 +579,7 @@ int tf_nhwc_f16_to_nchw_f32(void* dst, const void* src, int N, int C, int H, int
   return TF_OK;
 }
 int tf_nhwc_to_nchw_f16(void* dst, const void* src, int N, int C, int H, int W, tfStream_t s) {
-  TF_REQUIRE(dst && src && N >= 0 && N <= 65535 && C > 0, "tf_nhwc_to_nchw_f16: bad arguments");
+  TF_REQUIRE(dst && src && N >= 0 && N <= 65535 && C > 0 && H >= 0 && W >= 0, "tf_nhwc_to_nchw_f16: bad arguments");
   int HW = H * W;
   if ((long long)N * HW == 0) return TF_OK;
   hipLaunchKernelGGL(k_transpose_f16, dim3(ceil_div(C, 32), ceil_div(HW, 32), N), dim3(256), 0, tf_hs(s), (half_t*)dst, (const half_t*)src, HW, C);
@@ -577,7 +587,7 @@ int tf_nhwc_to_nchw_f16(void* dst, const void* src, int N, int C, int H, int W, 
   return TF_OK;
 }
 int tf_nchw_to_nhwc_f16(void* dst, const void* src, int N, int C, int H, int W, tfStream_t s) {
-  TF_REQUIRE(dst && src && N >= 0 && N <= 65535 && C > 0, "tf_nchw_to_nhwc_f16: bad arguments");
+  TF_REQUIRE(dst && src && N >= 0 && N <= 65535 && C > 0 && H >= 0 && W >= 0, "tf_nchw_to_nhwc_f16: bad arguments");
   int HW = H * W;
   if ((long long)N * HW == 0) return TF_OK;
   hipLaunchKernelGGL(k_transpose_f16, dim3(ceil_div(HW, 32), ceil_div(C, 32), N), dim3(256), 0, tf_hs(s), (half_t*)dst, (const half_t*)src, C, HW);
@@ -618,6 +628,7 @@ int tf_transpose_f32(void* out, const void* inp, int ndim, const int* shape, con
   TF_REQUIRE(out && inp && shape && axes && ndim >= 1 && ndim <= 4, "tf_transpose_f32: ndim=%d must be 1..4", ndim);
   long long istride[4], n = 1;
   bool seen[4] = {false, false, false, false};
+  for (int d = 0; d < ndim; ++d) TF_REQUIRE(shape[d] >= 0, "tf_transpose_f32: shape[%d]=%d", d, shape[d]);
   for (int d = ndim - 1, st = 1; d >= 0; --d) { istride[d] = n; n *= shape[d]; (void)st; }
   PermArgs a;
   a.ndim = ndim;
@@ -684,21 +695,21 @@ int tf_timestep_embedding_f16(void* out, const void* step_params, int dim, float
   return TF_OK;
 }
 int tf_cfg_duplicate_f16(void* x2b, const void* latent, int B, int C, int H, int W, tfStream_t s) {
-  TF_REQUIRE(x2b && latent && B > 0 && C > 0, "tf_cfg_duplicate_f16: bad arguments");
+  TF_REQUIRE(x2b && latent && B > 0 && C > 0 && H >= 0 && W >= 0, "tf_cfg_duplicate_f16: bad arguments");
   long long n = (long long)B * C * H * W;
   hipLaunchKernelGGL(k_cfg_duplicate<half_t>, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, tf_hs(s), (half_t*)x2b, (const float*)latent, B, C, H * W);
   TF_LAUNCH_CHECK();
   return TF_OK;
 }
 int tf_cfg_ddim_step_f32(void* latent, const void* eps2, const void* params, int B, int C, int H, int W, tfStream_t s) {
-  TF_REQUIRE(latent && eps2 && params && B > 0 && C > 0, "tf_cfg_ddim_step_f32: bad arguments");
+  TF_REQUIRE(latent && eps2 && params && B > 0 && C > 0 && H >= 0 && W >= 0, "tf_cfg_ddim_step_f32: bad arguments");
   long long n = (long long)B * C * H * W;
   hipLaunchKernelGGL(k_cfg_ddim<half_t>, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, tf_hs(s), (float*)latent, (const half_t*)eps2, (const half_t*)nullptr, (const float*)params, B, C, H * W);
   TF_LAUNCH_CHECK();
   return TF_OK;
 }
 int tf_cfg_ddim_step2_f32(void* latent, const void* eps_uncond, const void* eps_cond, const void* params, int B, int C, int H, int W, tfStream_t s) {
-  TF_REQUIRE(latent && eps_uncond && eps_cond && params && B > 0 && C > 0, "tf_cfg_ddim_step2_f32: bad arguments");
+  TF_REQUIRE(latent && eps_uncond && eps_cond && params && B > 0 && C > 0 && H >= 0 && W >= 0, "tf_cfg_ddim_step2_f32: bad arguments");
   long long n = (long long)B * C * H * W;
   hipLaunchKernelGGL(k_cfg_ddim<half_t>, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, tf_hs(s), (float*)latent, (const half_t*)eps_uncond, (const half_t*)eps_cond, (const float*)params, B, C, H * W);
   TF_LAUNCH_CHECK();
