@@ -234,6 +234,11 @@ size_t tf_conv2d_workspace(int N, int H, int W, int C1, int C2, int Cout, int R,
  *     (Cout, R*S*(C1+C2) + C3 + C4): each row = the KRSC conv row followed by the 1x1 row; bias = the sum of both biases.
  *     This is ResBlock's ``skip_connection(x) + h`` (:24, :31) computed inside its last conv instead of a separate
  *     Conv2d(1x1) launch plus a residual read.  Not combinable with upsample.
+ *     With stride > 1 the contract is: x3 | x4 are N x H x W tensors (the INPUT resolution) sampled at (ho * stride, wo * stride); a sample point
+ *     beyond H or W (pad > (R - 1) / 2) reads zero.
+ *
+ *     R != S is admitted: the single `pad` then applies to BOTH axes (Ho = (H + 2 pad - R) / stride + 1, Wo = (W + 2 pad - S) / stride + 1), so a
+ *     1 x 3 filter with pad = 1 grows the image by two rows of bias.
  *
  * (2) GroupNorm statistics of the OUTPUT (gn_partial != NULL), for the GroupNorm(32) that consumes it next
  *     (vision/resnet.py:17-18 after :11; attention/attention.py:60 after resnet.py:31): the group_norm of

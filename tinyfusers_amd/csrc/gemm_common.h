@@ -736,6 +736,13 @@ static inline int igemm_ring_form(int bm, int bn, bool wide, bool all8, bool gen
   return wide && igemm_wide_ok(bm, bn) ? 1 : 0;
 }
 static inline bool gemm_generic(const GemmP& p) { return (p.C1 % 64) != 0 || (p.C2 % 64) != 0 || (p.C3 % 64) != 0 || (p.C4 % 64) != 0; }
+// k_igemm_pp's lean addressing, where the gather is a fixed pixel shift per tap and validity a bit per tap (pp_fast_pixel): stride 1, no up-sampling, at most
+// 31 taps of a SQUARE filter (the mask is built over S x S taps: an R x S filter with R > S would lose its rows r >= S), and extra 1x1 sources whose every
+// sample point lies inside the image (the extra segment is read unmasked at the output pixel's own index: with Ho > H or Wo > W it would run on into the
+// next row / image instead of reading zero).  Everything else takes the general gather; the e4m3 form has the lean addressing only (pp_ok)
+static inline bool pp_fast(const GemmP& p) {
+  return p.stride == 1 && !p.ups && p.S * p.S <= 31 && p.Kc == p.S * p.S * p.C && !((p.C3 || p.C4) && (p.Ho > p.H || p.Wo > p.W));
+}
 static inline int gi_table_bytes(const GemmP& p) { return p.gi_part ? (p.gi_G + p.C) * 8 : 0; }
 // LDS of a k_igemm<bm, bn> launch without the gi table (ring or epilogue scratch, whichever is larger)
 static inline int igemm_lds_bytes(int bm, int bn, bool wide) {

@@ -63,7 +63,7 @@ static bool pp_ok(const GemmP& p, int bn, int bm = 256) {
   if (p.fp8) {
     // the e4m3 form: block-scaled activations only, the lean addressing only (stride 1, no up-sampling), a whole K tile's fragments in
     // registers (three-slot ring: no 256-wide tile), and room for the scale table behind the ring (not 256 x 160 with half-tile slabs)
-    if (!p.mx || bn == 256 || p.stride != 1 || p.ups || p.S * p.S > 31 || p.C3 || p.C4) return false;
+    if (!p.mx || bn == 256 || !pp_fast(p) || p.C3 || p.C4) return false;
     const bool h2 = (p.C1 % 128) || (p.C2 % 128);
     if (bm == 256 && bn == 160 && h2) return false;
     if (p.out8 && !(p.act == 1 && bn == 128)) return false;   // a block-scaled output: the GEGLU epilogue of the 128-wide tile

@@ -28,5 +28,3 @@ static int launch_pp2(const GemmP& p, hipStream_t st) {
   TF_LAUNCH_CHECK();
   return TF_OK;
 }
-// lean addressing where the gather is a fixed pixel shift per tap: stride 1, no up-sampling, at most 31 taps
-static inline bool pp_fast(const GemmP& p) { return p.stride == 1 && !p.ups && p.S * p.S <= 31; }
