@@ -15,6 +15,7 @@ BASELINE config 3: full 50-step sampler, batch 1, end-to-end img/s.
     python -m example.sd1 --steps 20 --sampler dpmpp2m --control-image edges.npy [--control-ckpt control_v11p_sd15_canny.safetensors] [--control-scale 1.0]   # ControlNet
     python -m example.sd1 --steps 20 --sampler dpmpp2m --lora style.safetensors:0.8 --lora lcm.safetensors:1:0   # LoRA adapters, FILE[:w[:w_te]], merged on the device
     python -m example.sd1 --steps 4 --sampler lcm --no-cfg --lora lcm.safetensors:1:0   # few-step sampling: the LCM sampler on the guidance-free single-branch step
+    python -m example.sd1 --steps 20 --sampler dpmpp2m --ip-adapter ip-adapter_sd15.safetensors --ip-embeds e.npy [--ip-scale 0.6]   # IP-Adapter: an image prompt, as CLIP image embeddings (1, 1024)
 With --ckpt the configuration is read off the checkpoint's conv_in (4, 9 or 8 input channels); --concat picks it on synthetic weights.
 """
 import argparse
@@ -57,7 +58,25 @@ if __name__ == "__main__":
     ap.add_argument("--lora", action="append", default=[], metavar="FILE[:w[:w_te]]",
                     help="merge this LoRA adapter (.safetensors / .ckpt / .pt; kohya or PEFT keys) at UNet weight w (default 1) and text-encoder weight w_te "
                          "(default w); repeatable")
+    ap.add_argument("--ip-adapter", nargs="?", const="", default=None, metavar="FILE",
+                    help="condition on an image prompt through an IP-Adapter (ip-adapter_sd15 .safetensors / .bin); without FILE: synthetic adapter weights")
+    ap.add_argument("--ip-embeds", default="", help="with --ip-adapter: the CLIP image embeddings of the prompt image, a float (1, E) .npy (E = 1024 for ViT-H); "
+                                                    "with synthetic adapter weights a seeded vector stands in when not given")
+    ap.add_argument("--ip-image", default="", help="with --ip-adapter: the prompt image itself -- needs a CLIP vision tower (--clip-vision), which this tree does not have yet")
+    ap.add_argument("--clip-vision", default="", help="with --ip-image: the CLIP ViT-H image encoder's checkpoint (not supported yet)")
+    ap.add_argument("--ip-scale", type=float, default=None, help="with --ip-adapter: the adapter's strength (default 1.0)")
     args = ap.parse_args()
+    if (args.ip_embeds or args.ip_image or args.clip_vision or args.ip_scale is not None) and args.ip_adapter is None:
+        ap.error("--ip-embeds, --ip-image, --clip-vision and --ip-scale need --ip-adapter")
+    if args.ip_adapter is not None:
+        if not args.sampler:
+            ap.error("--ip-adapter needs --sampler")
+        if args.ip_image or args.clip_vision:
+            ap.error("--ip-image / --clip-vision: the CLIP vision tower is not in this tree yet -- compute the image embeddings elsewhere and pass --ip-embeds")
+        if args.ip_adapter and not args.ip_embeds:
+            ap.error("--ip-adapter FILE needs --ip-embeds (the CLIP image embeddings of the prompt image)")
+        if args.concat == "edit":
+            ap.error("--ip-adapter on an InstructPix2Pix checkpoint is not supported")
     loras = []
     for spec in args.lora:
         parts = spec.split(":")
@@ -151,6 +170,19 @@ if __name__ == "__main__":
             update_state(net, cstate, "control_model.")
         del cstate
         model.attach_control(net)
+    if args.ip_adapter is not None:
+        from tinyfusers_amd.storage.ip_adapter import IPAdapter
+        if concat == "edit":
+            sys.exit("--ip-adapter on an InstructPix2Pix checkpoint is not supported")
+        unet = model.model.diffusion_model
+        if args.ip_adapter:
+            adapter = IPAdapter.load(unet, args.ip_adapter)
+        else:
+            adapter = IPAdapter(unet, 4, 1024)
+            astate = {k: (synth_normal(2, k, shp, 0.03) + (1.0 if k == "image_proj.norm.weight" else 0.0)).astype(np.float16) for k, shp in adapter.expected_shapes().items()}
+            with contextlib.redirect_stdout(io.StringIO()):
+                update_state(adapter, astate, "")
+        model.attach_ip_adapter(adapter)
     print(f"weights installed in {time.time() - t0:.1f}s")
     if loras:                                                    # before the prompts are encoded (text-encoder adapters) and before compile
         t0 = time.perf_counter()
@@ -224,6 +256,14 @@ if __name__ == "__main__":
         cond_kw = {"control_image": hint}
         if args.control_scale is not None:
             cond_kw["control_scale"] = args.control_scale
+    if args.ip_adapter is not None:
+        embeds = np.load(args.ip_embeds) if args.ip_embeds else synth_normal(args.seed, "sd.ip_embeds", (1, adapter.embed_dim))
+        embeds = np.asarray(embeds, np.float32).reshape(1, -1) if np.asarray(embeds).ndim == 1 else np.asarray(embeds, np.float32)
+        if embeds.shape != (1, adapter.embed_dim):
+            sys.exit(f"--ip-embeds: expected one float (1, {adapter.embed_dim}) embedding for this adapter, got {embeds.shape}")
+        cond_kw = dict(cond_kw, ip_image_embeds=embeds)
+        if args.ip_scale is not None:
+            cond_kw["ip_scale"] = args.ip_scale
     latent = model.latent_from_numpy(synth_normal(args.seed, "sd.latent", (1, 4) + lat_hw))
     if args.sampler:
         from tinyfusers_amd.variants.samplers import make
@@ -232,7 +272,7 @@ if __name__ == "__main__":
         print(f"sampler {schedule.sampler}: {len(schedule.timesteps)} steps, timesteps {schedule.timesteps[0]} .. {schedule.timesteps[-1]}"
               + (f" (strength {strength}{', inpainting' if mask is not None else ''})" if init_image is not None else ""))
         model.compile(unconditional_context, context, latent, sampler=schedule, inpaint=mask is not None, concat=concat, control=bool(args.control_image),
-                      cfg=not args.no_cfg)
+                      cfg=not args.no_cfg, ip_adapter=args.ip_adapter is not None)
     else:
         model.compile(unconditional_context, context, latent)
     times = []

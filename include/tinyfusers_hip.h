@@ -346,6 +346,19 @@ typedef enum {
   TF_SDPA_INST_SPLIT = 5      /* k_sdpa_split: two key slices inside the block */
 } tfSdpaInstance;
 int tf_sdpa_instance(int dtype, int B, int NH, int Tq, int Tk, int HS, long long k_st, long long v_st, int causal);
+/* ---- decoupled cross-attention in ONE launch: the attention of attention/attention.py:35-41 with a second key / value set next to the text tokens (the
+ * IP-Adapter's image tokens).  o = softmax(q k^T / sqrt(HS)) v + (*scale2_dev) softmax(q k2^T / sqrt(HS)) v2: two independent softmaxes, no mask;
+ * scale2_dev is one fp32 ON THE DEVICE, read by the kernel, so a captured launch follows a changed scale without a re-capture, and a scale of 0 gives
+ * tf_sdpa_16's values of the text set alone.  Strides and the output head-merge choices are tf_sdpa_16's (k2 / v2 carry their own).  HS in {40, 80,
+ * 160}, Tk >= 1, 1 <= Tk2 <= 64 (one key tile), dtype TF_DTYPE_F16 / TF_DTYPE_BF16; anything else returns TF_E_ARG or TF_E_UNSUPPORTED with a message
+ * before the device is touched, as does a key set whose (batch, head) slice spans 2 GiB or more.  The launch runs the dual instance of the family
+ * tf_sdpa_instance names for the text launch with the split forms left out (TF_SDPA_INST_DMA16 / _DMA32 / _DMA32_W8); tf_sdpa_dual_instance answers with
+ * that rule, host code only.  Profiled in family 4 with FLOPs 4 B NH Tq (Tk + Tk2) HS. */
+int tf_sdpa_dual_16(int dtype, void* o, const void* q, const void* k, const void* v, int Tk, const void* k2, const void* v2, int Tk2, const float* scale2_dev,
+                    int B, int NH, int Tq, int HS, long long q_sb, long long q_sh, long long q_st, long long k_sb, long long k_sh, long long k_st,
+                    long long v_sb, long long v_sh, long long v_st, long long k2_sb, long long k2_sh, long long k2_st, long long v2_sb, long long v2_sh,
+                    long long v2_st, long long o_sb, long long o_sh, long long o_st, tfStream_t s);
+int tf_sdpa_dual_instance(int dtype, int B, int NH, int Tq, int Tk, int Tk2, int HS, long long k_st, long long v_st, long long k2_st, long long v2_st);
 /* row softmax over (N, C) fp32 -- Device.softmax (storage/device.py:129-157; softmax_func.cu:22-113) */
 int tf_softmax_rows_f32(void* out, const void* inp, int N, int C, tfStream_t s);
 /* softmax step of the UNFUSED attention (attention/sdpa.py:63-75 as the reference runs it: scale * matmul, + mask (:67-68: bool ->

@@ -26,6 +26,25 @@ def sdpa_instance(dtype, B, NH, Tq, Tk, HS, k_st=None, v_st=None, causal=False):
     return SDPA_INSTANCES[rc]
 
 
+def sdpa_dual_strided(o, q, k, v, k2, v2, scale_ptr, B, NH, Tq, Tk, Tk2, HS, qs, ks, vs, k2s, v2s, os_):
+    """Raw launch of the decoupled cross-attention, o = softmax(q k^T / sqrt HS) v + s softmax(q k2^T / sqrt HS) v2 in ONE kernel (tf_sdpa_dual_16):
+    sdpa_strided's conventions plus a second key / value set of 1 .. 64 tokens with strides of its own; scale_ptr is the DEVICE address of the fp32 s,
+    read when the kernel runs.  HS in {40, 80, 160}."""
+    assert dtag(q.dtype) == dtag(k.dtype) == dtag(v.dtype) == dtag(k2.dtype) == dtag(v2.dtype) == dtag(o.dtype), "sdpa_dual: q / k / v / k2 / v2 / o must hold the same 16-bit type"
+    hip.tf_sdpa_dual_16(dtag(q.dtype), o.ptr, q.ptr, k.ptr, v.ptr, Tk, k2.ptr, v2.ptr, Tk2, scale_ptr, B, NH, Tq, HS, *qs, *ks, *vs, *k2s, *v2s, *os_, _sh())
+    return o
+
+
+def sdpa_dual_instance(dtype, B, NH, Tq, Tk, Tk2, HS, k_st=None, v_st=None, k2_st=None, v2_st=None):
+    """The kernel family sdpa_dual_strided's launch of that shape runs (tf_sdpa_dual_instance: the launcher's own rule, no device needed): "dma16",
+    "dma32" or "dma32_w8" -- sdpa_instance's answer for the text launch with the split forms left out.  A shape the launch would refuse raises."""
+    st = [HS if s is None else s for s in (k_st, v_st, k2_st, v2_st)]
+    rc = lib.tf_sdpa_dual_instance(dtag(dtype), B, NH, Tq, Tk, Tk2, HS, *st)
+    if rc not in SDPA_INSTANCES:
+        check(rc, "tf_sdpa_dual_instance")
+    return SDPA_INSTANCES[rc]
+
+
 def _is_causal_mask(m, tq, tk):
     m = np.asarray(m)
     if m.shape[-2:] != (tq, tk):

@@ -20,6 +20,9 @@
 #ifndef TF_TU_SPLIT
 #define TF_TU_SPLIT 0      // 1: the key-slice instances only (sdpa_split.hip / sdpa_split_bf16.hip), so that this unit's code objects stay what they were
 #endif
+#ifndef TF_TU_DUAL
+#define TF_TU_DUAL 0       // 1: the dual (two key sets) instances only (sdpa_dual.hip / sdpa_dual_bf16.hip), for the same reason
+#endif
 
 struct SdpaP {
   const half_t* q; const half_t* k; const half_t* v; half_t* o;
@@ -354,6 +357,13 @@ enum { SDPA_SPLIT_40_W16 = 1,    // <40, 2, 16, 2, 4>: 8 query waves x 2 slices,
        SDPA_SPLIT_80_Q16 = 2 };  // <80, 1, 8, 2, 3>: 16-query waves, 4 x 2, 64 queries per block (126 KiB): two waves per SIMD
 int tfk_sdpa_split(const SdpaP& p, int form, hipStream_t st);
 int tfk_sdpa_split_bf16(const SdpaP& p, int form, hipStream_t st);
+// the unsplit part of the launcher's rule (sdpa_instance below, in the float16 unit): what a launch runs once the split forms are left out
+int tfk_sdpa_instance_unsplit(int B, int NH, int Tq, int HS);
+static int sdpa_refuse(const char* who, int Tk, int HS, long long k_st, long long v_st) {
+  tf_set_error("%s: the keys / values of one (batch, head) slice span %lld / %lld bytes (Tk=%d, token strides %lld / %lld elements); every attention kernel "
+               "addresses a slice with 32-bit byte offsets (< 2 GiB)", who, ((long long)Tk * k_st + HS) * 2, ((long long)Tk * v_st + HS) * 2, Tk, k_st, v_st);
+  return TF_E_UNSUPPORTED;
+}
 
 #if TF_TU_SPLIT
 template <int HS, int QT, int NW, int KS, int SR, bool BF>
@@ -383,7 +393,131 @@ int TFK(tfk_sdpa_split)(const SdpaP& p, int form, hipStream_t st) {
   tf_set_error("tf_sdpa: no split kernel of form %d", form);
   return TF_E_UNSUPPORTED;
 }
-#else   // !TF_TU_SPLIT: everything below is the unsplit units' (sdpa.hip, sdpa_bf16.hip)
+#elif TF_TU_DUAL
+// ---------------------------------------------------------------------------------------------------------------
+// Decoupled cross-attention in one launch (tf_sdpa_dual_16; the IP-Adapter's image tokens next to the text tokens, attention/attention.py:35-41 with a
+// second key / value set): o = softmax(q k^T / sqrt d) v + s softmax(q k2^T / sqrt d) v2, two independent softmaxes, s one fp32 read from the device.
+// k_sdpa_dual is k_sdpa_dma's body with TF_SDPA_BODY_DUAL (sdpa_dma_body.inc): the 1 .. 64 image keys are one more tile of the ring, so the text
+// tiles take the path they take in k_sdpa_dma, no score and no intermediate o goes to HBM, and there is no second accumulator set and no extra LDS.
+struct SdpaDualP {
+  SdpaP p;                                 // the text launch, as tf_sdpa_16 would fill it (causal = 0)
+  const half_t* k2; const half_t* v2; const float* scale2;
+  int Tk2;
+  long long k2_sb, k2_sh, k2_st, v2_sb, v2_sh, v2_st;
+};
+
+// sum over the four 16-lane groups of the wave, result in every lane (the same order in every lane): max_over_lane_groups' two swaps with an add
+__device__ __forceinline__ float sum_over_lane_groups(float v) {
+  typedef unsigned u2v __attribute__((ext_vector_type(2)));
+  u2v r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  float m = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+  u2v q = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
+  return __uint_as_float(q[0]) + __uint_as_float(q[1]);
+}
+
+template <int HS, int QT, int NW, bool BF>
+__global__ void __launch_bounds__(NW * 64) k_sdpa_dual(const SdpaDualP pd) {
+  constexpr int KS = 1, SR = 0, DBG = 0;
+  const SdpaP& p = pd.p;
+#define TF_SDPA_BODY_DUAL 1
+#include "sdpa_dma_body.inc"
+#undef TF_SDPA_BODY_DUAL
+}
+
+template <int HS, int QT, int NW = 4>
+static int launch_sdpa_dual(const SdpaDualP& pd, hipStream_t st) {
+  constexpr int smem = sdpa_ring(SdpaDma<HS>::STAGE_B, NW, SdpaDma<HS>::S) * SdpaDma<HS>::STAGE_B;      // k_sdpa_dma<HS, QT, 0, NW>'s ring
+  constexpr int QB = 16 * NW * QT;
+  static bool attr_set = false;
+  if (!attr_set) {
+    TF_HIP(hipFuncSetAttribute((const void*)k_sdpa_dual<HS, QT, NW, kBF>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+    attr_set = true;
+  }
+  hipLaunchKernelGGL((k_sdpa_dual<HS, QT, NW, kBF>), dim3((unsigned)((pd.p.Tq + QB - 1) / QB * pd.p.NH * pd.p.B)), dim3(NW * 64), smem, st, pd);
+  TF_LAUNCH_CHECK();
+  return TF_OK;
+}
+
+// Which family a dual launch runs: the one sdpa_instance names for the text launch with the split forms left out, among the head sizes the dual form
+// is built for.  0: a key set no kernel can address; < 0: the rule names a family without a dual instance (TF_SDPA_GENERIC).
+static int sdpa_dual_rule(int B, int NH, int Tq, int Tk, int Tk2, int HS, long long k_st, long long v_st, long long k2_st, long long v2_st) {
+  const auto small = [&](int T, long long a, long long b) { return ((long long)T * a + HS) * 2 < (1ll << 31) && ((long long)T * b + HS) * 2 < (1ll << 31); };
+  if (!small(Tk, k_st, v_st) || !small(Tk2, k2_st, v2_st)) return 0;
+  const int inst = tfk_sdpa_instance_unsplit(B, NH, Tq, HS);
+  return inst == TF_SDPA_INST_DMA16 || inst == TF_SDPA_INST_DMA32 || inst == TF_SDPA_INST_DMA32_W8 ? inst : -1;
+}
+static int sdpa_dual_refuse(const char* who, int rule, int Tk, int Tk2, int HS, long long k_st, long long v_st, long long k2_st, long long v2_st) {
+  if (rule == 0) {
+    const bool text = !(((long long)Tk * k_st + HS) * 2 < (1ll << 31) && ((long long)Tk * v_st + HS) * 2 < (1ll << 31));
+    return text ? sdpa_refuse(who, Tk, HS, k_st, v_st) : sdpa_refuse(who, Tk2, HS, k2_st, v2_st);
+  }
+  tf_set_error("%s: the dual form exists for the LDS-DMA families only (TF_SDPA_GENERIC is set)", who);
+  return TF_E_UNSUPPORTED;
+}
+// the checks on sizes and strides shared by the launch and the query; 0 or a status with the message set
+static int sdpa_dual_args(const char* who, int dtype, int B, int NH, int Tq, int Tk, int Tk2, int HS, long long k_st, long long v_st, long long k2_st, long long v2_st) {
+  TF_REQUIRE(dtype == TF_DTYPE_F16 || dtype == TF_DTYPE_BF16, "%s: dtype=%d (0 = float16, 1 = bfloat16)", who, dtype);
+  TF_REQUIRE(B >= 0 && NH >= 1 && Tq >= 0 && Tk >= 1 && Tk2 >= 1, "%s: bad sizes B=%d NH=%d Tq=%d Tk=%d Tk2=%d", who, B, NH, Tq, Tk, Tk2);
+  TF_REQUIRE(HS >= 8 && HS % 8 == 0 && HS <= 160, "%s: head size %d must be a multiple of 8 in [8, 160]", who, HS);
+  TF_REQUIRE(k_st % 8 == 0 && v_st % 8 == 0 && k2_st % 8 == 0 && v2_st % 8 == 0, "%s: k / v / k2 / v2 strides must be multiples of 8 elements (16-B rows)", who);
+  if (Tk2 > 64) {
+    tf_set_error("%s: Tk2=%d: the second key set is one tile of at most 64 keys", who, Tk2);
+    return TF_E_UNSUPPORTED;
+  }
+  if (HS != 40 && HS != 80 && HS != 160) {
+    tf_set_error("%s: head size %d: the dual form is built for 40, 80 and 160 (the SD UNets' cross-attentions)", who, HS);
+    return TF_E_UNSUPPORTED;
+  }
+  return TF_OK;
+}
+
+int tfk_sdpa_dual_bf16(const SdpaDualP& pd, int inst, hipStream_t st);
+int TFK(tfk_sdpa_dual)(const SdpaDualP& pd, int inst, hipStream_t st) {
+  const int HS = pd.p.HS;
+  if (inst == TF_SDPA_INST_DMA16) return HS == 40 ? launch_sdpa_dual<40, 1>(pd, st) : HS == 80 ? launch_sdpa_dual<80, 1>(pd, st) : launch_sdpa_dual<160, 1>(pd, st);
+  if (inst == TF_SDPA_INST_DMA32_W8 && HS != 160) return HS == 40 ? launch_sdpa_dual<40, 2, 8>(pd, st) : launch_sdpa_dual<80, 2, 8>(pd, st);
+  return HS == 40 ? launch_sdpa_dual<40, 2>(pd, st) : HS == 80 ? launch_sdpa_dual<80, 2>(pd, st) : launch_sdpa_dual<160, 2>(pd, st);
+}
+
+#if !TF_TU_BF
+extern "C" int tf_sdpa_dual_instance(int dtype, int B, int NH, int Tq, int Tk, int Tk2, int HS, long long k_st, long long v_st, long long k2_st, long long v2_st) {
+  if (int rc = sdpa_dual_args("tf_sdpa_dual_instance", dtype, B, NH, Tq, Tk, Tk2, HS, k_st, v_st, k2_st, v2_st)) return rc;
+  TF_REQUIRE(B >= 1 && Tq >= 1, "tf_sdpa_dual_instance: bad sizes B=%d Tq=%d", B, Tq);
+  const int rule = sdpa_dual_rule(B, NH, Tq, Tk, Tk2, HS, k_st, v_st, k2_st, v2_st);
+  return rule > 0 ? rule : sdpa_dual_refuse("tf_sdpa_dual_instance", rule, Tk, Tk2, HS, k_st, v_st, k2_st, v2_st);
+}
+
+extern "C" int tf_sdpa_dual_16(int dtype, void* o, const void* q, const void* k, const void* v, int Tk, const void* k2, const void* v2, int Tk2, const float* scale2_dev,
+                               int B, int NH, int Tq, int HS, long long q_sb, long long q_sh, long long q_st, long long k_sb, long long k_sh, long long k_st,
+                               long long v_sb, long long v_sh, long long v_st, long long k2_sb, long long k2_sh, long long k2_st, long long v2_sb, long long v2_sh,
+                               long long v2_st, long long o_sb, long long o_sh, long long o_st, tfStream_t s) {
+  TF_REQUIRE(o && q && k && v && k2 && v2 && scale2_dev, "tf_sdpa_dual_16: null tensor");
+  if (int rc = sdpa_dual_args("tf_sdpa_dual_16", dtype, B, NH, Tq, Tk, Tk2, HS, k_st, v_st, k2_st, v2_st)) return rc;
+  TF_REQUIRE((long long)((Tq + 63) / 64) * NH * B < (1ll << 31), "tf_sdpa_dual_16: too many (query block, head, batch) work items");
+  const long long str[] = {q_sb, q_sh, q_st, k_sb, k_sh, v_sb, v_sh, k2_sb, k2_sh, v2_sb, v2_sh};
+  for (int i = 0; i < 11; ++i) TF_REQUIRE(str[i] % 8 == 0, "tf_sdpa_dual_16: q / k / v / k2 / v2 strides must be multiples of 8 elements (16-B rows)");
+  TF_REQUIRE(o_sb % 4 == 0 && o_sh % 4 == 0 && o_st % 4 == 0, "tf_sdpa_dual_16: output strides must be multiples of 4 elements");
+  if (B == 0 || Tq == 0) return TF_OK;
+  SdpaDualP pd;
+  SdpaP& p = pd.p;
+  p.q = (const half_t*)q; p.k = (const half_t*)k; p.v = (const half_t*)v; p.o = (half_t*)o;
+  p.B = B; p.NH = NH; p.Tq = Tq; p.Tk = Tk; p.HS = HS;
+  p.q_sb = q_sb; p.q_sh = q_sh; p.q_st = q_st; p.k_sb = k_sb; p.k_sh = k_sh; p.k_st = k_st;
+  p.v_sb = v_sb; p.v_sh = v_sh; p.v_st = v_st; p.o_sb = o_sb; p.o_sh = o_sh; p.o_st = o_st;
+  p.scale_log2e = (1.0f / sqrtf((float)HS)) * 1.4426950408889634f;
+  p.causal = 0;
+  p.dbg = 0;
+  pd.k2 = (const half_t*)k2; pd.v2 = (const half_t*)v2; pd.scale2 = scale2_dev; pd.Tk2 = Tk2;
+  pd.k2_sb = k2_sb; pd.k2_sh = k2_sh; pd.k2_st = k2_st; pd.v2_sb = v2_sb; pd.v2_sh = v2_sh; pd.v2_st = v2_st;
+  // the instance is decided (and a slice no kernel can address refused) before anything touches the device
+  const int rule = sdpa_dual_rule(B, NH, Tq, Tk, Tk2, HS, k_st, v_st, k2_st, v2_st);
+  if (rule <= 0) return sdpa_dual_refuse("tf_sdpa_dual_16", rule, Tk, Tk2, HS, k_st, v_st, k2_st, v2_st);
+  hipStream_t st = tf_hs(s);
+  TfProfScope prof_(TF_PROF_FAM_SDPA, 4.0 * B * NH * (double)Tq * ((double)Tk + Tk2) * HS, st);
+  return dtype == TF_DTYPE_BF16 ? tfk_sdpa_dual_bf16(pd, rule, st) : tfk_sdpa_dual(pd, rule, st);
+}
+#endif
+#else   // neither: everything below is the unsplit units' (sdpa.hip, sdpa_bf16.hip)
 
 template <int HS, int QT, int DBG = 0, int NW = 4, bool BF = false>        // DBG: compile-time ablation mask (tools/sdpa_dbg.py; bits as SdpaP::dbg); BF: bfloat16 q / k / v / o (sdpa_bf16.hip)
 __global__ void __launch_bounds__(NW * 64) k_sdpa_dma(const SdpaP p) {
@@ -469,6 +603,7 @@ static int sdpa_split_form(int B, int NH, int Tq, int Tk, int HS, int causal, bo
 // Which kernel family a launch runs (TF_SDPA_INST_* of include/tinyfusers_hip.h), from the shape and the K / V token strides alone; 0 = no kernel
 // can run it.  THE rule: tf_sdpa_f16 / tfk_sdpa_bf16 branch on this value and tf_sdpa_instance returns it.  *form: the SDPA_SPLIT_* of a split launch.
 enum { SDPA_INST_NONE = 0 };     // (not one of tfSdpaInstance's values)
+static int sdpa_instance_unsplit(int B, int NH, int Tq, int HS);
 static int sdpa_instance(int B, int NH, int Tq, int Tk, int HS, long long k_st, long long v_st, int causal, int* form) {
   // K/V offsets inside a (batch, head) slice must fit 32-bit byte offsets: the buffer offsets of the DMA kernels, and k_sdpa's own
   // (unsigned)(key * k_st + col) * 2u under a 32-bit num_records
@@ -476,6 +611,10 @@ static int sdpa_instance(int B, int NH, int Tq, int Tk, int HS, long long k_st, 
   *form = 0;
   if (!small) return SDPA_INST_NONE;
   if ((*form = sdpa_split_form(B, NH, Tq, Tk, HS, causal, small))) return TF_SDPA_INST_SPLIT;
+  return sdpa_instance_unsplit(B, NH, Tq, HS);
+}
+// the rest of the rule, which the dual launcher (sdpa_dual.hip: no split forms) asks for on its own
+static int sdpa_instance_unsplit(int B, int NH, int Tq, int HS) {
   if (g_sdpa_generic || (HS != 40 && HS != 64 && HS != 80 && HS != 128 && HS != 160)) return TF_SDPA_INST_GENERIC;
   // 16 queries per wave (QT = 1) doubles the waves in flight; g_sdpa_qt: 0 = per-shape choice, 1 / 2 forced (TF_SDPA_QT)
   // (measured: 32x32 d80 22.5 -> 19.7 us, 16x16 d160 13.4 -> 10.6 us with 16-query waves; 64x64 d40 93.8 -> 118.7 us: only when
@@ -495,12 +634,8 @@ int TFK(tfk_sdpa_instance)(int B, int NH, int Tq, int Tk, int HS, long long k_st
   int form;
   return sdpa_instance(B, NH, Tq, Tk, HS, k_st, v_st, causal, &form);
 }
-static int sdpa_refuse(const char* who, int Tk, int HS, long long k_st, long long v_st) {
-  tf_set_error("%s: the keys / values of one (batch, head) slice span %lld / %lld bytes (Tk=%d, token strides %lld / %lld elements); every attention kernel "
-               "addresses a slice with 32-bit byte offsets (< 2 GiB)", who, ((long long)Tk * k_st + HS) * 2, ((long long)Tk * v_st + HS) * 2, Tk, k_st, v_st);
-  return TF_E_UNSUPPORTED;
-}
 #if !TF_TU_BF
+int tfk_sdpa_instance_unsplit(int B, int NH, int Tq, int HS) { return sdpa_instance_unsplit(B, NH, Tq, HS); }
 int g_sdpa_force_ks = 0;
 extern "C" int tf_sdpa_force_split(int ks) {
   TF_REQUIRE(ks >= 0 && ks <= 2, "tf_sdpa_force_split: ks=%d (0 = per-shape choice, 1 = unsplit, 2 = two key slices)", ks);

@@ -1,6 +1,17 @@
-// Body of the LDS-DMA attention kernels, #included into k_sdpa_dma (KS = 1, SR = 0 as local constants) and k_sdpa_split (sdpa.hip): one text, two
-// __global__ functions -- a shared __device__ function, even force-inlined, changed the code of the shipped k_sdpa_dma instances.
+// Body of the LDS-DMA attention kernels, #included into k_sdpa_dma (KS = 1, SR = 0 as local constants), k_sdpa_split and k_sdpa_dual (sdpa.hip): one
+// text, three __global__ functions -- a shared __device__ function, even force-inlined, changed the code of the shipped k_sdpa_dma instances.
 // In scope: template parameters HS, QT, DBG, NW, BF; constants KS (key slices), SR (stages per ring when KS > 1); the kernel argument `p`.
+//
+// TF_SDPA_BODY_DUAL (a compile-time flag, #defined to 1 around the #include in k_sdpa_dual only; KS = 1, DBG = 0, no causal mask; also in scope: `pd`,
+// the SdpaDualP that holds `p`): o = softmax(q k^T) v + s softmax(q k2^T) v2 with a second key set of at most 64 keys.  The second set is one more
+// tile of the same ring -- local tile `ntiles`, fetched through descriptors of its own -- and one more trip of the same loop (`img`): the text
+// row sums l are set aside first, the tile takes its own maximum and its own row sums l2 (fp32, a lane-group sum), its P fragments are scaled per
+// query by s l / l2 before the 16-bit rounding, and its P.V MFMAs accumulate onto the text accumulators, so that the plain epilogue's one multiply by
+// 1 / l finishes both terms -- and at s = 0 stores what the plain kernel stores, value for value.  Without the flag every line below preprocesses to
+// what it was.
+#ifndef TF_SDPA_BODY_DUAL
+#define TF_SDPA_BODY_DUAL 0
+#endif
   static_assert(!(BF && DBG), "the ablation instances are fp16");
   static_assert(NW % KS == 0 && (KS == 1 || (DBG == 0 && SR >= 2)), "key slices: whole query groups, a ring each, no ablation form");
   constexpr int NQ = NW / KS;                                // query groups (waves per slice)
@@ -52,9 +63,16 @@
     ntiles = min(ntiles, last_q / 64 + 1);
   }
   // this slice's tiles: global tiles t0 .. t0 + n_my - 1, walked as local tiles 0 .. n_my - 1 of its ring; `trip` iterations for every wave of the block
+#if TF_SDPA_BODY_DUAL
+  static_assert(KS == 1 && DBG == 0, "the dual form has no key slices and no ablation build");
+  const int trip = ntiles + 1, t0 = 0, n_my = ntiles + 1;      // the image tile is local tile `ntiles`
+  const float scale2 = *pd.scale2;
+  float l_txt[QT] = {};                                           // the text row sums, set when the image tile begins
+#else
   const int trip = KS == 1 ? ntiles : (ntiles + KS - 1) / KS;
   const int t0 = KS == 1 ? 0 : sl * trip;
   const int n_my = KS == 1 ? ntiles : max(0, min(trip, ntiles - t0));
+#endif
 
   // this wave's 1-KiB pieces of a tile: piece j = qg + NQ i (clamped: the spare slots of the last round repeat piece
   // NI-1, same bytes to the same place); j < KPC -> K image, else V image
@@ -82,6 +100,30 @@
   auto issue = [&](int lt_) {             // local tile lt_ of this slice -> stage lt_ % S of its ring
     const unsigned base = lds0 + (unsigned)(lt_ % S) * STAGE_B;
     const int tt = t0 + lt_;
+#if TF_SDPA_BODY_DUAL
+    if (lt_ == ntiles) {
+      // the image tile: the same pieces to the same places through descriptors of its own (rows >= Tk2 lie beyond num_records and come back as zeros,
+      // as a ragged text tile's do); voff's arithmetic with the image strides, done here, once per kernel
+      const i4v rs_k2 = sdpa_rsrc(pd.k2 + b * pd.k2_sb + h * pd.k2_sh, (unsigned)(((long long)(pd.Tk2 - 1) * pd.k2_st + HS) * 2));
+      const i4v rs_v2 = sdpa_rsrc(pd.v2 + b * pd.v2_sb + h * pd.v2_sh, (unsigned)(((long long)(pd.Tk2 - 1) * pd.v2_st + HS) * 2));
+#pragma unroll
+      for (int i = 0; i < LPW; ++i) {
+        const int j = min(qg + NQ * i, NI - 1);
+        if (j < KPC) {
+          int x = 64 * j + lane, r = x / KPC, cc = x - r * KPC;
+          int kt = r >> 4, rr = r & 15;
+          int key = 32 * (kt >> 1) + 8 * (rr >> 2) + 4 * (kt & 1) + (rr & 3);
+          sdpa_dma16(rs_k2, cc < CK ? (unsigned)(key * (int)pd.k2_st + cc * 8) * 2u : 0x80000000u, base + j * 1024);
+        } else {
+          int x = 64 * (j - KPC) + lane, grp = x / VGC, rem = x - grp * VGC;
+          int rr = rem / VPC, cc = rem - rr * VPC, r = 8 * grp + rr;
+          const unsigned off = (rr < 8 && grp < 8 && cc < CK) ? (unsigned)(r * (int)pd.v2_st + cc * 8) * 2u : 0x80000000u;
+          if (!(HAS_PAD && rr < 8 && grp < 8 && cc == CK)) sdpa_dma16(rs_v2, off, base + j * 1024);     // (the preset ones column stays out of the DMA)
+        }
+      }
+      return;
+    }
+#endif
 #pragma unroll
     for (int i = 0; i < LPW; ++i) {
       int j = min(qg + NQ * i, NI - 1);
@@ -124,6 +166,29 @@
     const half_t* ks_ = reinterpret_cast<const half_t*>(smem_raw + (sl * S + i % S) * STAGE_B);
     const half_t* vs_ = ks_ + C::K_BYTES / 2;
 
+#if TF_SDPA_BODY_DUAL
+    const bool img = i == ntiles;                          // (wave-uniform)
+    const int key0 = img ? 0 : t * 64, nkeys = img ? pd.Tk2 : p.Tk;
+    if (img) {
+      // the text softmax is complete.  Its row sum l is taken out of the accumulators' reach (at d = 40 the image tile's P.V adds to the row that
+      // holds it) and both are scaled by the power of two that brings l into [1, 2): exact, so the epilogue's o * (1 / l) -- the plain kernel's own
+      // expression -- rounds to what the plain kernel stores, and the image tile's P, scaled by s l / l2 below, stays <= 2 |s|.  The image tile's own
+      // softmax starts from nothing.
+#pragma unroll
+      for (int qt = 0; qt < QT; ++qt) {
+        float l = lt[qt][0];
+        if constexpr (HAS_PAD) l = __shfl(ot[(HS / 16) % NDT][qt][0], lr + 16 * ((HS % 16) / 4), 64);
+        const float e2 = __uint_as_float(0x7f000000u - (__float_as_uint(l) & 0x7f800000u));      // 2^-floor(log2 l)
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt) ot[dt][qt] *= e2;
+        l_txt[qt] = l * e2;
+        m_run[qt] = 0.f;
+      }
+    }
+#else
+    constexpr bool img = false;
+    const int key0 = t * 64, nkeys = p.Tk;
+#endif
     f4 st[4][QT];
     f4 init4[QT];
 #pragma unroll
@@ -140,8 +205,8 @@
         }
       }
     }
-    const int kbase = t * 64 + 8 * lg;
-    if (t * 64 + 64 > p.Tk || p.causal) {
+    const int kbase = key0 + 8 * lg;
+    if (key0 + 64 > nkeys || p.causal) {
 #pragma unroll
       for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
@@ -150,7 +215,7 @@
 #pragma unroll
           for (int qt = 0; qt < QT; ++qt) {
             int qi = qblk + qt * 16 + lr;
-            if (key >= p.Tk || (p.causal && key > qi)) st[kt][qt][e] = -INFINITY;
+            if (key >= nkeys || (p.causal && key > qi)) st[kt][qt][e] = -INFINITY;
           }
         }
     }
@@ -171,12 +236,12 @@
     bool over = false;
 #pragma unroll
     for (int q_ = 0; q_ < QT; ++q_) over = over || (mx[q_] > RESCALE_THR);
-    if (i == 0 || __any(over)) {
+    if (i == 0 || img || __any(over)) {
 #pragma unroll
       for (int qt = 0; qt < QT; ++qt) {
-        float delta = mx[qt] == -INFINITY ? 0.f : (i == 0 ? mx[qt] : fmaxf(mx[qt], 0.f));
+        float delta = mx[qt] == -INFINITY ? 0.f : (i == 0 || img ? mx[qt] : fmaxf(mx[qt], 0.f));
         m_run[qt] += delta;
-        if (i != 0) {
+        if (i != 0 && !img) {
           float alpha = __builtin_amdgcn_exp2f(-delta);
 #pragma unroll
           for (int dt = 0; dt < NDT; ++dt) ot[dt][qt] *= alpha;
@@ -189,17 +254,40 @@
       }
     }
     h8 pf[2][QT];
+#if TF_SDPA_BODY_DUAL
+    if (img) {
+      // own row sums in fp32 (this lane's 16 keys, then the four lane groups); P is scaled by s l / l2 per query -- the query is the lane's own
+      // column; l: the text row sum the epilogue divides by -- and rounded to 16 bits once
+#pragma unroll
+      for (int qt = 0; qt < QT; ++qt) {
+        float l2 = 0.f;
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { st[kt][qt][e] = __builtin_amdgcn_exp2f(st[kt][qt][e]); l2 += st[kt][qt][e]; }
+        const float c2 = scale2 * l_txt[qt] / sum_over_lane_groups(l2);      // l2 >= 1: Tk2 >= 1 and the maximum's own term is 2^0
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) pf[kt >> 1][qt][(kt & 1) * 4 + e] = f2e<BF>(st[kt][qt][e] * c2);
+      }
+    } else
+#endif
+    {
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt)
 #pragma unroll
       for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
         for (int e = 0; e < 4; ++e) pf[kt >> 1][qt][(kt & 1) * 4 + e] = (DBG & 1) ? (half_t)st[kt][qt][e] : f2e<BF>(__builtin_amdgcn_exp2f(st[kt][qt][e]));
+    }
     if constexpr (!HAS_PAD) {
+      if (!img) {
 #pragma unroll
       for (int kc = 0; kc < 2; ++kc) {
 #pragma unroll
         for (int q_ = 0; q_ < QT; ++q_) lt[q_] = mfma16<BF>(ones, pf[kc][q_], lt[q_]);
+      }
       }
     }
 #pragma unroll
@@ -260,8 +348,12 @@
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) {
     // row sum: the ones-MFMA's accumulator, or row HS of O^T (the preset ones column of V): accumulator tile HS / 16, lane group (HS % 16) / 4
+#if TF_SDPA_BODY_DUAL
+    float l = l_txt[qt];                 // the text row sum, saved (and scaled into [1, 2) with the accumulators) in front of the image tile
+#else
     float l = lt[qt][0];
     if constexpr (HAS_PAD) l = __shfl(ot[(HS / 16) % NDT][qt][0], lr + 16 * ((HS % 16) / 4), 64);
+#endif
     float inv = l > 0.f ? 1.0f / l : 0.f;
     int qi = qblk + qt * 16 + lr;
     if (qi < p.Tq) {

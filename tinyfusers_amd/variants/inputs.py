@@ -65,10 +65,47 @@ def control_scales(control_scale, n_res):
     return scales
 
 
-def check_compile(cin, has_control_net, config, latent, sampler, inpaint, concat, control, cfg=True):
+def ip_scales(ip_scale, n_attn, who="start"):
+    """ip_scale= -> the fp32 words of the adapter's scale buffer (one per cross-attention in adapter order, padded to whole 4-word writes): all
+    ones when not given."""
+    scales = np.ones(((n_attn + 3) // 4 * 4,), np.float32)
+    if ip_scale is not None:
+        sc = np.asarray(ip_scale, dtype=np.float32)
+        if sc.ndim > 1 or (sc.ndim == 1 and sc.shape[0] != n_attn):
+            raise ValueError(f"StableDiffusion.{who}: ip_scale takes one float or {n_attn} (one per cross-attention), got shape {sc.shape}")
+        if not np.isfinite(sc).all():
+            raise ValueError(f"StableDiffusion.{who}: ip_scale={ip_scale}")
+        scales[:n_attn] = sc
+    return scales
+
+
+def ip_embeds(x, batch, width):
+    """start(ip_image_embeds=): a host float (B, E) array (or one row for every image) -> fp32 (B, E)."""
+    if isinstance(x, DeviceArray):
+        raise TypeError("StableDiffusion.start: ip_image_embeds= takes a host array")
+    e = np.ascontiguousarray(x, dtype=np.float32)
+    if e.ndim != 2 or e.shape[0] not in (1, batch) or e.shape[1] != width:
+        raise ValueError(f"StableDiffusion.start: ip_image_embeds must be float {(batch, width)} (or one row for all) for the compiled latent and the attached adapter, got {e.shape}")
+    if not np.isfinite(e).all():
+        raise ValueError("StableDiffusion.start: ip_image_embeds holds non-finite values")
+    return np.ascontiguousarray(np.broadcast_to(e, (batch, width)))
+
+
+def check_compile(cin, has_control_net, config, latent, sampler, inpaint, concat, control, cfg=True, ip_adapter=False, has_ip_adapter=False):
     """compile()'s refusals, before any device work: ``cin`` the UNet's in_channels, ``config`` the package's config module."""
     def refuse(exc, text):
         raise exc(f"StableDiffusion.compile: {text}")
+    if ip_adapter:
+        if not has_ip_adapter:
+            refuse(ValueError, "ip_adapter=True needs an adapter: attach_ip_adapter(IPAdapter.load(unet, FILE)) first")
+        if sampler is None:
+            refuse(ValueError, "ip_adapter=True needs a sampler schedule (sampler=<Schedule>)")
+        if concat == "edit":
+            refuse(ValueError, "ip_adapter=True and concat='edit' together are not supported (the adapter's unconditional convention is defined for two guidance groups, InstructPix2Pix runs three)")
+        if config.cfg_parallel:
+            refuse(UnsupportedSamplerConfig, "an adapted model has no two-chain CFG form (TF_CFG_PARALLEL)")
+        if config.dtype == "fp8":
+            refuse(UnsupportedSamplerConfig, "ip_adapter=True runs in the fp16 and the bf16 step, not under the fp8 policy (config.set_dtype('fp8'))")
     if not cfg:
         if sampler is None:
             refuse(ValueError, "cfg=False needs a sampler schedule (sampler=<Schedule>): the reference-shaped step() keeps its CFG form")

@@ -72,6 +72,7 @@ class StableDiffusion:
             self.cond_stage_model = namedtuple("CondStageModel", ["transformer"])(
                 transformer=namedtuple("Transformer", ["text_model"])(text_model=CLIPTextTransformer(init=init)))
         self.control_model = None        # a ControlNet (vision/controlnet.py), under the LDM checkpoint's name: attach_control sets it
+        self._ip_model = None            # an IPAdapter (storage/ip_adapter.py): attach_ip_adapter sets it (private: no checkpoint of the model names it)
         self._reset_state(everything=True)
 
     def _reset_state(self, everything=False):
@@ -91,6 +92,7 @@ class StableDiffusion:
         self._x0_init = self._mask = None        # inpaint=True: the clean latent and the (B,1,h,w) mask
         self._cond = self._edit = None           # concat=: the conditioning channels; [0] g_I of the three-branch update
         self._hint_emb = self._control_scales = None                 # control=True
+        self._ip, self._ip_model_compiled, self._ip_kv, self._ip_scales, self._ip_keep = False, None, None, None, None     # the adapter the step captured, ip_adapter=True: image-token K|V (G B, T, kv_n), the scales
         self._seed, self._image_offset, self._cursor = (0, 0), 0, 0  # what start() sets, step_sampler advances
         self._kv_all = self._kv_key = self._ckv_all = self._emb_cur = self._emb_key = self._keep_row = None     # hoisted K|V and time-embedding row
         self._emb_rows = {}
@@ -106,6 +108,24 @@ class StableDiffusion:
         if replace(net.cfg, in_channels=4) != replace(self.model.diffusion_model.cfg, in_channels=4):
             raise ValueError(f"StableDiffusion.attach_control: the ControlNet was built for {net.cfg}, the UNet is {self.model.diffusion_model.cfg}")
         self.control_model = net
+        return self
+
+    def attach_ip_adapter(self, adapter):
+        """Give the model an IPAdapter (storage/ip_adapter.py) built for its UNet: ``compile(..., ip_adapter=True)`` then captures the step whose
+        cross-attentions are the dual launches.  The adapter acts on the UNet only; a ControlNet's cross-attentions stay plain."""
+        from ..storage.ip_adapter import IPAdapter, adapter_paths
+        if not isinstance(adapter, IPAdapter):
+            raise TypeError(f"StableDiffusion.attach_ip_adapter: takes an IPAdapter, got {type(adapter).__name__}")
+        table = adapter_paths(self.model.diffusion_model)
+        if adapter.paths != [(n, p) for n, p, _ in table] or adapter.context_dim != self.model.diffusion_model.cfg.context_dim \
+                or [p.to_k_ip.out_features for p in adapter.ip_adapter.values()] != [st.proj_in._shape[0] for _, _, st in table]:
+            raise ValueError("StableDiffusion.attach_ip_adapter: the adapter was built for another UNet configuration")
+        self._ip_model = adapter
+        return self
+
+    def detach_ip_adapter(self):
+        """Forget the adapter.  A step compiled with ip_adapter=True keeps running on the weights it captured until the next compile."""
+        self._ip_model = None
         return self
 
     # -- reference surface -------------------------------------------------------------------------
@@ -305,7 +325,7 @@ class StableDiffusion:
 
     # -- whole-step HIP graph ------------------------------------------------------------------------
     def compile(self, unconditional_context, context, latent, stream=None, warmup=2, timesteps=None, sampler=None, inpaint=False, concat=None, control=False,
-                cfg=True):
+                cfg=True, ip_adapter=False):
         """Capture one denoising step for these (static) buffers into a HIP graph.  Afterwards
         ``step(timestep, a_t, a_prev, guidance)`` updates ``latent`` in place with one graph launch.
 
@@ -350,17 +370,29 @@ class StableDiffusion:
         None or 1.0 and raise ValueError for anything else.  Not with concat="edit", TF_CFG_PARALLEL or the fp8 policy.  cfg=True with an LCM schedule
         runs the two-branch step with that table (LCM-LoRA at guidance 1-2).
 
+        ``ip_adapter=True`` (with a sampler and an attached IPAdapter, ``attach_ip_adapter``): every cross-attention of the UNet becomes the dual
+        launch (tf_sdpa_dual_16) -- the same number of graph nodes.  The model owns the image tokens' K|V (G B, T, kv_n), zero until
+        ``start(ip_image_embeds=)`` projects it (outside the graph, as the text K|V is), and a device fp32 array with one strength per
+        cross-attention, all ones; ``set_ip_scale`` changes them without a re-capture, and at 0 the step computes what the un-adapted step
+        computes.  Combines with cfg=False, inpaint=True, concat="inpaint", control=True, LoRA, bf16; not with concat="edit", TF_CFG_PARALLEL or
+        the fp8 policy.  (The warm-up steps run every dual instance once before the capture: its first launch sets a function attribute.)
+
         The arguments are remembered: ``set_adapters`` (LoRA) on a compiled model swaps weight handles and calls ``compile`` again with the same ones."""
-        inputs.check_compile(self.model.diffusion_model.cfg.in_channels, self.control_model is not None, config, latent, sampler, inpaint, concat, control, cfg)
+        inputs.check_compile(self.model.diffusion_model.cfg.in_channels, self.control_model is not None, config, latent, sampler, inpaint, concat, control, cfg,
+                             ip_adapter=ip_adapter, has_ip_adapter=self._ip_model is not None)
+        if ip_adapter and warmup < 1:
+            raise ValueError("StableDiffusion.compile: ip_adapter=True needs warmup >= 1 (the first launch of an attention instance cannot be captured)")
         if sampler is not None:
             timesteps = sampler.timesteps
         self._reset_state()
         self._compile_args = dict(unconditional_context=unconditional_context, context=context, latent=latent, warmup=warmup, timesteps=timesteps,
-                                  sampler=sampler, inpaint=inpaint, concat=concat, control=control, cfg=cfg)
+                                  sampler=sampler, inpaint=inpaint, concat=concat, control=control, cfg=cfg, ip_adapter=ip_adapter)
         self._stream = stream or Stream()
         self._latent, self._unc, self._ctx = latent, unconditional_context, context
         self._sched, self._inpaint, self._concat, self._control = sampler, bool(inpaint), concat, bool(control)
         self._groups = 3 if concat == "edit" else 2 if cfg else 1
+        self._ip = bool(ip_adapter)
+        self._ip_model_compiled = self._ip_model if self._ip else None
         if sampler is not None:
             with use_stream(self._stream):
                 self._alloc_sampler_buffers()
@@ -387,6 +419,10 @@ class StableDiffusion:
         if self._control:
             self._hint_emb = DeviceArray.zeros((self._groups * b, self.control_model.cfg.model_channels, h, w), _step_dtype(), "nhwc")
             self._control_scales = DeviceArray.from_numpy(np.ones((16,), np.float32), np.float32, "row")     # one per residual; 16: whole 4-word writes
+        if self._ip:
+            ad = self._ip_model_compiled
+            self._ip_kv = DeviceArray.zeros((self._groups * b, ad.num_tokens, ad.kv_layout()[1]), _step_dtype(), "row")
+            self._ip_scales = DeviceArray.from_numpy(inputs.ip_scales(None, len(ad.paths)), np.float32, "row")
 
     def _hoist(self, sp, timesteps):
         """The private stacked context and -- config.hoist_step_invariants -- what depends on it or on the timestep alone: the K|V projections and
@@ -452,8 +488,9 @@ class StableDiffusion:
     def _unet(self, x2, sp):
         """The UNet's output for the stacked input: plain, from the hoisted row and K|V, or controlled."""
         unet, cn, row, ctx = self.model.diffusion_model, self.control_model, self._emb_cur, self._ctx2
+        ip = (self._ip_model_compiled, self._ip_kv, self._ip_scales) if self._ip else None
         if not self._control:
-            return unet(x2, sp, ctx, shared=None if row is None else (None, row, self._kv_all))     # (step() has put this timestep's row into _emb_cur)
+            return unet(x2, sp, ctx, shared=None if row is None else (None, row, self._kv_all), ip=ip)     # (step() has put this timestep's row into _emb_cur)
         # the UNet's encoder, then the ControlNet on the same stacked latent, then the seam (UNetModel.__call__ calls `residuals` behind its
         # middle block); each model reads its own view of the hoisted row [UNet's | ControlNet's]
         shared_u = shared_c = None
@@ -462,7 +499,7 @@ class StableDiffusion:
             shared_u = (None, row.view((1, nu), "row"), self._kv_all)
             shared_c = (None, row.view((1, row.shape[1] - nu), "row", nu), self._ckv_all)
         residuals = lambda: cn(x2, self._hint_emb, sp, ctx, shared=shared_c)
-        return unet(x2, sp, ctx, shared=shared_u, control=(residuals, self._control_scales))
+        return unet(x2, sp, ctx, shared=shared_u, control=(residuals, self._control_scales), ip=ip)
 
     def _unet_two_chains(self, x2, sp):
         """config.cfg_parallel: the unconditional and the conditional half of the CFG pair (variants/sd.py:31-32) as two independent UNet chains: one
@@ -551,7 +588,8 @@ class StableDiffusion:
         return self._sched
 
     def start(self, seed=None, noise=None, image_offset=0, init_image=None, init_latent=None, mask=None, cond_image=None, cond_mask=None,
-              cond_latent=None, image_guidance=None, control_image=None, control_hint=None, control_scale=None):
+              cond_latent=None, image_guidance=None, control_image=None, control_hint=None, control_scale=None, ip_image_embeds=None, ip_image=None,
+              ip_scale=None):
         """A new image batch for the compiled sampler: sets the latent in place and rewinds the schedule.  ``seed``: the initial latent is
         drawn on the device (tag 0; image b is global image image_offset + b), and the ancestral noise of every step comes from the same seed
         (tag 1); ``noise``: a host (B,C,H,W) array for the initial latent instead (the ancestral noise then uses ``seed``, default 0).
@@ -573,8 +611,15 @@ class StableDiffusion:
         A controlled model (compile(..., control=True)) needs its hint at every start: ``control_image`` (uint8 (B | 1, 8h, 8w, 3), host or device;
         x / 255 on the device) or ``control_hint`` (a host float (B | 1, 3, 8h, 8w) array in [0, 1]) goes through the ControlNet's hint stem once,
         here; a single hint serves every image.  ``control_scale``: the strength of the 13 residuals, one float or one per residual (12 skip
-        connections in input-block order, then the middle block); 1 when not given.  Hint and scales follow a new start without a recompile."""
+        connections in input-block order, then the middle block); 1 when not given.  Hint and scales follow a new start without a recompile.
+
+        An adapted model (compile(..., ip_adapter=True)) needs its image prompt at every start: ``ip_image_embeds``, a host float (B | 1, E) array of
+        CLIP image embeddings.  The conditional group reads the adapter's tokens of the embeddings, the unconditional group its tokens of zeros (the
+        published convention); the image tokens' K|V is projected here, outside the graph.  ``ip_scale``: one float or one per cross-attention (adapter
+        order: down, up, mid); 1 when not given.  ``ip_image`` (uint8 (B, 224, 224, 3)) needs a CLIP vision tower, which this tree does not have yet:
+        it is refused with that reason."""
         self._require_sampler("start")
+        ipa = self._check_ip(ip_image_embeds, ip_image, ip_scale)
         ctrl = self._check_control(control_image, control_hint, control_scale)
         cond = self._check_cond(cond_image, cond_mask, cond_latent, image_guidance)
         latent = self._check_latent(seed, noise, image_offset, init_image, init_latent, mask)
@@ -583,7 +628,53 @@ class StableDiffusion:
             self._write_cond(*cond)
         if ctrl is not None:
             self._write_control(*ctrl)
+        if ipa is not None:
+            self._write_ip(*ipa)
         return self._latent
+
+    def _check_ip(self, ip_image_embeds, ip_image, ip_scale):
+        """start()'s adapter arguments, checked against the compiled model before anything changes: None for a model without ip_adapter=True,
+        else (fp32 (B, E) embeddings, the fp32 scale words)."""
+        if not self._ip:
+            if any(v is not None for v in (ip_image_embeds, ip_image, ip_scale)):
+                raise ValueError("StableDiffusion.start: ip_image_embeds=, ip_image= and ip_scale= need a model compiled with ip_adapter=True")
+            return None
+        if ip_image is not None:
+            raise UnsupportedSamplerConfig("StableDiffusion.start: ip_image= needs a CLIP vision tower (attach_clip_vision), which this tree does not have yet -- "
+                                           "compute the image embeddings elsewhere and pass ip_image_embeds=")
+        if ip_image_embeds is None:
+            raise ValueError("StableDiffusion.start: a model compiled with ip_adapter=True reads its image prompt at every step -- pass ip_image_embeds=")
+        ad = self._ip_model_compiled
+        return inputs.ip_embeds(ip_image_embeds, self._latent.shape[0], ad.embed_dim), inputs.ip_scales(ip_scale, len(ad.paths))
+
+    def _write_ip_scales(self, scales):
+        for q in range(len(scales) // 4):                                # stream-ordered: the values travel as kernel arguments
+            hip.tf_set_step_params(self._ip_scales.ptr + 16 * q, *(float(v) for v in scales[4 * q:4 * q + 4]), _sh())
+
+    def _write_ip(self, embeds, scales):
+        """The scales and the image tokens' K|V of every guidance group, on the sampler stream behind every step already queued: [tokens(0) |
+        tokens(embeds)] for the CFG pair, tokens(embeds) alone for cfg=False."""
+        self.synchronize()
+        ad, b = self._ip_model_compiled, self._latent.shape[0]
+        rows = np.concatenate([np.zeros_like(embeds)] * (self._groups - 1) + [embeds])
+        with use_stream(self._stream):
+            self._write_ip_scales(scales)
+            dev = DeviceArray.from_numpy(rows, _step_dtype(), "row")
+            tokens = ad.tokens(dev)
+            kv = ad.context_kv(tokens)
+            assert kv.shape == self._ip_kv.shape and kv.dtype == self._ip_kv.dtype, (kv.shape, self._ip_kv.shape)
+            hip.tf_memcpy_async(self._ip_kv.ptr, kv.ptr, kv.nbytes, 3, _sh())
+            self._ip_keep = (dev, tokens, kv)                            # (referenced until the kernels have run)
+
+    def set_ip_scale(self, ip_scale):
+        """The adapter's strength -- one float or one per cross-attention -- from the next step on: the captured step reads the values from the
+        device, so nothing is captured again."""
+        self._require_sampler("set_ip_scale")
+        if not self._ip:
+            raise ValueError("StableDiffusion.set_ip_scale: needs a model compiled with ip_adapter=True")
+        scales = inputs.ip_scales(ip_scale, len(self._ip_model_compiled.paths), "set_ip_scale")
+        with use_stream(self._stream, ordered=False):
+            self._write_ip_scales(scales)
 
     def _check_control(self, control_image, control_hint, control_scale):
         """start()'s ControlNet arguments, checked against the compiled model before anything changes: None for a model without control=True, else

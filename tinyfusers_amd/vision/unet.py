@@ -203,8 +203,10 @@ class StepModel:
             kv_all = self.context_kv(context)                                         # every attn2's K|V of the context
         return emb, emb_all, kv_all, br
 
-    def _runner(self, emb, emb_all, kv_all, context):
+    def _runner(self, emb, emb_all, kv_all, context, ip=None):
         bt = self._prepare()
+        # ip = (kv_ip_all (b, T, kv_n), {id(SpatialTransformer): (column offset, scale index)}, kv_n, scales): an IP-Adapter's image-token K|V
+        # for every cross-attention and the device fp32 array of their strengths (UNetModel.__call__(ip=))
 
         def run(x, bb, nxt, force_gn=0, residual=None):
             # nxt = the module that reads this one's output as a single tensor (None across a concat): when it opens
@@ -219,7 +221,11 @@ class StepModel:
                 return bb(x, emb, emb_out=emb_all.view((emb_all.shape[0], n), "row", off), out_gn=gn, out_norm=on)
             if isinstance(bb, SpatialTransformer):
                 c = bb.proj_in.weight.shape[0]
-                return bb(x, context, kv=KVSlice(kv_all, bt["kv_off"][id(bb)], c, bt["kv_n"]), out_gn=gn, out_norm=on)
+                bip = None
+                if ip is not None:
+                    off, idx = ip[1][id(bb)]
+                    bip = (KVSlice(ip[0], off, c, ip[2]), ip[3].ptr + 4 * idx)
+                return bb(x, context, kv=KVSlice(kv_all, bt["kv_off"][id(bb)], c, bt["kv_n"]), out_gn=gn, out_norm=on, ip=bip)
             if isinstance(bb, (Downsample, Upsample)):
                 return bb(x, out_gn=gn, out_norm=on)
             if isinstance(bb, Conv2d):
@@ -298,13 +304,29 @@ class UNetModel(StepModel):
         self.out = [GroupNorm(32, mc, init=init), Tensor.silu, Conv2d(mc, cfg.out_channels, kernel_size=[3, 3], padding=[1, 1], init=init)]
         self._batched = None
 
-    def __call__(self, x, timesteps=None, context=None, shared=None, control=None):
+    def ip_slots(self, adapter):
+        """{id(SpatialTransformer): (column offset in the adapter's K|V GEMM, index of its scale)} for ``adapter`` (storage/ip_adapter.py)."""
+        from ..storage.ip_adapter import adapter_paths
+        offs, _ = adapter.kv_layout()
+        paths = adapter_paths(self)
+        if [(n, p) for n, p, _ in paths] != adapter.paths:
+            raise ValueError("UNetModel.ip_slots: the adapter was built for another UNet")
+        return {id(st): (offs[k], k) for k, (_, _, st) in enumerate(paths)}
+
+    def __call__(self, x, timesteps=None, context=None, shared=None, control=None, ip=None):
         """control = (residuals, scales): a ControlNet's len(input_blocks) + 1 residual tensors (or a callable that returns them, called behind
         the middle block) and the device fp32 array of their strengths.  Behind the middle block one launch (control_add) makes new skip tensors
         and a new middle output, skip_i + s_i residual_i, which carry no statistics: the output path's concat GroupNorms then compute theirs
-        (ff/group_norm.py::_gn, the explicit path), and no producer is asked for concat statistics.  None: the step as it always was."""
+        (ff/group_norm.py::_gn, the explicit path), and no producer is asked for concat statistics.  None: the step as it always was.
+        ip = (adapter, kv_ip_all, scales): an IP-Adapter (storage/ip_adapter.py), its context_kv of the image tokens (b, T, kv_n) and a device fp32
+        array with one strength per cross-attention in adapter order: every cross-attention becomes the dual launch.  None: the plain launches."""
         emb, emb_all, kv_all, br = self._shared(timesteps, context, shared)
-        run = self._runner(emb, emb_all, kv_all, context)
+        if ip is not None:
+            adapter, kv_ip, scales = ip
+            if kv_ip.shape[0] != x.shape[0] or kv_ip.shape[2] != adapter.kv_layout()[1] or scales.dtype != np.float32 or scales.size < len(adapter.paths):
+                raise ValueError(f"UNetModel: ip K|V {kv_ip.shape} / scales {scales.shape} do not fit a batch of {x.shape[0]} and {len(adapter.paths)} cross-attentions")
+            ip = (kv_ip, self.ip_slots(adapter), adapter.kv_layout()[1], scales)
+        run = self._runner(emb, emb_all, kv_all, context, ip)
         x, saved_inputs = self._encode(run, x, br, concat_stats=control is None)
         if control is not None:
             residuals, scales = control

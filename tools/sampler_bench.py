@@ -3,7 +3,7 @@
 tf_cfg_sampler_step_f32) against the DDIM step (tf_cfg_ddim_step_f32), 100 graph replays each, alternated over several rounds; and the
 config-3 end-to-end img/s (CLIP x2 -> steps -> VAE decode, batch 1) at 20 DPM++2M steps against 50 DDIM steps.
 
-    python tools/sampler_bench.py [--replays 100] [--rounds 5] [--images 3] [--dpm-steps 20] [--inpaint] [--concat inpaint|edit] [--control] [--lora] [--lcm]
+    python tools/sampler_bench.py [--replays 100] [--rounds 5] [--images 3] [--dpm-steps 20] [--inpaint] [--concat inpaint|edit] [--control] [--lora] [--lcm] [--ip-adapter]
 --inpaint adds the masked DPM++2M step (tf_cfg_sampler_step_masked_f32, a model compiled with inpaint=True on the same shape, half the
 latent repainted) to the alternation, and the VAE encoder's time for a 512^2 image (StableDiffusion.encode_image).
 --concat adds the DPM++2M step of a concat-conditioned UNet (SD15_INPAINT: 9 input channels, two CFG groups; SD15_EDIT: 8 input channels, three
@@ -12,6 +12,10 @@ image (upload, VAE encoder, conditioning buffer).
 --control adds the controlled DPM++2M step (compile(..., control=True): the same UNet weights plus a synthetic SD-1.5 ControlNet) to the
 alternation, the time of start(control_image=...) for a 512^2 hint (upload, x / 255, the hint stem), and k_control_add's achieved GB/s on the
 13 skip shapes of the step next to tf_add_16 on the same byte count.
+--ip-adapter adds, interleaved with the plain DPM++2M step in the same rounds: the adapted step (compile(..., ip_adapter=True): the same UNet weights
+plus a synthetic ip-adapter_sd15, every cross-attention the fused tf_sdpa_dual_16 launch) and an adapted step that composes what the fused launch
+replaces -- two tf_sdpa_16 launches plus tf_add_16 per cross-attention, built only inside this tool (the image term at scale 1) -- and the time of
+start(ip_image_embeds=) (tokens + the hoisted K_ip | V_ip GEMM); written to profiles/sampler_bench_ip_adapter.json as well.
 --lora adds, for a synthetic adapter of rank 16 and of rank 128 over the 192 UNet attention / FF / proj targets plus the 72 text-encoder targets:
 lora_merge_ms (one set_adapters on an uncompiled model, every launch, wall clock incl. the final sync), lora_merge_gb_s (base read + dst write
 over the launches' device time) next to add_16_gb_s, lora_recapture_ms (set_adapters on a compiled model minus the merge), lora_step_over_plain
@@ -189,6 +193,7 @@ def main():
     ap.add_argument("--concat", choices=["inpaint", "edit"], default=None, help="also time the step of the 9-channel inpainting / 8-channel edit UNet against the plain one")
     ap.add_argument("--control", action="store_true", help="also time the ControlNet-conditioned step against the plain one, start(control_image=), and k_control_add")
     ap.add_argument("--lora", action="store_true", help="also time the LoRA merge (tf_lora_merge_16), the re-capture and the adapted step, for rank 16 and rank 128")
+    ap.add_argument("--ip-adapter", action="store_true", help="also time the IP-Adapter step (fused dual attention) against the plain one and against a composed two-launch form")
     ap.add_argument("--lcm", action="store_true", help="also time the guidance-free step (cfg=False) against the CFG step for DPM++2M and LCM, and LCM-4 cfg=False end to end")
     args = ap.parse_args()
 
@@ -252,6 +257,38 @@ def main():
         ctl_m.attach_control(net).compile(unc, ctx, lat_e, sampler=dpm_sched, control=True)
         hint_img = np.random.default_rng(1).integers(0, 256, (1, 512, 512, 3), dtype=np.uint8)
         ctl_m.start(seed=1234, control_image=hint_img)
+    ipa = {}                                                               # --ip-adapter: key -> (model, latent)
+    if args.ip_adapter:
+        import tinyfusers_amd.attention.attention as attn_mod
+        from tinyfusers_amd.attention.sdpa import sdpa_strided
+        from tinyfusers_amd.storage.ip_adapter import IPAdapter
+        from tinyfusers_amd.storage.tensor import dtag
+
+        def composed(o, q, k, v, k2, v2, scale_ptr, b, nh, tq, tk, tk2, hs, qs, ks, vs, k2s, v2s, os_):
+            """what sdpa_dual_strided replaces: two plain attention launches and an add (scale 1; the tool's own arm, never in the library)"""
+            o2 = T.DeviceArray.empty(o.shape, o.dtype, "row")
+            sdpa_strided(o, q, k, v, b, nh, tq, tk, hs, qs, ks, vs, os_)
+            sdpa_strided(o2, q, k2, v2, b, nh, tq, tk2, hs, qs, k2s, v2s, os_)
+            hip.tf_add_16(dtag(o.dtype), o.ptr, o.ptr, o2.ptr, o.size, T._sh())
+            o._base = (o._base, o2)                                        # (referenced while the launches are queued / captured)
+            return o
+        ip_emb = synth_normal(7, "ip.embeds", (1, 1024))
+        fused_fn = attn_mod.sdpa_dual_strided
+        for key, fn in (("dpmpp2m_ip_fused", fused_fn), ("dpmpp2m_ip_composed", composed)):
+            m = StableDiffusion()
+            update_state(m.model.diffusion_model, state, "")
+            ad = IPAdapter(m.model.diffusion_model, 4, 1024)
+            with contextlib.redirect_stdout(io.StringIO()):
+                update_state(ad, {k_: (synth_normal(3, k_, s_, 0.03) + (1.0 if k_ == "image_proj.norm.weight" else 0.0)).astype(np.float16)
+                                  for k_, s_ in ad.expected_shapes().items()}, "")
+            lat_i = m.latent_from_numpy(noise)
+            attn_mod.sdpa_dual_strided = fn
+            try:
+                m.attach_ip_adapter(ad).compile(unc, ctx, lat_i, sampler=dpm_sched, ip_adapter=True)
+            finally:
+                attn_mod.sdpa_dual_strided = fused_fn
+            m.start(seed=1234, ip_image_embeds=ip_emb)
+            ipa[key] = (m, lat_i)
     few = {}                                                               # --lcm: key -> (model, latent, schedule, guidance)
     if args.lcm:
         from tinyfusers_amd.variants.samplers import LCM
@@ -305,6 +342,18 @@ def main():
                 hip.tf_memcpy_async(lat_e.ptr, lat0.ptr, lat_e.nbytes, 3, ctl_m._stream.handle)
             ctl_m.step_sampler(i, 7.5)
 
+    def ipa_replays(key):
+        m, lat_i = ipa[key]
+        k = len(dpm_sched.timesteps)
+
+        def replays(n):
+            for s in range(n):
+                i = s % k
+                if i == 0:
+                    hip.tf_memcpy_async(lat_i.ptr, lat0.ptr, lat_i.nbytes, 3, m._stream.handle)
+                m.step_sampler(i, 7.5)
+        return replays
+
     def few_replays(key):
         m, lat_f, sched, g = few[key]
         k = len(sched.timesteps)
@@ -341,6 +390,10 @@ def main():
     if args.control:
         ctl_replays(20)
         step_ms["dpmpp2m_control"] = []
+    ipa_fn = {k: ipa_replays(k) for k in ipa}
+    for k in ipa:
+        ipa_fn[k](20)
+        step_ms[k] = []
     few_fn = {k: few_replays(k) for k in few}
     for k in few:
         few_fn[k](20)
@@ -354,6 +407,8 @@ def main():
             step_ms[cat_key].append(timed(cat_m, cat_replays, args.replays))
         if args.control:
             step_ms["dpmpp2m_control"].append(timed(ctl_m, ctl_replays, args.replays))
+        for k in ipa:
+            step_ms[k].append(timed(ipa[k][0], ipa_fn[k], args.replays))
         for k in few:
             step_ms[k].append(timed(few[k][0], few_fn[k], args.replays))
     med = {k: float(np.median(v)) for k, v in step_ms.items()}
@@ -390,6 +445,22 @@ def main():
             st.append(time.perf_counter() - t0)                          # (includes the 0.75 MB host -> device upload of the hint)
         extra.update({"dpmpp2m_control_step_ms": round(med["dpmpp2m_control"], 4), "control_over_plain": round(med["dpmpp2m_control"] / med["dpmpp2m"], 4),
                       "start_control_image_512_ms": round(1e3 * float(np.median(st[1:])), 3), **control_add_bench(T, hip, ctl_m, timed, args)})
+
+    if args.ip_adapter:
+        fm = ipa["dpmpp2m_ip_fused"][0]
+        st = []
+        for r in range(args.rounds + 1):
+            t0 = time.perf_counter()
+            fm.start(seed=1234, ip_image_embeds=ip_emb)
+            fm.synchronize()
+            st.append(time.perf_counter() - t0)
+        for k in ipa:
+            assert np.isfinite(ipa[k][1].numpy()).all(), k
+        spread_ms = lambda k: round(max(step_ms[k]) - min(step_ms[k]), 4)
+        extra.update({"dpmpp2m_ip_fused_step_ms": round(med["dpmpp2m_ip_fused"], 4), "dpmpp2m_ip_composed_step_ms": round(med["dpmpp2m_ip_composed"], 4),
+                      "ip_fused_over_plain": round(med["dpmpp2m_ip_fused"] / med["dpmpp2m"], 4), "ip_composed_over_plain": round(med["dpmpp2m_ip_composed"] / med["dpmpp2m"], 4),
+                      "start_ip_image_embeds_ms": round(1e3 * float(np.median(st[1:])), 3), "start_ip_image_ms": "not measured (no CLIP vision tower in the tree)",
+                      "ip_round_spread_ms": {k: spread_ms(k) for k in ("dpmpp2m", "dpmpp2m_ip_fused", "dpmpp2m_ip_composed")}})
 
     if args.lora:
         extra.update(lora_bench(T, hip, timed, args, state, ddim_m, unc, ctx, noise, dpm_sched, dpm_m, dpm_replays, lat0))
@@ -445,6 +516,9 @@ def main():
         out["e2e_lcm4_nocfg"] = e2e(lcm1_m, 4, lcm_sample, uncond=False)
         out["e2e_lcm4_nocfg_over_dpmpp2m"] = round(out["e2e_lcm4_nocfg"]["img_per_s"] / out["e2e_dpmpp2m"]["img_per_s"], 3)
     print(json.dumps(out))
+    if args.ip_adapter:
+        with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sampler_bench_ip_adapter.json"), "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
     del arena
 
 

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Graph-timed SDPA shapes of the SD-1.5 step (self + cross attention at every level) through tf_sdpa_f16.
-usage: tools/sdpa_bench.py [d40] [--ks 0|1|2]    (--ks: tf_sdpa_force_split -- 0 per-shape choice, 1 unsplit, 2 key slices wherever a split kernel exists)"""
+usage: tools/sdpa_bench.py [d40] [--ks 0|1|2]    (--ks: tf_sdpa_force_split -- 0 per-shape choice, 1 unsplit, 2 key slices wherever a split kernel exists)
+       tools/sdpa_bench.py --dual               (the cross-attentions as plain / dual (tf_sdpa_dual_16) / two launches + add, interleaved rounds)"""
 import os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -14,7 +15,39 @@ SHAPES = [("self 64^2 d40", 2, 8, 4096, 4096, 40), ("self 32^2 d80", 2, 8, 1024,
           ("c5 self 96^2 d40", 8, 8, 9216, 9216, 40), ("c5 cross 96^2 d40", 8, 8, 9216, 77, 40), ("c5 self 48^2 d80", 8, 8, 2304, 2304, 80)]
 
 
+def dual(rounds=3, tk2=4):
+    """--dual: the SD-1.5 cross-attentions (CFG batch 2 and batch 1) three ways, interleaved over `rounds` rounds in one process: the plain launch
+    (tf_sdpa_16, text keys alone), the dual launch (tf_sdpa_dual_16, + `tk2` image keys) and what the dual launch replaces -- two tf_sdpa_16 launches and
+    tf_add_16 (the image term at scale 1).  One line per shape: the median of each arm and its spread (max - min) between rounds, in us."""
+    rng = np.random.default_rng(0)
+    one = T.DeviceArray.from_numpy(np.float32([1.0]), np.float32, "row")
+    for name, b, nh, tq, tk, hs in [s for s in SHAPES if s[0].startswith("cross")] + [("cross 64^2 d40 B1", 1, 8, 4096, 77, 40), ("cross 32^2 d80 B1", 1, 8, 1024, 77, 80)]:
+        c = nh * hs
+        arr = lambda t: T.DeviceArray.from_numpy(rng.standard_normal((b, t, c)).astype(np.float16), layout="row")
+        q, k, v, k2, v2 = arr(tq), arr(tk), arr(tk), arr(tk2), arr(tk2)
+        o, o2 = T.DeviceArray.empty((b, tq, c), np.float16, "row"), T.DeviceArray.empty((b, tq, c), np.float16, "row")
+        s3 = lambda t: (t * c, hs, c)
+
+        def plain():
+            hip.tf_sdpa_16(0, o.ptr, q.ptr, k.ptr, v.ptr, b, nh, tq, tk, hs, *s3(tq), *s3(tk), *s3(tk), *s3(tq), 0, st.handle)
+
+        def fused():
+            hip.tf_sdpa_dual_16(0, o.ptr, q.ptr, k.ptr, v.ptr, tk, k2.ptr, v2.ptr, tk2, one.ptr, b, nh, tq, hs, *s3(tq), *s3(tk), *s3(tk), *s3(tk2), *s3(tk2), *s3(tq), st.handle)
+
+        def composed():
+            plain()
+            hip.tf_sdpa_16(0, o2.ptr, q.ptr, k2.ptr, v2.ptr, b, nh, tq, tk2, hs, *s3(tq), *s3(tk2), *s3(tk2), *s3(tq), 0, st.handle)
+            hip.tf_add_16(0, o.ptr, o.ptr, o2.ptr, o.size, st.handle)
+        us = {f.__name__: [] for f in (plain, fused, composed)}
+        for _ in range(rounds):
+            for f in (plain, fused, composed):
+                us[f.__name__].append(time_call(f))
+        print(f"{name:18s} B={b} Tq={tq:5d} Tk={tk}+{tk2} d={hs:3d}  " + "  ".join(f"{n} {np.median(t):7.2f} us (spread {max(t) - min(t):.2f})" for n, t in us.items()), flush=True)
+
+
 def main():
+    if "--dual" in sys.argv:
+        return dual()
     rng = np.random.default_rng(0)
     ks = int(sys.argv[sys.argv.index("--ks") + 1]) if "--ks" in sys.argv else 0
     split = hasattr(lib, "tf_sdpa_force_split")          # (an earlier library under TF_LIB_PATH has no key slices)
