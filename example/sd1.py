@@ -16,6 +16,7 @@ BASELINE config 3: full 50-step sampler, batch 1, end-to-end img/s.
     python -m example.sd1 --steps 20 --sampler dpmpp2m --lora style.safetensors:0.8 --lora lcm.safetensors:1:0   # LoRA adapters, FILE[:w[:w_te]], merged on the device
     python -m example.sd1 --steps 4 --sampler lcm --no-cfg --lora lcm.safetensors:1:0   # few-step sampling: the LCM sampler on the guidance-free single-branch step
     python -m example.sd1 --steps 20 --sampler dpmpp2m --ip-adapter ip-adapter_sd15.safetensors --ip-embeds e.npy [--ip-scale 0.6]   # IP-Adapter: an image prompt, as CLIP image embeddings (1, 1024)
+    python -m example.sd1 --steps 20 --sampler dpmpp2m --ip-adapter ip-adapter_sd15.safetensors --ip-image x.npy [--clip-vision image_encoder.safetensors]   # ... or as the picture itself, uint8 (224, 224, 3): the CLIP ViT-H tower runs on the device
 With --ckpt the configuration is read off the checkpoint's conv_in (4, 9 or 8 input channels); --concat picks it on synthetic weights.
 """
 import argparse
@@ -62,8 +63,10 @@ if __name__ == "__main__":
                     help="condition on an image prompt through an IP-Adapter (ip-adapter_sd15 .safetensors / .bin); without FILE: synthetic adapter weights")
     ap.add_argument("--ip-embeds", default="", help="with --ip-adapter: the CLIP image embeddings of the prompt image, a float (1, E) .npy (E = 1024 for ViT-H); "
                                                     "with synthetic adapter weights a seeded vector stands in when not given")
-    ap.add_argument("--ip-image", default="", help="with --ip-adapter: the prompt image itself -- needs a CLIP vision tower (--clip-vision), which this tree does not have yet")
-    ap.add_argument("--clip-vision", default="", help="with --ip-image: the CLIP ViT-H image encoder's checkpoint (not supported yet)")
+    ap.add_argument("--ip-image", default="", help="with --ip-adapter: the prompt image itself (.npy or an image file), uint8 (S, S, 3) ALREADY resized and centre-cropped to the "
+                                                   "image tower's size (224 for ViT-H); the CLIP vision tower turns it into the embeddings on the device")
+    ap.add_argument("--clip-vision", default="", help="with --ip-image: the CLIP image encoder's checkpoint (CLIPVisionModelWithProjection .safetensors / .bin); "
+                                                      "default: synthetic ViT-H weights")
     ap.add_argument("--ip-scale", type=float, default=None, help="with --ip-adapter: the adapter's strength (default 1.0)")
     args = ap.parse_args()
     if (args.ip_embeds or args.ip_image or args.clip_vision or args.ip_scale is not None) and args.ip_adapter is None:
@@ -71,10 +74,12 @@ if __name__ == "__main__":
     if args.ip_adapter is not None:
         if not args.sampler:
             ap.error("--ip-adapter needs --sampler")
-        if args.ip_image or args.clip_vision:
-            ap.error("--ip-image / --clip-vision: the CLIP vision tower is not in this tree yet -- compute the image embeddings elsewhere and pass --ip-embeds")
-        if args.ip_adapter and not args.ip_embeds:
-            ap.error("--ip-adapter FILE needs --ip-embeds (the CLIP image embeddings of the prompt image)")
+        if args.ip_image and args.ip_embeds:
+            ap.error("--ip-image and --ip-embeds: pass one of them")
+        if args.clip_vision and not args.ip_image:
+            ap.error("--clip-vision needs --ip-image")
+        if args.ip_adapter and not (args.ip_embeds or args.ip_image):
+            ap.error("--ip-adapter FILE needs --ip-embeds (the CLIP image embeddings of the prompt image) or --ip-image")
         if args.concat == "edit":
             ap.error("--ip-adapter on an InstructPix2Pix checkpoint is not supported")
     loras = []
@@ -183,6 +188,12 @@ if __name__ == "__main__":
             with contextlib.redirect_stdout(io.StringIO()):
                 update_state(adapter, astate, "")
         model.attach_ip_adapter(adapter)
+        if args.ip_image:
+            from dataclasses import replace
+            from tinyfusers_amd.vae.clip_vision import VIT_H, ClipVision, synthetic_state
+            with contextlib.redirect_stdout(io.StringIO()):
+                tower = ClipVision.load(args.clip_vision or synthetic_state(replace(VIT_H, projection=adapter.embed_dim), 3))
+            model.attach_clip_vision(tower)
     print(f"weights installed in {time.time() - t0:.1f}s")
     if loras:                                                    # before the prompts are encoded (text-encoder adapters) and before compile
         t0 = time.perf_counter()
@@ -256,7 +267,16 @@ if __name__ == "__main__":
         cond_kw = {"control_image": hint}
         if args.control_scale is not None:
             cond_kw["control_scale"] = args.control_scale
-    if args.ip_adapter is not None:
+    if args.ip_adapter is not None and args.ip_image:
+        ip_image = load_array(args.ip_image, "RGB")
+        ip_image = ip_image[None] if ip_image.ndim == 3 else ip_image
+        size = tower.cfg.image
+        if ip_image.dtype != np.uint8 or ip_image.shape != (1, size, size, 3):
+            sys.exit(f"--ip-image: expected one uint8 ({size}, {size}, 3) image (resize and centre-crop it first), got {ip_image.dtype} {ip_image.shape}")
+        cond_kw = dict(cond_kw, ip_image=ip_image)
+        if args.ip_scale is not None:
+            cond_kw["ip_scale"] = args.ip_scale
+    elif args.ip_adapter is not None:
         embeds = np.load(args.ip_embeds) if args.ip_embeds else synth_normal(args.seed, "sd.ip_embeds", (1, adapter.embed_dim))
         embeds = np.asarray(embeds, np.float32).reshape(1, -1) if np.asarray(embeds).ndim == 1 else np.asarray(embeds, np.float32)
         if embeds.shape != (1, adapter.embed_dim):

@@ -158,7 +158,7 @@ float tf_prof_overhead_us(void);   /* the per-bracket event overhead tf_prof_ena
 int tf_prof_dump(const char* csv_path);   /* per-shape table: M,N,K,taps,tile,split-K,launches,ms,TFLOP/s */
 /* the same event brackets around the launches of the other kernel families of the step while tf_prof_enable(1) is on (eager launches only):
  * family 1 = GroupNorm (k_gn_stats / k_gn_apply; ff/group_norm.py:3-21), 2 = the split-K reduce launches (incl. the forms that emit / apply the next
- * GroupNorm), 3 = LayerNorm (ff/layer_norm.py:8-49), 4 = SDPA (attention/sdpa.py:53-77).  `work` = the launches' ALGORITHMIC work: HBM bytes
+ * GroupNorm), 3 = LayerNorm (ff/layer_norm.py:8-49), 4 = SDPA (attention/sdpa.py:53-77), 5 = the image tower's input edge and exact GELU (tf_vit_patchify_u8_16, tf_gelu_erf_16; HBM bytes).  `work` = the launches' ALGORITHMIC work: HBM bytes
  * (every operand read once, every result written once) for families 1-3, FLOPs (4 B NH Tq Tk d) for family 4 -- what bench.py prices against
  * the 8 TB/s HBM roof / the MFMA peak */
 int tf_prof_read_family(int family, double* ms, double* work, long long* launches);
@@ -600,6 +600,27 @@ typedef struct { const void* up; const void* down_t; int rp; float scale; } tfLo
  * to the accumulator, the base is added in fp32 and the sum is rounded once.  scale_i == 0 contributes nothing whatever the adapter holds; with
  * every scale 0 dst has base's bits.  Any N, Kd >= 1; dst and base are distinct buffers, base is only read.  No atomics: deterministic */
 int tf_lora_merge_16(int dtype, void* dst, const void* base, const void* table, int n_adapters, int N, int Kd, tfStream_t s);
+
+/* ---- CLIP ViT image tower (csrc/vit.hip; vae/clip_vision.py, the image-prompt front end of the IP-Adapter): what a ViT needs beyond the text
+ * tower's kernels (vae/encoder.py:36-81, ff/nn.py:25-34).  dtype tags every 16-bit tensor (TF_DTYPE_F16 / TF_DTYPE_BF16); all three check their
+ * arguments before the device is touched (TF_E_ARG, the message names the entry), store with plain vector stores and use no atomics, so a graph
+ * replay is bit-identical to the eager launch; every 16-bit tensor must be 16-byte aligned. */
+/* The input edge: image_u8 (B, S, S, 3) uint8 -> out (B (S/P)^2, Kpad), the patch matrix the stride-P patch-embedding conv reads as a GEMM.  Row
+ * (b, py, px); column ky 3P + kx 3 + c holds fmaf((float)u8, scale3[c], shift3[c]) -- fp32, rounded once to 16 bits -- of pixel (py P + ky, px P + kx),
+ * channel c, so one patch row is 3P contiguous image bytes; columns 3 P^2 .. Kpad - 1 are zero.  scale3 / shift3: three floats each ON THE HOST (they
+ * travel as kernel arguments; scale = 1 / (255 std), shift = -mean / std).  S % P == 0, Kpad % 8 == 0, Kpad >= 3 P^2, P <= 64.  With the (width, 3, P, P)
+ * conv weight re-packed to that column order and zero-padded to Kpad, out . W^T is the bias-free convolution of the normalised image. */
+int tf_vit_patchify_u8_16(int dtype, void* out, const void* image_u8, int B, int S, int P, int Kpad, const float* scale3, const float* shift3,
+                          tfStream_t stream);
+/* Token assembly + pre-LayerNorm in one launch: out (B, T, D) = LayerNorm(e) gamma + beta with e[b, 0] = class_emb + pos_emb[0] and
+ * e[b, 1 + p] = patch_out[b, p] + pos_emb[1 + p] (patch_out (B, T - 1, D), class_emb (D), pos_emb (T, D)); e is kept in fp32 and never stored.
+ * D a multiple of 8, <= 2560 (the register form of tf_layer_norm_f16, ff/layer_norm.py:8-49); statistics two-pass in fp32.  Profiled in family 3
+ * (tf_vit_patchify_u8_16 and tf_gelu_erf_16: family 5). */
+int tf_vit_embed_ln_16(int dtype, void* out, const void* patch_out, const void* class_emb, const void* pos_emb, const void* gamma, const void* beta,
+                       int B, int T, int D, float eps, tfStream_t stream);
+/* The exact GELU (storage/tensor.py:80-82 is the tanh form, ff/nn.py:25-34 the quick form): y = 0.5 x erfc(-x / sqrt 2) in fp32 -- the form that
+ * does not cancel in the negative tail -- within 1 ulp of the 16-bit type of the correctly rounded value for every finite input.  y == x allowed. */
+int tf_gelu_erf_16(int dtype, void* y, const void* x, long long n, tfStream_t stream);
 
 /* ---- ControlNet (csrc/control.hip; vision/controlnet.py): a second copy of the encoder half of vision/unet.py:51-76 whose 13 outputs are
  * added to what the UNet saves for its skip concats (vision/unet.py:72) and to its middle block's output, inside the captured step. */

@@ -239,11 +239,13 @@ class SpatialTransformer:
 class CLIPAttention:
     """attention/attention.py:78-104 -- 12-head causal self-attention of the CLIP text encoder.  q/k/v run as one
     (3*768, 768) GEMM with the LayerNorm in front folded in; heads are read through strides; unlike CrossAttention
-    the reference merges the heads back WITH the transpose (:100), i.e. the standard (b, t, h*d) layout."""
+    the reference merges the heads back WITH the transpose (:100), i.e. the standard (b, t, h*d) layout.  ``embed_dim`` / ``num_heads``: the
+    text tower's 768 / 12 by default; the CLIP ViT image tower (vae/clip_vision.py) runs the same layer at 1280 / 16, unmasked."""
 
-    def __init__(self, init=True):
-        self.embed_dim = 768
-        self.num_heads = 12
+    def __init__(self, init=True, embed_dim=768, num_heads=12):
+        assert embed_dim % num_heads == 0, (embed_dim, num_heads)
+        self.embed_dim = embed_dim
+        self.num_heads = num_heads
         self.head_dim = self.embed_dim // self.num_heads
         self.k_proj = Linear(self.embed_dim, self.embed_dim, init=init)
         self.v_proj = Linear(self.embed_dim, self.embed_dim, init=init)
@@ -274,7 +276,7 @@ class CLIPAttention:
         else:
             w, bias = self._qkv(None)
             qkv = linear_f16(hidden_states, w, bias)
-        o = DeviceArray.empty((b, t, c), np.float16, "row")
+        o = DeviceArray.empty((b, t, c), hidden_states.dtype, "row")
         if general:
             def heads_of(off):                                     # columns off .. off + c of qkv -> (b, heads, t, d), contiguous
                 out = DeviceArray.empty((b, nh, t, hs), np.float16, "row")

@@ -43,7 +43,7 @@ static inline hipStream_t tf_hs(struct tfStream_st* s) { return s ? s->s : (hipS
 // ---- per-launch profiling of kernel FAMILIES with HIP events on the launch stream (runtime.hip; bench.py's roofline legs).  While
 // tf_prof_enable(1) is on, a launcher brackets its kernel with `TfProfScope scope(family, work, stream);` -- work = the launch's algorithmic
 // HBM bytes (norm / reduce families) or FLOPs (SDPA) -- and tf_prof_read_family hands back accumulated milliseconds, work and launches.
-enum { TF_PROF_FAM_GROUP_NORM = 1, TF_PROF_FAM_SPLITK_REDUCE = 2, TF_PROF_FAM_LAYER_NORM = 3, TF_PROF_FAM_SDPA = 4, TF_PROF_NFAM = 5 };
+enum { TF_PROF_FAM_GROUP_NORM = 1, TF_PROF_FAM_SPLITK_REDUCE = 2, TF_PROF_FAM_LAYER_NORM = 3, TF_PROF_FAM_SDPA = 4, TF_PROF_FAM_VIT_ELEMENTWISE = 5, TF_PROF_NFAM = 6 };
 extern bool g_tf_prof;
 extern float g_tf_prof_overhead_ms;     // what an event bracket reads beyond the kernel's own duration (measured by tf_prof_enable, csrc/gemm.hip)
 void tf_prof_fam_reset();

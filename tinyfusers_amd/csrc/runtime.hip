@@ -54,7 +54,7 @@ void tf_prof_fam_add(int family, double work, double ms) {
 extern "C" {
 
 int tf_prof_read_family(int family, double* ms, double* work, long long* launches) {
-  TF_REQUIRE(family >= 1 && family < TF_PROF_NFAM, "tf_prof_read_family: family=%d (1 GroupNorm, 2 split-K reduce, 3 LayerNorm, 4 SDPA)", family);
+  TF_REQUIRE(family >= 1 && family < TF_PROF_NFAM, "tf_prof_read_family: family=%d (1 GroupNorm, 2 split-K reduce, 3 LayerNorm, 4 SDPA, 5 ViT patchify / exact GELU)", family);
   for (auto& r : g_fam_pending) {
     float t = 0.f;
     TF_HIP(hipEventSynchronize(r.b));

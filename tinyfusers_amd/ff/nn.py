@@ -4,7 +4,7 @@ alternating value / gate so that both halves of a pair land in the same MFMA lan
 import numpy as np
 
 from ..native import hip
-from ..storage.tensor import DeviceArray, Tensor, _sh
+from ..storage.tensor import DeviceArray, Tensor, _sh, dtag
 from .linear import Linear, fold_layer_norm, linear_f16, linear_ln_f16
 
 
@@ -91,11 +91,15 @@ class FeedForward:
 
 class CLIPMLP:
     """ff/nn.py:25-34 -- fc1 -> quick_gelu -> fc2.  ``ln``: the LayerNorm in front of the block, folded into fc1;
-    ``residual`` is added in fc2's epilogue (vae/encoder.py:62-65)."""
+    ``residual`` is added in fc2's epilogue (vae/encoder.py:62-65).  ``dim`` / ``hidden`` / ``act``: the text tower's 768 / 3072 / "quick_gelu" by
+    default; "gelu" is the exact (erf) GELU of the CLIP ViT image tower (tf_gelu_erf_16, in place on fc1's output)."""
 
-    def __init__(self, init=True):
-        self.fc1 = Linear(768, 3072, init=init)
-        self.fc2 = Linear(3072, 768, init=init)
+    def __init__(self, init=True, dim=768, hidden=3072, act="quick_gelu"):
+        if act not in ("quick_gelu", "gelu"):
+            raise ValueError(f"CLIPMLP: act= takes 'quick_gelu' or 'gelu', got {act!r}")
+        self.act = act
+        self.fc1 = Linear(dim, hidden, init=init)
+        self.fc2 = Linear(hidden, dim, init=init)
 
     def _folded(self, ln):
         key = (self.fc1.weight.wkey, self.fc1.bias.wkey, ln.weight.wkey, ln.bias.wkey)
@@ -105,4 +109,7 @@ class CLIPMLP:
 
     def __call__(self, hidden_states, residual=None, ln=None):
         h = linear_ln_f16(hidden_states, self._folded(ln), ln.eps) if ln is not None else self.fc1(hidden_states)
+        if self.act == "gelu":
+            hip.tf_gelu_erf_16(dtag(h.dtype), h.ptr, h.ptr, h.size, _sh())
+            return self.fc2(h, residual=residual)
         return self.fc2(Tensor.quick_gelu(h), residual=residual)

@@ -73,6 +73,7 @@ class StableDiffusion:
                 transformer=namedtuple("Transformer", ["text_model"])(text_model=CLIPTextTransformer(init=init)))
         self.control_model = None        # a ControlNet (vision/controlnet.py), under the LDM checkpoint's name: attach_control sets it
         self._ip_model = None            # an IPAdapter (storage/ip_adapter.py): attach_ip_adapter sets it (private: no checkpoint of the model names it)
+        self._clip_vision = None         # a ClipVision (vae/clip_vision.py): attach_clip_vision sets it; start(ip_image=) runs it
         self._reset_state(everything=True)
 
     def _reset_state(self, everything=False):
@@ -96,7 +97,7 @@ class StableDiffusion:
         self._seed, self._image_offset, self._cursor = (0, 0), 0, 0  # what start() sets, step_sampler advances
         self._kv_all = self._kv_key = self._ckv_all = self._emb_cur = self._emb_key = self._keep_row = None     # hoisted K|V and time-embedding row
         self._emb_rows = {}
-        self._ctx_tmp = self._kv_tmp = self._start_keep = self._cond_keep = self._control_keep = None   # referenced until their kernels have run
+        self._ctx_tmp = self._kv_tmp = self._start_keep = self._cond_keep = self._control_keep = self._ip_tower_keep = None   # referenced until their kernels have run
 
     def attach_control(self, net):
         """Give the model a ControlNet (vision/controlnet.py) built for the UNet's configuration: ``compile(..., control=True)`` then captures
@@ -120,7 +121,27 @@ class StableDiffusion:
         if adapter.paths != [(n, p) for n, p, _ in table] or adapter.context_dim != self.model.diffusion_model.cfg.context_dim \
                 or [p.to_k_ip.out_features for p in adapter.ip_adapter.values()] != [st.proj_in._shape[0] for _, _, st in table]:
             raise ValueError("StableDiffusion.attach_ip_adapter: the adapter was built for another UNet configuration")
+        if self._clip_vision is not None:
+            self._check_tower_fits(self._clip_vision, adapter, "attach_ip_adapter")
         self._ip_model = adapter
+        return self
+
+    @staticmethod
+    def _check_tower_fits(tower, adapter, who):
+        if tower.cfg.projection != adapter.embed_dim:
+            raise ValueError(f"StableDiffusion.{who}: the CLIP vision tower projects to {tower.cfg.projection} values, the IP-Adapter's image "
+                             f"projection reads {adapter.embed_dim}")
+
+    def attach_clip_vision(self, tower):
+        """Give the model a CLIP image tower (vae/clip_vision.py::ClipVision): ``start(ip_image=)`` then turns a picture into the image embeddings
+        on the device.  Its projection width must be the attached adapter's embedding width (checked here and in attach_ip_adapter, whichever
+        comes second).  Nothing is captured again: the tower runs in start(), outside the step's graph."""
+        from ..vae.clip_vision import ClipVision
+        if not isinstance(tower, ClipVision):
+            raise TypeError(f"StableDiffusion.attach_clip_vision: takes a ClipVision, got {type(tower).__name__}")
+        if self._ip_model is not None:
+            self._check_tower_fits(tower, self._ip_model, "attach_clip_vision")
+        self._clip_vision = tower
         return self
 
     def detach_ip_adapter(self):
@@ -616,8 +637,9 @@ class StableDiffusion:
         An adapted model (compile(..., ip_adapter=True)) needs its image prompt at every start: ``ip_image_embeds``, a host float (B | 1, E) array of
         CLIP image embeddings.  The conditional group reads the adapter's tokens of the embeddings, the unconditional group its tokens of zeros (the
         published convention); the image tokens' K|V is projected here, outside the graph.  ``ip_scale``: one float or one per cross-attention (adapter
-        order: down, up, mid); 1 when not given.  ``ip_image`` (uint8 (B, 224, 224, 3)) needs a CLIP vision tower, which this tree does not have yet:
-        it is refused with that reason."""
+        order: down, up, mid); 1 when not given.  ``ip_image`` (uint8 (B | 1, S, S, 3), host or device, S the tower's image size: 224 for ViT-H; resized
+        and cropped by the caller) instead of ``ip_image_embeds``: the attached CLIP vision tower (``attach_clip_vision``) computes the embeddings on
+        the device, ordered into the sampler stream; [0 | embeddings] for the CFG pair is built there too.  Without a tower it is refused."""
         self._require_sampler("start")
         ipa = self._check_ip(ip_image_embeds, ip_image, ip_scale)
         ctrl = self._check_control(control_image, control_hint, control_scale)
@@ -639,13 +661,23 @@ class StableDiffusion:
             if any(v is not None for v in (ip_image_embeds, ip_image, ip_scale)):
                 raise ValueError("StableDiffusion.start: ip_image_embeds=, ip_image= and ip_scale= need a model compiled with ip_adapter=True")
             return None
+        if ip_image is not None and ip_image_embeds is not None:
+            raise ValueError("StableDiffusion.start: pass ip_image= or ip_image_embeds=, not both")
+        ad, b = self._ip_model_compiled, self._latent.shape[0]
         if ip_image is not None:
-            raise UnsupportedSamplerConfig("StableDiffusion.start: ip_image= needs a CLIP vision tower (attach_clip_vision), which this tree does not have yet -- "
-                                           "compute the image embeddings elsewhere and pass ip_image_embeds=")
+            tower = self._clip_vision
+            if tower is None:
+                raise UnsupportedSamplerConfig("StableDiffusion.start: ip_image= needs a CLIP vision tower -- attach_clip_vision(ClipVision.load(FILE)) first, "
+                                               "or compute the image embeddings elsewhere and pass ip_image_embeds=")
+            self._check_tower_fits(tower, ad, "start")
+            if dtag(tower.dtype) != dtag(_step_dtype()):
+                raise ValueError("StableDiffusion.start: the CLIP vision tower's weights and the step hold different 16-bit types (load both under one config.dtype)")
+            s = tower.cfg.image
+            rule = f"StableDiffusion.start: ip_image must be uint8 {(b, s, s, 3)} (or one image for all) for the compiled latent and the attached tower"
+            return inputs.u8_image(ip_image, rule, (s, s), (1, b))[0], inputs.ip_scales(ip_scale, len(ad.paths))
         if ip_image_embeds is None:
-            raise ValueError("StableDiffusion.start: a model compiled with ip_adapter=True reads its image prompt at every step -- pass ip_image_embeds=")
-        ad = self._ip_model_compiled
-        return inputs.ip_embeds(ip_image_embeds, self._latent.shape[0], ad.embed_dim), inputs.ip_scales(ip_scale, len(ad.paths))
+            raise ValueError("StableDiffusion.start: a model compiled with ip_adapter=True reads its image prompt at every step -- pass ip_image_embeds= or ip_image=")
+        return inputs.ip_embeds(ip_image_embeds, b, ad.embed_dim), inputs.ip_scales(ip_scale, len(ad.paths))
 
     def _write_ip_scales(self, scales):
         for q in range(len(scales) // 4):                                # stream-ordered: the values travel as kernel arguments
@@ -653,18 +685,44 @@ class StableDiffusion:
 
     def _write_ip(self, embeds, scales):
         """The scales and the image tokens' K|V of every guidance group, on the sampler stream behind every step already queued: [tokens(0) |
-        tokens(embeds)] for the CFG pair, tokens(embeds) alone for cfg=False."""
+        tokens(embeds)] for the CFG pair, tokens(embeds) alone for cfg=False.  ``embeds``: the checked fp32 host (B, E) array, or the checked uint8
+        image batch (B | 1, S, S, 3), host or device, which the attached tower turns into the embeddings here."""
+        if isinstance(embeds, DeviceArray):
+            hip.tf_stream_sync(_sh())                                  # (made on the caller's stream)
         self.synchronize()
         ad, b = self._ip_model_compiled, self._latent.shape[0]
-        rows = np.concatenate([np.zeros_like(embeds)] * (self._groups - 1) + [embeds])
         with use_stream(self._stream):
             self._write_ip_scales(scales)
-            dev = DeviceArray.from_numpy(rows, _step_dtype(), "row")
+            if embeds.dtype == np.uint8:
+                dev = self._ip_rows_from_images(embeds, b, ad.embed_dim)
+            else:
+                dev = DeviceArray.from_numpy(np.concatenate([np.zeros_like(embeds)] * (self._groups - 1) + [embeds]), _step_dtype(), "row")
             tokens = ad.tokens(dev)
             kv = ad.context_kv(tokens)
             assert kv.shape == self._ip_kv.shape and kv.dtype == self._ip_kv.dtype, (kv.shape, self._ip_kv.shape)
             hip.tf_memcpy_async(self._ip_kv.ptr, kv.ptr, kv.nbytes, 3, _sh())
             self._ip_keep = (dev, tokens, kv)                            # (referenced until the kernels have run)
+
+    def _ip_rows_from_images(self, images, b, e):
+        """(G B, E) device rows [0 | tower(images)] (the tower's rows alone for cfg=False): a memset and a copy.  One image for every latent is
+        copied B times in front of the tower, so it runs the very launches B copies handed in by the caller run -- the GEMMs pick their tiles by the
+        row count, and the result must not depend on who made the copies (the tower streams its weights once per call whatever the batch)."""
+        if images.shape[0] != b:
+            if isinstance(images, DeviceArray):
+                one, images = images, DeviceArray.empty((b,) + images.shape[1:], np.uint8, "row")
+                for k in range(b):
+                    hip.tf_memcpy_async(images.ptr + k * one.nbytes, one.ptr, one.nbytes, 3, _sh())
+            else:
+                images = np.ascontiguousarray(np.repeat(images, b, axis=0))
+        emb = self._clip_vision(images)
+        per = e * emb.dtype.itemsize
+        dev = DeviceArray.empty((self._groups * b, e), emb.dtype, "row")
+        lead = (self._groups - 1) * b
+        if lead:
+            hip.tf_memset_async(dev.ptr, 0, lead * per, _sh())
+        hip.tf_memcpy_async(dev.ptr + lead * per, emb.ptr, b * per, 3, _sh())
+        self._ip_tower_keep = (images, emb)
+        return dev
 
     def set_ip_scale(self, ip_scale):
         """The adapter's strength -- one float or one per cross-attention -- from the next step on: the captured step reads the values from the

@@ -15,7 +15,9 @@ alternation, the time of start(control_image=...) for a 512^2 hint (upload, x / 
 --ip-adapter adds, interleaved with the plain DPM++2M step in the same rounds: the adapted step (compile(..., ip_adapter=True): the same UNet weights
 plus a synthetic ip-adapter_sd15, every cross-attention the fused tf_sdpa_dual_16 launch) and an adapted step that composes what the fused launch
 replaces -- two tf_sdpa_16 launches plus tf_add_16 per cross-attention, built only inside this tool (the image term at scale 1) -- and the time of
-start(ip_image_embeds=) (tokens + the hoisted K_ip | V_ip GEMM); written to profiles/sampler_bench_ip_adapter.json as well.
+start(ip_image_embeds=) (tokens + the hoisted K_ip | V_ip GEMM) and start(ip_image=) through the CLIP ViT-H image tower (clip_vision_bench: the tower
+captured and eager at batch 1 and 2, its weight-streaming floor, the exact-GELU passes' share, the GEMM shapes it had to autotune); written to
+profiles/sampler_bench_ip_adapter.json as well.
 --lora adds, for a synthetic adapter of rank 16 and of rank 128 over the 192 UNet attention / FF / proj targets plus the 72 text-encoder targets:
 lora_merge_ms (one set_adapters on an uncompiled model, every launch, wall clock incl. the final sync), lora_merge_gb_s (base read + dst write
 over the launches' device time) next to add_16_gb_s, lora_recapture_ms (set_adapters on a compiled model minus the merge), lora_step_over_plain
@@ -181,6 +183,100 @@ def lora_bench(T, hip, timed, args, state, donor, unc, ctx, noise, sched, plain_
                               "lora_step_over_plain": round(l / p, 4), "host_merge_ms": round(host_ms, 1)}
     hip.tf_event_destroy(ev0); hip.tf_event_destroy(ev1)
     return out
+
+
+def clip_vision_bench(T, hip, model, ip_emb, args):
+    """--ip-adapter: the CLIP ViT-H image tower (vae/clip_vision.py, synthetic weights) in front of the adapted model.  Interleaved rounds, medians and
+    the spread between rounds: the tower at batch 1 and 2, captured (graph replay) and eager, wall time from the call to the drained stream (the
+    150 KB image upload included); start(ip_image=) against start(ip_image_embeds=) on the batch-1 model; the 32 exact-GELU passes of one tower on
+    their own (stream events); the tower against its weight-streaming floor (every fp16 weight once at the 8 TB/s HBM peak); the GEMM shapes of
+    the tower that had no row in the tuning table (autotuned on the first eager call)."""
+    import tempfile
+    from tinyfusers_amd.native import lib
+    from tinyfusers_amd.vae.clip_vision import VIT_H, ClipVision, param_shapes, synthetic_state
+    with contextlib.redirect_stdout(io.StringIO()):
+        tower = ClipVision.load(synthetic_state(VIT_H, 11))
+    weight_bytes = 2 * sum(int(np.prod(s)) for s in param_shapes(VIT_H).values())
+    rng = np.random.default_rng(5)
+    imgs = {b: rng.integers(0, 256, (b, 224, 224, 3), dtype=np.uint8) for b in (1, 2)}
+    def table_keys():
+        """The shape keys that have a row in the library's tuning table right now (tf_gemm_tune_count / tf_gemm_tune_entry: its own host-side view)."""
+        n, key, cfg_ = ctypes.c_int(0), (ctypes.c_int * 10)(), (ctypes.c_int * 5)()
+        hip.tf_gemm_tune_count(ctypes.byref(n))
+        keys = set()
+        for i in range(n.value):
+            hip.tf_gemm_tune_entry(i, key, cfg_)
+            keys.add(tuple(key))
+        return keys
+    before = table_keys()                                                  # (the shipped table plus what this process has tuned so far)
+    with tempfile.TemporaryDirectory() as d:                               # which GEMM shapes the first eager calls had to tune
+        lib.tf_gemm_tune_trace(1)
+        for b in (1, 2):
+            tower(imgs[b])                                                 # eager, then captured
+        lib.tf_gemm_tune_trace_dump(os.path.join(d, "keys.txt").encode())
+        lib.tf_gemm_tune_trace(0)
+        rows = sorted({tuple(int(v) for v in line.split())[:10] for line in open(os.path.join(d, "keys.txt"))})
+    # (the trace's own "had a row" flag is that of a key's LAST lookup, behind the tuning: the table as it stood before the first call decides)
+    untuned = [list(r[:3]) for r in rows if r not in before]
+
+    def wall(fn):
+        t0 = time.perf_counter()
+        out = fn()
+        tower._stream.synchronize()
+        del out
+        return 1e3 * (time.perf_counter() - t0)
+    model.attach_clip_vision(tower)
+    t = {k: [] for k in ("captured_b1", "eager_b1", "captured_b2", "eager_b2", "start_ip_image", "start_ip_image_embeds")}
+    for r in range(args.rounds + 1):
+        for b in (1, 2):
+            t[f"captured_b{b}"].append(wall(lambda: tower(imgs[b])))
+            t[f"eager_b{b}"].append(wall(lambda: tower.eager(imgs[b])))
+        for key, kw in (("start_ip_image", dict(ip_image=imgs[1])), ("start_ip_image_embeds", dict(ip_image_embeds=ip_emb))):
+            t0 = time.perf_counter()
+            model.start(seed=1234, **kw)
+            model.synchronize()
+            t[key].append(1e3 * (time.perf_counter() - t0))
+    med = {k: float(np.median(v[1:])) for k, v in t.items()}
+    spread = {k: round(max(v[1:]) - min(v[1:]), 3) for k, v in t.items()}
+    # the GELU pass alone: 32 in-place launches on a (257 B, 5120) buffer, per batch size
+    gelu = {}
+    ev0, ev1, ms = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_float()
+    hip.tf_event_create(ctypes.byref(ev0)); hip.tf_event_create(ctypes.byref(ev1))
+    with T.use_stream(tower._stream):
+        for b in (1, 2):
+            x = T.DeviceArray.from_numpy(rng.standard_normal((257 * b, VIT_H.mlp)).astype(np.float32), np.float16, "row")
+            per = []
+            for r in range(args.rounds + 1):
+                hip.tf_event_record(ev0, tower._stream.handle)
+                for _ in range(VIT_H.layers):
+                    hip.tf_gelu_erf_16(0, x.ptr, x.ptr, x.size, T._sh())
+                hip.tf_event_record(ev1, tower._stream.handle)
+                tower._stream.synchronize()
+                hip.tf_event_elapsed_ms(ctypes.byref(ms), ev0, ev1)
+                per.append(ms.value)
+            gelu[b] = float(np.median(per[1:]))
+    hip.tf_event_destroy(ev0); hip.tf_event_destroy(ev1)
+    # the same from the library's own brackets: family 5 (tf_vit_patchify_u8_16 + the 32 tf_gelu_erf_16) over one instrumented eager tower at batch 1
+    fam = {}
+    hip.tf_prof_enable(1)
+    try:
+        tower.eager(imgs[1])
+        tower._stream.synchronize()
+        fms, fwork, fn = ctypes.c_double(), ctypes.c_double(), ctypes.c_longlong()
+        hip.tf_prof_read_family(5, ctypes.byref(fms), ctypes.byref(fwork), ctypes.byref(fn))
+        fam = {"launches": fn.value, "ms": round(fms.value, 4), "bytes": int(fwork.value)}
+    finally:
+        hip.tf_prof_enable(0)
+    floor_ms = weight_bytes / 8e12 * 1e3
+    tower.release_graphs()
+    return {"clip_vision": {"config": "ViT-H/14 (synthetic weights)", "weight_bytes": weight_bytes, "weight_floor_ms_at_8TBps": round(floor_ms, 4),
+                            "tower_ms": {k: round(med[k], 3) for k in ("captured_b1", "eager_b1", "captured_b2", "eager_b2")},
+                            "tower_over_floor": {k: round(med[k] / floor_ms, 2) for k in ("captured_b1", "captured_b2")},
+                            "gelu_32_passes_ms": {f"b{b}": round(gelu[b], 4) for b in gelu},
+                            "gelu_share_of_captured_tower": {f"b{b}": round(gelu[b] / med[f"captured_b{b}"], 4) for b in gelu},
+                            "prof_family_5_patchify_and_gelu_b1": fam,
+                            "round_spread_ms": spread, "gemm_shapes_autotuned_MNK": untuned, "gemm_shapes_total": len(rows)},
+            "start_ip_image_ms": round(med["start_ip_image"], 3), "start_ip_image_embeds_interleaved_ms": round(med["start_ip_image_embeds"], 3)}
 
 
 def main():
@@ -459,8 +555,9 @@ def main():
         spread_ms = lambda k: round(max(step_ms[k]) - min(step_ms[k]), 4)
         extra.update({"dpmpp2m_ip_fused_step_ms": round(med["dpmpp2m_ip_fused"], 4), "dpmpp2m_ip_composed_step_ms": round(med["dpmpp2m_ip_composed"], 4),
                       "ip_fused_over_plain": round(med["dpmpp2m_ip_fused"] / med["dpmpp2m"], 4), "ip_composed_over_plain": round(med["dpmpp2m_ip_composed"] / med["dpmpp2m"], 4),
-                      "start_ip_image_embeds_ms": round(1e3 * float(np.median(st[1:])), 3), "start_ip_image_ms": "not measured (no CLIP vision tower in the tree)",
-                      "ip_round_spread_ms": {k: spread_ms(k) for k in ("dpmpp2m", "dpmpp2m_ip_fused", "dpmpp2m_ip_composed")}})
+                      "start_ip_image_embeds_ms": round(1e3 * float(np.median(st[1:])), 3),
+                      "ip_round_spread_ms": {k: spread_ms(k) for k in ("dpmpp2m", "dpmpp2m_ip_fused", "dpmpp2m_ip_composed")},
+                      **clip_vision_bench(T, hip, fm, ip_emb, args)})
 
     if args.lora:
         extra.update(lora_bench(T, hip, timed, args, state, ddim_m, unc, ctx, noise, dpm_sched, dpm_m, dpm_replays, lat0))
