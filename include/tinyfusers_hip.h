@@ -528,7 +528,7 @@ int tf_set_step_params(void* step_params, float timestep, float a_t, float a_pre
  * row of a timestep once, keeps it, and hands it to the captured step through this copy instead of four launches per step */
 int tf_set_step_params_copy(void* step_params, float timestep, float a_t, float a_prev, float guidance, void* dst, const void* src, long long nbytes, tfStream_t s);
 int tf_timestep_embedding_f16(void* out, const void* step_params, int dim, float max_period, tfStream_t s);
-/* latent (B,C,H,W) f32 NCHW  ->  unet input (2B,H,W,C) f16 NHWC = [latent ; latent]  (variants/sd.py:31) */
+/* latent (B,C,H,W) f32 NCHW  ->  unet input (2B,H,W,C) f16 NHWC = [latent ; latent]  (variants/sd.py:31; csrc/sampler.hip, the step's head) */
 int tf_cfg_duplicate_f16(void* x2b_nhwc, const void* latent_nchw_f32, int B, int C, int H, int W, tfStream_t s);
 /* e = e_u + g (e_c - e_u); DDIM sigma=0 update, latent updated in place (variants/sd.py:44-45, :14-25) */
 int tf_cfg_ddim_step_f32(void* latent_nchw_f32, const void* unet_out_2b_nhwc_f16, const void* step_params, int B, int C,
@@ -538,9 +538,13 @@ int tf_cfg_ddim_step_f32(void* latent_nchw_f32, const void* unet_out_2b_nhwc_f16
 int tf_cfg_ddim_step2_f32(void* latent, const void* eps_uncond, const void* eps_cond, const void* step_params, int B, int C, int H, int W, tfStream_t s);
 
 /* ---- samplers beyond sigma = 0 DDIM (csrc/sampler.hip; generalises variants/sd.py:14-25 and the CFG combine of :27-46) -------------
+ * csrc/sampler.hip holds the sampler side of every mode below: the generator, the parameter launch, ONE kernel for the step's opening launch
+ * (tf_cfg_duplicate_*, tf_cfg_concat_*, tf_latent_stack1_*) and ONE for its closing launch (tf_cfg_sampler_step_*, tf_cfg_sampler_step_masked_*,
+ * tf_cfg3_sampler_step_*, tf_sampler_step1_*); the entries differ in what their parameters mean and in which arguments they refuse.
  * Noise: Philox4x32-10, key = (seed_lo, seed_hi), counter = (q, global image index, step, tag); counter q of an image gives its NCHW
  * elements 4q .. 4q+3 (u = ((bits >> 8) + 0.5) 2^-24, Box-Muller on (u0, u1) and (u2, u3)).  Tag 0: initial latent; tag 1: the ancestral
- * noise of schedule step `step`.  Image k's noise is independent of the batch size and of the rank that draws it. */
+ * noise of schedule step `step`; tag 2: the known region of an inpainting step.  Image k's noise is independent of the batch size and of the
+ * rank that draws it. */
 /* out (images, per_image) fp32 N(0,1): images image_offset .. image_offset + images - 1 (per_image <= 2^32) */
 int tf_randn_f32(void* out, int images, long long per_image, unsigned seed_lo, unsigned seed_hi, int image_offset, int step, int tag, tfStream_t s);
 /* tf_set_step_params_copy (variants/sd.py:27-46 step scalars) extended to the sampler block of 8 words: [0..3] as there, then u32 [4] the
@@ -554,8 +558,8 @@ int tf_cfg_sampler_step_f32(void* latent, const void* eps2, void* x0_hist, const
 int tf_cfg_sampler_step_bf16(void* latent, const void* eps2, void* x0_hist, const void* step_params, const void* coeffs, int rows, int B, int C, int H, int W, tfStream_t s);
 
 /* ---- image-to-image and masked inpainting (csrc/img2img.hip): the encoder edges of vae/vae.py:12-15 (image -> means, only the means kept),
- * the inverse of the decode scale and tail of variants/sd.py:48-54, and the sampler update of variants/sd.py:14-25 (tf_cfg_sampler_step_*)
- * with a latent blend.  Philox tags: 0 the initial latent, 1 the ancestral noise, 2 the known region of an inpainting step. */
+ * the inverse of the decode scale and tail of variants/sd.py:48-54; on the sampler's side the noising to a start level and the sampler
+ * update of variants/sd.py:14-25 (tf_cfg_sampler_step_*) with a latent blend. */
 /* uint8 (B,H,W,3) -> fp16 x / 127.5 - 1 in the same element order: the NHWC (B,3,H,W) image AutoencoderKL.encode reads; n = B*H*W*3 */
 int tf_image_from_u8_f16(void* out, const void* x, long long n, tfStream_t s);
 /* encoder means (B,4,H,W) fp16 NHWC -> x0 (B,4,H,W) fp32 NCHW = 0.18215 means (the decode side divides by it, variants/sd.py:49) */
@@ -570,7 +574,7 @@ int tf_cfg_sampler_step_masked_f32(void* latent, const void* eps2, void* x0_hist
 int tf_cfg_sampler_step_masked_bf16(void* latent, const void* eps2, void* x0_hist, const void* step_params, const void* coeffs, int rows, const void* x0_init,
                                     const void* mask, int B, int C, int H, int W, tfStream_t s);
 
-/* ---- the guidance-free step (csrc/single.hip; variants/sd.py compile(..., cfg=False)): ONE guidance group instead of the CFG pair of
+/* ---- the guidance-free step (variants/sd.py compile(..., cfg=False)): ONE guidance group instead of the CFG pair of
  * variants/sd.py:31 and :44 -- what a consistency model (LCM, LCM-LoRA) samples with at guidance 1, where e = e_u + 1 (e_c - e_u) = e_c and
  * the unconditional half of every launch is thrown away.  The opening and the closing launch of the captured step; the UNet between them
  * runs on B images against the context alone. */
@@ -635,7 +639,7 @@ int tf_control_add_16(int dtype, const void* table, int n_entries, const void* s
  * x / 127.5 - 1 of vae/vae.py:12-15); n = B*H*W*3 */
 int tf_hint_from_u8_16(int dtype, void* out, const void* x_u8, long long n, tfStream_t s);
 
-/* ---- concat-conditioned UNets (csrc/concat.hip): the SD-1.5 inpainting checkpoint (9 input channels [latent | mask | latent of the masked
+/* ---- concat-conditioned UNets (the encoder edges: csrc/img2img.hip): the SD-1.5 inpainting checkpoint (9 input channels [latent | mask | latent of the masked
  * image]) and InstructPix2Pix (8 input channels [latent | latent of the image to edit], three guidance branches) on the sampler above: the
  * CFG duplication of variants/sd.py:31 with the conditioning channels appended, the update of variants/sd.py:14-25 behind a three-branch
  * combine, and the encoder edges of vae/vae.py:12-15 that fill the conditioning buffer. */

@@ -1,6 +1,6 @@
 """Host-side checks of the concat-conditioned checkpoints (no GPU): StableDiffusion.concat_mask / concat_mask_u8 (the nearest-neighbour mask
 rule of the SD-1.5 inpainting UNet, against latent_mask's block maximum), the SD15_INPAINT / SD15_EDIT configurations and the module trees they
-build, the compile() refusals that are decided before any device work, and the header block of csrc/concat.hip (test_abi checks that the
+build, the compile() refusals that are decided before any device work, and the header block of the concat-conditioned entries (test_abi checks that the
 library exports what the header declares)."""
 import os
 import re
@@ -119,7 +119,7 @@ def test_compile_refuses_mismatched_concat_arguments_before_touching_a_device():
 # ---- 4. header ---------------------------------------------------------------------------------------------------------------------------
 def test_header_declares_the_concat_entries_with_their_citations():
     hdr = open(os.path.join(ROOT, "include", "tinyfusers_hip.h")).read()
-    i = hdr.index("csrc/concat.hip")
+    i = hdr.index("---- concat-conditioned UNets")
     block = hdr[hdr.rindex("/*", 0, i):]
     head = block[:block.index("*/")]
     for cite in ("variants/sd.py:31", "variants/sd.py:14-25", "vae/vae.py:12-15"):

@@ -141,7 +141,7 @@ def test_header_and_ctypes_declare_the_control_entries():
     import tinyfusers_amd.native as native
     hdr = open(os.path.join(ROOT, "include", "tinyfusers_hip.h")).read()
     i = hdr.index("csrc/control.hip")
-    block = hdr[hdr.rindex("/*", 0, i):hdr.index("csrc/concat.hip")]
+    block = hdr[hdr.rindex("/*", 0, i):hdr.index("---- concat-conditioned UNets")]
     assert "vision/unet.py:72" in block[:block.index("*/")]
     names = set(re.findall(r"\b(tf_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", block, flags=re.S)))
     assert names == {"tf_control_add_16", "tf_hint_from_u8_16"}

@@ -1,4 +1,4 @@
-"""GPU checks of the concat-conditioned checkpoints (csrc/concat.hip, StableDiffusion.compile(..., concat="inpaint" | "edit"),
+"""GPU checks of the concat-conditioned checkpoints (csrc/sampler.hip and csrc/img2img.hip, StableDiffusion.compile(..., concat="inpaint" | "edit"),
 start(cond_image= / cond_mask= / cond_latent=, image_guidance=)): the four kernels bit for bit against their host constructions and their
 img2img / sampler namesakes, one three-branch update against a float64 restatement, tiny-UNet trajectories of a 9-channel and an 8-channel
 model (graph == eager, reproducible, against the CPU oracle fed the concatenated input), the conditioning path through the VAE encoder, the
@@ -117,6 +117,32 @@ def test_cfg_concat_matches_the_host_construction_and_cfg_duplicate(tf, shape, d
         concat(buf.ptr, d_lat.ptr, None, B, C, Cc, H, W, 2, 0, None)
 
 
+@pytest.mark.parametrize("dtype", ["fp16", "bf16"])
+def test_latent_stack_grid_stride_loop_matches_the_host_construction(tf, dtype):
+    """(3, 4, 256, 256) with 5 conditioning channels: 786432 elements per group for tf_cfg_duplicate_*, 1769472 for tf_cfg_concat_* -- both past the
+    2048 x 256 threads of the largest grid, so threads take a second (and a fourth) trip.  Two groups against the host cast of the test above."""
+    from tinyfusers_amd.native import hip
+    B, C, Cc, H, W = 3, 4, 5, 256, 256
+    rng = np.random.default_rng(31)
+    lat = 3 * rng.standard_normal((B, C, H, W), dtype=np.float32)
+    cond = rng.standard_normal((B, Cc, H, W), dtype=np.float32)
+    d_lat = tf.DeviceArray.from_numpy(lat, np.float32, "row")
+    d_cond = tf.DeviceArray.from_numpy(cond, np.float32, "row")
+    n = B * H * W * C
+    d_dup = _raw16(tf, 2 * n, 0x7E55)
+    (hip.tf_cfg_duplicate_bf16 if dtype == "bf16" else hip.tf_cfg_duplicate_f16)(d_dup.ptr, d_lat.ptr, B, C, H, W, None)
+    want = _bits16(lat.transpose(0, 2, 3, 1), dtype).reshape(-1)
+    got = _read16(d_dup).reshape(2, n)
+    assert np.array_equal(got[0], want) and np.array_equal(got[1], want)
+    n = B * H * W * (C + Cc)
+    d_cat = _raw16(tf, 2 * n, 0x7E55)
+    (hip.tf_cfg_concat_bf16 if dtype == "bf16" else hip.tf_cfg_concat_f16)(d_cat.ptr, d_lat.ptr, d_cond.ptr, B, C, Cc, H, W, 2, 0b01, None)
+    got = _read16(d_cat).reshape(2, n)
+    for g, kept in enumerate((np.zeros_like(cond), cond)):          # group 0 drops the conditioning
+        want = _bits16(np.concatenate([lat, kept], axis=1).transpose(0, 2, 3, 1), dtype).reshape(-1)
+        assert np.array_equal(got[g], want), g
+
+
 # ---- 2. tf_image_from_u8_masked_f16 -------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("hw", [(3, 5), (16, 24)])
 def test_image_from_u8_masked_keeps_unmasked_pixels_and_zeroes_the_rest(tf, hw):
@@ -197,55 +223,55 @@ def test_one_three_branch_sampler_step_matches_float64(tf, name, dtype):
     from tinyfusers_amd.native import hip
     from tinyfusers_amd.storage.tensor import bfloat16
     from tinyfusers_amd.variants import samplers as S
-    B, C, H, W = 2, 4, 8, 12
-    n_img, offset = C * H * W, 5
-    sch = S.make(name).schedule(25, strength=0.8)
-    i = 9
-    table = sch.coeffs.copy()
-    table[i, 2] = table[i, 2] or 0.25                            # every term live: c_1 != 0 and c_n != 0
-    table[i, 3] = table[i, 3] or 0.6
-    rng = np.random.default_rng(4)
-    x, hist = (rng.standard_normal((B, C, H, W)).astype(np.float32) for _ in range(2))
-    dt = bfloat16 if dtype == "bf16" else np.float16
-    d_eps = tf.DeviceArray.from_numpy(rng.standard_normal((3 * B, C, H, W)), dt, "nhwc")
-    eps3 = d_eps.numpy().astype(np.float64)                      # the values the kernel reads
-    d_tab = tf.DeviceArray.from_numpy(table.astype(np.float32), np.float32, "row")
-    sp = tf.DeviceArray.zeros((8,), np.float32, "row")
-    edit = tf.DeviceArray.zeros((4,), np.float32, "row")
-    three = hip.tf_cfg3_sampler_step_bf16 if dtype == "bf16" else hip.tf_cfg3_sampler_step_f32
-    two = hip.tf_cfg_sampler_step_bf16 if dtype == "bf16" else hip.tf_cfg_sampler_step_f32
+    for B, C, H, W in ((2, 4, 8, 12), (2, 3, 5, 7)):             # (105 elements per image: a partial last counter)
+        n_img, offset = C * H * W, 5
+        sch = S.make(name).schedule(25, strength=0.8)
+        i = 9
+        table = sch.coeffs.copy()
+        table[i, 2] = table[i, 2] or 0.25                            # every term live: c_1 != 0 and c_n != 0
+        table[i, 3] = table[i, 3] or 0.6
+        rng = np.random.default_rng(4)
+        x, hist = (rng.standard_normal((B, C, H, W)).astype(np.float32) for _ in range(2))
+        dt = bfloat16 if dtype == "bf16" else np.float16
+        d_eps = tf.DeviceArray.from_numpy(rng.standard_normal((3 * B, C, H, W)), dt, "nhwc")
+        eps3 = d_eps.numpy().astype(np.float64)                      # the values the kernel reads
+        d_tab = tf.DeviceArray.from_numpy(table.astype(np.float32), np.float32, "row")
+        sp = tf.DeviceArray.zeros((8,), np.float32, "row")
+        edit = tf.DeviceArray.zeros((4,), np.float32, "row")
+        three = hip.tf_cfg3_sampler_step_bf16 if dtype == "bf16" else hip.tf_cfg3_sampler_step_f32
+        two = hip.tf_cfg_sampler_step_bf16 if dtype == "bf16" else hip.tf_cfg_sampler_step_f32
 
-    def run(eps, lo_img, hi_img, g_i, off=offset, branches=3):
-        sl = slice(lo_img, hi_img)
-        nb = hi_img - lo_img
-        lat = tf.DeviceArray.from_numpy(x[sl], np.float32, "row")
-        h = tf.DeviceArray.from_numpy(hist[sl], np.float32, "row")
-        e = tf.DeviceArray.from_numpy(np.concatenate([eps[k * B + lo_img:k * B + hi_img] for k in range(eps.shape[0] // B)]), dt, "nhwc")
-        _set_params(hip, sp, sch.timesteps[i], sch.alphas[i], sch.alphas_prev[i], G_T, i, SEED, off)
-        if branches == 3:
-            hip.tf_set_step_params(edit.ptr, float(g_i), 0.0, 0.0, 0.0, None)
-            three(lat.ptr, e.ptr, h.ptr, sp.ptr, d_tab.ptr, len(table), edit.ptr, nb, C, H, W, None)
-        else:
-            two(lat.ptr, e.ptr, h.ptr, sp.ptr, d_tab.ptr, len(table), nb, C, H, W, None)
-        return lat.numpy(), h.numpy()
+        def run(eps, lo_img, hi_img, g_i, off=offset, branches=3):
+            sl = slice(lo_img, hi_img)
+            nb = hi_img - lo_img
+            lat = tf.DeviceArray.from_numpy(x[sl], np.float32, "row")
+            h = tf.DeviceArray.from_numpy(hist[sl], np.float32, "row")
+            e = tf.DeviceArray.from_numpy(np.concatenate([eps[k * B + lo_img:k * B + hi_img] for k in range(eps.shape[0] // B)]), dt, "nhwc")
+            _set_params(hip, sp, sch.timesteps[i], sch.alphas[i], sch.alphas_prev[i], G_T, i, SEED, off)
+            if branches == 3:
+                hip.tf_set_step_params(edit.ptr, float(g_i), 0.0, 0.0, 0.0, None)
+                three(lat.ptr, e.ptr, h.ptr, sp.ptr, d_tab.ptr, len(table), edit.ptr, nb, C, H, W, None)
+            else:
+                two(lat.ptr, e.ptr, h.ptr, sp.ptr, d_tab.ptr, len(table), nb, C, H, W, None)
+            return lat.numpy(), h.numpy()
 
-    z = np.stack([randn_ref(SEED, offset + b, n_img, i, 1).reshape(C, H, W) for b in range(B)])
-    got, got_h = run(eps3, 0, B, G_I)
-    ref, ref_x0 = _cfg3_ref(x, eps3, hist, sch.alphas[i], G_T, G_I, table[i], z)
-    print(f"three-branch {name} {dtype}: max |d| / (1 + |ref|) latent {float(np.max(np.abs(got - ref) / (1 + np.abs(ref)))):.2e}, "
-          f"x0 {float(np.max(np.abs(got_h - ref_x0) / (1 + np.abs(ref_x0)))):.2e} (gate 1e-5)")
-    assert np.all(np.abs(got - ref) <= 1e-5 * (1 + np.abs(ref))), float(np.max(np.abs(got - ref) / (1 + np.abs(ref))))
-    assert np.all(np.abs(got_h - ref_x0) <= 1e-5 * (1 + np.abs(ref_x0)))
-    # batch independence: image 1 alone, as global image offset + 1
-    one, one_h = run(eps3, 1, 2, G_I, off=offset + 1)
-    assert np.array_equal(one[0], got[1]) and np.array_equal(one_h[0], got_h[1])
-    # g_I = 1 with e1 := e0 is the two-branch update on [e0 ; e2] (to the gate: FMA contraction may differ between the two kernels)
-    same = np.concatenate([eps3[:B], eps3[:B], eps3[2 * B:]])
-    a, ah = run(same, 0, B, 1.0)
-    b, bh = run(np.concatenate([eps3[:B], eps3[2 * B:]]), 0, B, None, branches=2)
-    assert np.all(np.abs(a - b) <= 1e-5 * (1 + np.abs(b))) and np.all(np.abs(ah - bh) <= 1e-5 * (1 + np.abs(bh)))
-    with pytest.raises(RuntimeError, match="bad arguments"):
-        three(sp.ptr, d_eps.ptr, sp.ptr, sp.ptr, d_tab.ptr, len(table), None, B, C, H, W, None)
+        z = np.stack([randn_ref(SEED, offset + b, n_img, i, 1).reshape(C, H, W) for b in range(B)])
+        got, got_h = run(eps3, 0, B, G_I)
+        ref, ref_x0 = _cfg3_ref(x, eps3, hist, sch.alphas[i], G_T, G_I, table[i], z)
+        print(f"three-branch {name} {dtype}: max |d| / (1 + |ref|) latent {float(np.max(np.abs(got - ref) / (1 + np.abs(ref)))):.2e}, "
+              f"x0 {float(np.max(np.abs(got_h - ref_x0) / (1 + np.abs(ref_x0)))):.2e} (gate 1e-5)")
+        assert np.all(np.abs(got - ref) <= 1e-5 * (1 + np.abs(ref))), float(np.max(np.abs(got - ref) / (1 + np.abs(ref))))
+        assert np.all(np.abs(got_h - ref_x0) <= 1e-5 * (1 + np.abs(ref_x0)))
+        # batch independence: image 1 alone, as global image offset + 1
+        one, one_h = run(eps3, 1, 2, G_I, off=offset + 1)
+        assert np.array_equal(one[0], got[1]) and np.array_equal(one_h[0], got_h[1])
+        # g_I = 1 with e1 := e0 is the two-branch update on [e0 ; e2] (to the gate: FMA contraction may differ between the two kernels)
+        same = np.concatenate([eps3[:B], eps3[:B], eps3[2 * B:]])
+        a, ah = run(same, 0, B, 1.0)
+        b, bh = run(np.concatenate([eps3[:B], eps3[2 * B:]]), 0, B, None, branches=2)
+        assert np.all(np.abs(a - b) <= 1e-5 * (1 + np.abs(b))) and np.all(np.abs(ah - bh) <= 1e-5 * (1 + np.abs(bh)))
+        with pytest.raises(RuntimeError, match="bad arguments"):
+            three(sp.ptr, d_eps.ptr, sp.ptr, sp.ptr, d_tab.ptr, len(table), None, B, C, H, W, None)
 
 
 # ---- 5. - 7. tiny concat-conditioned UNets -----------------------------------------------------------------------------------------------

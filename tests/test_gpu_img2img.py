@@ -1,4 +1,4 @@
-"""GPU checks of image-to-image and masked inpainting (csrc/img2img.hip, StableDiffusion.encode_image / start(init_image=, init_latent=,
+"""GPU checks of image-to-image and masked inpainting (csrc/img2img.hip and csrc/sampler.hip, StableDiffusion.encode_image / start(init_image=, init_latent=,
 mask=) / compile(..., inpaint=True)): the uint8 edge and the encoder against the oracle, the noising of a clean latent against float64
 numpy with the host Philox, one masked sampler update against a float64 restatement, tiny-UNet img2img and inpainting trajectories (graph ==
 eager, reproducible, against the CPU oracle, the kept region exactly on its noised trajectory) and the SD-1.5 shapes end to end."""
@@ -177,62 +177,62 @@ def test_one_masked_sampler_step_matches_float64(tf, name, dtype):
     from tinyfusers_amd.native import hip
     from tinyfusers_amd.storage.tensor import bfloat16
     from tinyfusers_amd.variants import samplers as S
-    B, C, H, W = 2, 4, 8, 12
-    n_img, g, offset = C * H * W, 7.5, 5
-    sch = S.make(name).schedule(25, strength=0.8)
-    i = 9
-    table = sch.coeffs.copy()
-    table[i, 2] = table[i, 2] or 0.25                            # every term live: c_1 != 0 and c_n != 0
-    table[i, 3] = table[i, 3] or 0.6
-    rng = np.random.default_rng(4)
-    x, hist, x0i = (rng.standard_normal((B, C, H, W)).astype(np.float32) for _ in range(3))
-    eps2 = rng.standard_normal((2 * B, C, H, W))
-    m = rng.random((B, 1, H, W)).astype(np.float32)               # fractional, with exact 0 and 1 pixels
-    m[:, :, 0, :4], m[:, :, 1, :4] = 0.0, 1.0
-    dt = bfloat16 if dtype == "bf16" else np.float16
-    d_eps = tf.DeviceArray.from_numpy(eps2, dt, "nhwc")
-    eps2 = d_eps.numpy().astype(np.float64)                      # the values the kernel reads
-    d_tab = tf.DeviceArray.from_numpy(table.astype(np.float32), np.float32, "row")
-    sp = tf.DeviceArray.zeros((8,), np.float32, "row")
-    masked = hip.tf_cfg_sampler_step_masked_bf16 if dtype == "bf16" else hip.tf_cfg_sampler_step_masked_f32
-    plain = hip.tf_cfg_sampler_step_bf16 if dtype == "bf16" else hip.tf_cfg_sampler_step_f32
+    for B, C, H, W in ((2, 4, 8, 12), (2, 3, 5, 7)):             # (105 elements per image: a partial last counter)
+        n_img, g, offset = C * H * W, 7.5, 5
+        sch = S.make(name).schedule(25, strength=0.8)
+        i = 9
+        table = sch.coeffs.copy()
+        table[i, 2] = table[i, 2] or 0.25                            # every term live: c_1 != 0 and c_n != 0
+        table[i, 3] = table[i, 3] or 0.6
+        rng = np.random.default_rng(4)
+        x, hist, x0i = (rng.standard_normal((B, C, H, W)).astype(np.float32) for _ in range(3))
+        eps2 = rng.standard_normal((2 * B, C, H, W))
+        m = rng.random((B, 1, H, W)).astype(np.float32)               # fractional, with exact 0 and 1 pixels
+        m[:, :, 0, :4], m[:, :, 1, :4] = 0.0, 1.0
+        dt = bfloat16 if dtype == "bf16" else np.float16
+        d_eps = tf.DeviceArray.from_numpy(eps2, dt, "nhwc")
+        eps2 = d_eps.numpy().astype(np.float64)                      # the values the kernel reads
+        d_tab = tf.DeviceArray.from_numpy(table.astype(np.float32), np.float32, "row")
+        sp = tf.DeviceArray.zeros((8,), np.float32, "row")
+        masked = hip.tf_cfg_sampler_step_masked_bf16 if dtype == "bf16" else hip.tf_cfg_sampler_step_masked_f32
+        plain = hip.tf_cfg_sampler_step_bf16 if dtype == "bf16" else hip.tf_cfg_sampler_step_f32
 
-    def run(row, lo_img, hi_img, mask, off=offset, with_mask=True):
-        sl = slice(lo_img, hi_img)
-        lat = tf.DeviceArray.from_numpy(x[sl], np.float32, "row")
-        h = tf.DeviceArray.from_numpy(hist[sl], np.float32, "row")
-        xi = tf.DeviceArray.from_numpy(x0i[sl], np.float32, "row")
-        dm = tf.DeviceArray.from_numpy(mask[sl], np.float32, "row")
-        e2 = d_eps if (lo_img, hi_img) == (0, B) else tf.DeviceArray.from_numpy(np.concatenate([eps2[sl], eps2[B + lo_img:B + hi_img]]), dt, "nhwc")
-        _set_params(hip, sp, sch.timesteps[row], sch.alphas[row], sch.alphas_prev[row], g, row, SEED, off)
-        nb = hi_img - lo_img
-        if with_mask:
-            masked(lat.ptr, e2.ptr, h.ptr, sp.ptr, d_tab.ptr, len(table), xi.ptr, dm.ptr, nb, C, H, W, None)
-        else:
-            plain(lat.ptr, e2.ptr, h.ptr, sp.ptr, d_tab.ptr, len(table), nb, C, H, W, None)
-        return lat.numpy(), h.numpy()
+        def run(row, lo_img, hi_img, mask, off=offset, with_mask=True):
+            sl = slice(lo_img, hi_img)
+            lat = tf.DeviceArray.from_numpy(x[sl], np.float32, "row")
+            h = tf.DeviceArray.from_numpy(hist[sl], np.float32, "row")
+            xi = tf.DeviceArray.from_numpy(x0i[sl], np.float32, "row")
+            dm = tf.DeviceArray.from_numpy(mask[sl], np.float32, "row")
+            e2 = d_eps if (lo_img, hi_img) == (0, B) else tf.DeviceArray.from_numpy(np.concatenate([eps2[sl], eps2[B + lo_img:B + hi_img]]), dt, "nhwc")
+            _set_params(hip, sp, sch.timesteps[row], sch.alphas[row], sch.alphas_prev[row], g, row, SEED, off)
+            nb = hi_img - lo_img
+            if with_mask:
+                masked(lat.ptr, e2.ptr, h.ptr, sp.ptr, d_tab.ptr, len(table), xi.ptr, dm.ptr, nb, C, H, W, None)
+            else:
+                plain(lat.ptr, e2.ptr, h.ptr, sp.ptr, d_tab.ptr, len(table), nb, C, H, W, None)
+            return lat.numpy(), h.numpy()
 
-    z = np.stack([randn_ref(SEED, offset + b, n_img, i, 1).reshape(C, H, W) for b in range(B)])
-    known = _known_ref(x0i, sch.alphas_prev[i], SEED, i, offset)
-    got, got_h = run(i, 0, B, m)
-    ref, ref_x0 = _masked_ref(x, eps2, hist, sch.alphas[i], sch.alphas_prev[i], g, table[i], z, known, m)
-    assert np.all(np.abs(got - ref) <= 1e-5 * (1 + np.abs(ref))), float(np.max(np.abs(got - ref) / (1 + np.abs(ref))))
-    assert np.all(np.abs(got_h - ref_x0) <= 1e-5 * (1 + np.abs(ref_x0)))
-    keep = np.broadcast_to(m == 0, got.shape)                     # the kept pixels: sqrt(a_s) x0_init + sqrt(1 - a_s) z2, z2 = tag 2 at the row
-    assert keep.sum() > 0 and np.all(np.abs(got[keep] - known[keep]) <= 2e-6 * (1 + np.abs(known[keep])))
-    # batch independence: image 1 alone, as global image offset + 1
-    one, _ = run(i, 1, 2, m, off=offset + 1)
-    assert np.array_equal(one[0], got[1])
-    # mask 1 everywhere: the unmasked update, bit for bit
-    ones = np.ones_like(m)
-    a, ah = run(i, 0, B, ones)
-    b, bh = run(i, 0, B, ones, with_mask=False)
-    assert np.array_equal(a, b) and np.array_equal(ah, bh)
-    # the last row (a_s = 1) with mask 0: x0_init exactly
-    last = len(table) - 1
-    assert sch.alphas_prev[last] == 1.0
-    fin, _ = run(last, 0, B, np.zeros_like(m))
-    assert np.array_equal(fin, x0i)
+        z = np.stack([randn_ref(SEED, offset + b, n_img, i, 1).reshape(C, H, W) for b in range(B)])
+        known = _known_ref(x0i, sch.alphas_prev[i], SEED, i, offset)
+        got, got_h = run(i, 0, B, m)
+        ref, ref_x0 = _masked_ref(x, eps2, hist, sch.alphas[i], sch.alphas_prev[i], g, table[i], z, known, m)
+        assert np.all(np.abs(got - ref) <= 1e-5 * (1 + np.abs(ref))), float(np.max(np.abs(got - ref) / (1 + np.abs(ref))))
+        assert np.all(np.abs(got_h - ref_x0) <= 1e-5 * (1 + np.abs(ref_x0)))
+        keep = np.broadcast_to(m == 0, got.shape)                     # the kept pixels: sqrt(a_s) x0_init + sqrt(1 - a_s) z2, z2 = tag 2 at the row
+        assert keep.sum() > 0 and np.all(np.abs(got[keep] - known[keep]) <= 2e-6 * (1 + np.abs(known[keep])))
+        # batch independence: image 1 alone, as global image offset + 1
+        one, _ = run(i, 1, 2, m, off=offset + 1)
+        assert np.array_equal(one[0], got[1])
+        # mask 1 everywhere: the unmasked update, bit for bit
+        ones = np.ones_like(m)
+        a, ah = run(i, 0, B, ones)
+        b, bh = run(i, 0, B, ones, with_mask=False)
+        assert np.array_equal(a, b) and np.array_equal(ah, bh)
+        # the last row (a_s = 1) with mask 0: x0_init exactly
+        last = len(table) - 1
+        assert sch.alphas_prev[last] == 1.0
+        fin, _ = run(last, 0, B, np.zeros_like(m))
+        assert np.array_equal(fin, x0i)
 
 
 # ---- 5. / 6. tiny-UNet img2img and inpainting --------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""GPU checks of few-step sampling: the guidance-free single-branch step (csrc/single.hip, StableDiffusion.compile(..., cfg=False)) and the
+"""GPU checks of few-step sampling: the guidance-free single-branch step (csrc/sampler.hip, StableDiffusion.compile(..., cfg=False)) and the
 LCM table of variants/samplers.py -- tf_latent_stack1_* against group 0 of the CFG launches it replaces, one fused single-branch update against
 float64 numpy, tiny-UNet trajectories (graph == eager, reproducible from a seed, against the CPU oracle on B images with the context alone), the
 modes it composes with (inpaint, the inpainting checkpoint, ControlNet, LoRA), and the SD-1.5 size once."""

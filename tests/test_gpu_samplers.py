@@ -92,44 +92,104 @@ def test_one_fused_sampler_step_matches_float64(tf, name, dtype):
     from tinyfusers_amd.native import hip
     from tinyfusers_amd.storage.tensor import bfloat16
     from tinyfusers_amd.variants import samplers as S
-    B, C, H, W = 2, 4, 8, 12
-    n_img, g, offset = C * H * W, 7.5, 5
-    sch = S.make(name).schedule(25)
-    i = 9
-    table = sch.coeffs.copy()
-    table[i, 2] = table[i, 2] or 0.25                            # every term live: c_1 != 0 and c_n != 0
-    table[i, 3] = table[i, 3] or 0.6
-    rng = np.random.default_rng(4)
-    x = rng.standard_normal((B, C, H, W))
-    eps2 = rng.standard_normal((2 * B, C, H, W))
-    hist = rng.standard_normal((B, C, H, W))
-    dt = bfloat16 if dtype == "bf16" else np.float16
-    d_eps = tf.DeviceArray.from_numpy(eps2, dt, "nhwc")
-    eps2 = d_eps.numpy().astype(np.float64)                      # the values the kernel reads
-    d_tab = tf.DeviceArray.from_numpy(table.astype(np.float32), np.float32, "row")
+    for B, C, H, W in ((2, 4, 8, 12), (2, 3, 5, 7)):             # (105 elements per image: a partial last counter)
+        n_img, g, offset = C * H * W, 7.5, 5
+        sch = S.make(name).schedule(25)
+        i = 9
+        table = sch.coeffs.copy()
+        table[i, 2] = table[i, 2] or 0.25                            # every term live: c_1 != 0 and c_n != 0
+        table[i, 3] = table[i, 3] or 0.6
+        rng = np.random.default_rng(4)
+        x = rng.standard_normal((B, C, H, W))
+        eps2 = rng.standard_normal((2 * B, C, H, W))
+        hist = rng.standard_normal((B, C, H, W))
+        dt = bfloat16 if dtype == "bf16" else np.float16
+        d_eps = tf.DeviceArray.from_numpy(eps2, dt, "nhwc")
+        eps2 = d_eps.numpy().astype(np.float64)                      # the values the kernel reads
+        d_tab = tf.DeviceArray.from_numpy(table.astype(np.float32), np.float32, "row")
+        sp = tf.DeviceArray.zeros((8,), np.float32, "row")
+        entry = hip.tf_cfg_sampler_step_bf16 if dtype == "bf16" else hip.tf_cfg_sampler_step_f32
+
+        def run(row, x_in, hist_in):
+            lat = tf.DeviceArray.from_numpy(x_in.astype(np.float32), np.float32, "row")
+            h = tf.DeviceArray.from_numpy(hist_in.astype(np.float32), np.float32, "row")
+            _set_params(hip, sp, sch.timesteps[row], sch.alphas[row], sch.alphas_prev[row], g, row, SEED, offset)
+            entry(lat.ptr, d_eps.ptr, h.ptr, sp.ptr, d_tab.ptr, len(table), B, C, H, W, None)
+            return lat.numpy().astype(np.float64), h.numpy().astype(np.float64)
+
+        z = np.stack([randn_ref(SEED, offset + b, n_img, i, 1).reshape(C, H, W) for b in range(B)])
+        got, got_h = run(i, x, hist)
+        ref, ref_x0 = _step_ref(x, eps2, hist.astype(np.float32).astype(np.float64), sch.alphas[i], g, table[i], z)
+        assert np.all(np.abs(got - ref) <= 1e-5 * (1 + np.abs(ref))), float(np.max(np.abs(got - ref) / (1 + np.abs(ref))))
+        assert np.all(np.abs(got_h - ref_x0) <= 1e-5 * (1 + np.abs(ref_x0)))
+        # first step (c_1 == 0): the history is not read -- a NaN-filled one gives the zeroed one's finite result
+        assert table[0, 2] == 0.0
+        a, _ = run(0, x, np.full(x.shape, np.nan))
+        b, _ = run(0, x, np.zeros(x.shape))
+        assert np.isfinite(a).all() and np.array_equal(a, b)
+        z0 = np.stack([randn_ref(SEED, offset + k, n_img, 0, 1).reshape(C, H, W) for k in range(B)])
+        ref0, _ = _step_ref(x, eps2, 0.0, sch.alphas[0], g, table[0], z0)
+        assert np.all(np.abs(a - ref0) <= 1e-5 * (1 + np.abs(ref0)))
+
+
+# ---- 2b. the update's grid-stride loop: every form of the one kernel -------------------------------------------------------------------
+BIG = (3, 4, 512, 512)              # 786432 Philox counters: more than the 2048 x 256 threads of the largest grid, so some threads take a second trip
+
+
+@pytest.fixture(scope="module")
+def big_step(tf):
+    """Inputs of test_sampler_step_grid_stride_loop_equals_the_single_trip_launches, made once and only read: the host arrays and the device
+    copies of x0_init and the mask.  eps holds three guidance groups of B images as the kernel reads them, (group, image, H, W, C); a form of
+    G groups reads the first G."""
+    B, C, H, W = BIG
+    rng = np.random.default_rng(12)
+    x, hist, x0i = (rng.standard_normal(BIG, dtype=np.float32) for _ in range(3))
+    m = rng.random((B, 1, H, W), dtype=np.float32)
+    m[:, :, 0, :4], m[:, :, 1, :4] = 0.0, 1.0
+    eps = rng.standard_normal((3, B, H, W, C), dtype=np.float32)
+    return dict(x=x, hist=hist, eps=eps, d_x0i=tf.DeviceArray.from_numpy(x0i, np.float32, "row"), d_m=tf.DeviceArray.from_numpy(m, np.float32, "row"))
+
+
+@pytest.mark.parametrize("dtype", ["fp16", "bf16"])
+@pytest.mark.parametrize("form", ["cfg", "cfg-masked", "cfg3", "single", "single-masked"])
+def test_sampler_step_grid_stride_loop_equals_the_single_trip_launches(tf, big_step, form, dtype):
+    """Image k of one B = 3 launch (threads loop) == a B = 1 launch at image offset k (262144 counters: no thread loops), latent and history,
+    bit for bit, on a row with c_1 != 0 and c_n != 0.  No host reference: batch independence against the host Philox is asserted at small sizes."""
+    from tinyfusers_amd.native import hip
+    from tinyfusers_amd.storage.tensor import bfloat16
+    from tinyfusers_amd.variants import samplers as S
+    B, C, H, W = BIG
+    bf = dtype == "bf16"
+    suffix = "bf16" if bf else "f32"
+    groups = {"cfg": 2, "cfg-masked": 2, "cfg3": 3, "single": 1, "single-masked": 1}[form]
+    masked = form.endswith("masked")
+    entry = getattr(hip, {"cfg": "tf_cfg_sampler_step_", "cfg-masked": "tf_cfg_sampler_step_masked_", "cfg3": "tf_cfg3_sampler_step_",
+                          "single": "tf_sampler_step1_", "single-masked": "tf_sampler_step1_"}[form] + suffix)
+    sch = S.make("euler-a").schedule(25)
+    i, offset = 9, 5
+    table = sch.coeffs.astype(np.float32)
+    table[i, 2] = 0.25                                           # the history is read
+    assert table[i, 3] != 0.0                                    # the noise is live
+    d_tab = tf.DeviceArray.from_numpy(table, np.float32, "row")
     sp = tf.DeviceArray.zeros((8,), np.float32, "row")
-    entry = hip.tf_cfg_sampler_step_bf16 if dtype == "bf16" else hip.tf_cfg_sampler_step_f32
+    edit = tf.DeviceArray.zeros((4,), np.float32, "row")
+    hip.tf_set_step_params(edit.ptr, 1.5, 0.0, 0.0, 0.0, None)
+    d_x0i, d_m = big_step["d_x0i"], big_step["d_m"]
 
-    def run(row, x_in, hist_in):
-        lat = tf.DeviceArray.from_numpy(x_in.astype(np.float32), np.float32, "row")
-        h = tf.DeviceArray.from_numpy(hist_in.astype(np.float32), np.float32, "row")
-        _set_params(hip, sp, sch.timesteps[row], sch.alphas[row], sch.alphas_prev[row], g, row, SEED, offset)
-        entry(lat.ptr, d_eps.ptr, h.ptr, sp.ptr, d_tab.ptr, len(table), B, C, H, W, None)
-        return lat.numpy().astype(np.float64), h.numpy().astype(np.float64)
+    def run(first, nb):
+        lat = tf.DeviceArray.from_numpy(big_step["x"][first:first + nb], np.float32, "row")
+        h = tf.DeviceArray.from_numpy(big_step["hist"][first:first + nb], np.float32, "row")
+        e = tf.DeviceArray.from_numpy(big_step["eps"][:groups, first:first + nb].reshape(groups * nb, H, W, C), bfloat16 if bf else np.float16, "row")
+        _set_params(hip, sp, sch.timesteps[i], sch.alphas[i], sch.alphas_prev[i], 7.5, i, SEED, offset + first)
+        extra = (d_x0i.ptr + 4 * first * C * H * W, d_m.ptr + 4 * first * H * W) if masked else (None, None) if groups == 1 else (edit.ptr,) if groups == 3 else ()
+        entry(lat.ptr, e.ptr, h.ptr, sp.ptr, d_tab.ptr, len(table), *extra, nb, C, H, W, None)
+        return lat.numpy(), h.numpy()
 
-    z = np.stack([randn_ref(SEED, offset + b, n_img, i, 1).reshape(C, H, W) for b in range(B)])
-    got, got_h = run(i, x, hist)
-    ref, ref_x0 = _step_ref(x, eps2, hist.astype(np.float32).astype(np.float64), sch.alphas[i], g, table[i], z)
-    assert np.all(np.abs(got - ref) <= 1e-5 * (1 + np.abs(ref))), float(np.max(np.abs(got - ref) / (1 + np.abs(ref))))
-    assert np.all(np.abs(got_h - ref_x0) <= 1e-5 * (1 + np.abs(ref_x0)))
-    # first step (c_1 == 0): the history is not read -- a NaN-filled one gives the zeroed one's finite result
-    assert table[0, 2] == 0.0
-    a, _ = run(0, x, np.full(x.shape, np.nan))
-    b, _ = run(0, x, np.zeros(x.shape))
-    assert np.isfinite(a).all() and np.array_equal(a, b)
-    z0 = np.stack([randn_ref(SEED, offset + k, n_img, 0, 1).reshape(C, H, W) for k in range(B)])
-    ref0, _ = _step_ref(x, eps2, 0.0, sch.alphas[0], g, table[0], z0)
-    assert np.all(np.abs(a - ref0) <= 1e-5 * (1 + np.abs(ref0)))
+    got, got_h = run(0, B)
+    assert np.isfinite(got).all() and not np.array_equal(got[0], got[1])
+    for k in range(B):
+        one, one_h = run(k, 1)
+        assert np.array_equal(one[0], got[k]) and np.array_equal(one_h[0], got_h[k]), k
 
 
 # ---- 3. ancestral noise is fresh every step ---------------------------------------------------------------------------------------

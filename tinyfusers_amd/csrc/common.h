@@ -167,3 +167,13 @@ static constexpr bool kBF = TF_TU_BF != 0;
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline long long ceil_div_ll(long long a, long long b) { return (a + b - 1) / b; }
+
+// The launch geometry of every grid-stride kernel of one work item per thread: blocks of 256 threads, at most 2048 of them (8 per CU; the
+// kernel's loop strides the rest), at least 1
+#define EW_BLOCK 256
+static inline int ew_grid(long long nthreads) {
+  long long g = ceil_div_ll(nthreads, EW_BLOCK);
+  if (g > 256 * 8) g = 256 * 8;
+  if (g < 1) g = 1;
+  return (int)g;
+}

@@ -5,7 +5,7 @@
 #include "../../include/tinyfusers_hip.h"
 
 #define CT_MAX 16                        // entries of one launch (SD-1.5: 12 skip tensors + the middle block's output)
-#define CT_BLOCK 256
+#define CT_BLOCK EW_BLOCK                // (k_hint_from_u8 launches on ew_grid)
 #define CT_VPL 4                         // 16-byte vectors per lane and stream
 #define CT_CHUNK (CT_BLOCK * CT_VPL)     // vectors of one block
 
@@ -89,13 +89,6 @@ __global__ void __launch_bounds__(CT_BLOCK) k_hint_from_u8(T* __restrict__ out, 
   }
 }
 
-static inline int ct_grid(long long nthreads) {
-  long long g = (nthreads + CT_BLOCK - 1) / CT_BLOCK;
-  if (g > 256 * 8) g = 256 * 8;   // grid-stride the rest
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 extern "C" {
 
 int tf_control_add_16(int dtype, const void* table, int n_entries, const void* scales_f32, tfStream_t s) {
@@ -132,11 +125,11 @@ int tf_hint_from_u8_16(int dtype, void* out, const void* x_u8, long long n, tfSt
   const bool vec = n % 8 == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)x_u8 & 7) == 0;
   const unsigned char* in = (const unsigned char*)x_u8;
   if (dtype == TF_DTYPE_BF16) {
-    if (vec) hipLaunchKernelGGL((k_hint_from_u8<bf16_t, true>), dim3(ct_grid(n >> 3)), dim3(CT_BLOCK), 0, tf_hs(s), (bf16_t*)out, in, n);
-    else hipLaunchKernelGGL((k_hint_from_u8<bf16_t, false>), dim3(ct_grid(n)), dim3(CT_BLOCK), 0, tf_hs(s), (bf16_t*)out, in, n);
+    if (vec) hipLaunchKernelGGL((k_hint_from_u8<bf16_t, true>), dim3(ew_grid(n >> 3)), dim3(CT_BLOCK), 0, tf_hs(s), (bf16_t*)out, in, n);
+    else hipLaunchKernelGGL((k_hint_from_u8<bf16_t, false>), dim3(ew_grid(n)), dim3(CT_BLOCK), 0, tf_hs(s), (bf16_t*)out, in, n);
   } else {
-    if (vec) hipLaunchKernelGGL((k_hint_from_u8<half_t, true>), dim3(ct_grid(n >> 3)), dim3(CT_BLOCK), 0, tf_hs(s), (half_t*)out, in, n);
-    else hipLaunchKernelGGL((k_hint_from_u8<half_t, false>), dim3(ct_grid(n)), dim3(CT_BLOCK), 0, tf_hs(s), (half_t*)out, in, n);
+    if (vec) hipLaunchKernelGGL((k_hint_from_u8<half_t, true>), dim3(ew_grid(n >> 3)), dim3(CT_BLOCK), 0, tf_hs(s), (half_t*)out, in, n);
+    else hipLaunchKernelGGL((k_hint_from_u8<half_t, false>), dim3(ew_grid(n)), dim3(CT_BLOCK), 0, tf_hs(s), (half_t*)out, in, n);
   }
   TF_LAUNCH_CHECK();
   return TF_OK;

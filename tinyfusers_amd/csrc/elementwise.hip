@@ -4,14 +4,6 @@
 #include "common.h"
 #include "../../include/tinyfusers_hip.h"
 
-#define EW_BLOCK 256
-static inline int ew_grid(long long nvec) {
-  long long g = ceil_div_ll(nvec, EW_BLOCK);
-  if (g > 256 * 8) g = 256 * 8;  // 8 blocks/CU, grid-stride the rest
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 enum { OP_SILU = 0, OP_SIGMOID = 1, OP_GELU = 2, OP_QGELU = 3 };
 
 template <int OP>
@@ -322,19 +314,6 @@ __global__ void k_timestep_embedding(T* out, const float* params, int dim, float
     out[half_dim + i] = (T)sinf(a);
   }
 }
-// latent (B,C,H,W) f32 -> x (2B,H,W,C) f16, both CFG halves the same latent (variants/sd.py:31)
-template <typename T = half_t>
-__global__ void __launch_bounds__(EW_BLOCK) k_cfg_duplicate(T* __restrict__ x, const float* __restrict__ lat, int B, int C, int HW) {
-  long long n = (long long)B * C * HW, gs = (long long)gridDim.x * EW_BLOCK;
-  for (long long i = (long long)blockIdx.x * EW_BLOCK + threadIdx.x; i < n; i += gs) {
-    int c = (int)(i % C);
-    long long p = i / C;
-    int hw = (int)(p % HW), b = (int)(p / HW);
-    T v = (T)lat[((long long)b * C + c) * HW + hw];
-    x[i] = v;
-    x[n + i] = v;
-  }
-}
 // e = e_u + g (e_c - e_u); pred_x0 = (x - sqrt(1-a_t) e)/sqrt(a_t); x' = sqrt(a_prev) pred_x0 + sqrt(1-a_prev) e
 template <typename T = half_t>
 __global__ void __launch_bounds__(EW_BLOCK) k_cfg_ddim(float* __restrict__ lat, const T* __restrict__ eps2, const T* __restrict__ eps_c,
@@ -434,13 +413,6 @@ int tf_convert_bf16_to_f16(void* y_f16, const void* x_bf16, long long n, tfStrea
 int tf_timestep_embedding_bf16(void* out, const void* step_params, int dim, float max_period, tfStream_t s) {
   TF_REQUIRE(out && step_params && dim > 0 && dim % 2 == 0, "tf_timestep_embedding_bf16: dim=%d must be even", dim);
   hipLaunchKernelGGL(k_timestep_embedding<bf16_t>, dim3(1), dim3(256), 0, tf_hs(s), (bf16_t*)out, (const float*)step_params, dim, max_period);
-  TF_LAUNCH_CHECK();
-  return TF_OK;
-}
-int tf_cfg_duplicate_bf16(void* x2b, const void* latent, int B, int C, int H, int W, tfStream_t s) {
-  TF_REQUIRE(x2b && latent && B > 0 && C > 0 && H >= 0 && W >= 0, "tf_cfg_duplicate_bf16: bad arguments");
-  long long n = (long long)B * C * H * W;
-  hipLaunchKernelGGL(k_cfg_duplicate<bf16_t>, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, tf_hs(s), (bf16_t*)x2b, (const float*)latent, B, C, H * W);
   TF_LAUNCH_CHECK();
   return TF_OK;
 }
@@ -691,13 +663,6 @@ int tf_set_step_params_copy(void* step_params, float timestep, float a_t, float 
 int tf_timestep_embedding_f16(void* out, const void* step_params, int dim, float max_period, tfStream_t s) {
   TF_REQUIRE(out && step_params && dim > 0 && dim % 2 == 0, "tf_timestep_embedding_f16: dim=%d must be even", dim);
   hipLaunchKernelGGL(k_timestep_embedding<half_t>, dim3(1), dim3(256), 0, tf_hs(s), (half_t*)out, (const float*)step_params, dim, max_period);
-  TF_LAUNCH_CHECK();
-  return TF_OK;
-}
-int tf_cfg_duplicate_f16(void* x2b, const void* latent, int B, int C, int H, int W, tfStream_t s) {
-  TF_REQUIRE(x2b && latent && B > 0 && C > 0 && H >= 0 && W >= 0, "tf_cfg_duplicate_f16: bad arguments");
-  long long n = (long long)B * C * H * W;
-  hipLaunchKernelGGL(k_cfg_duplicate<half_t>, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, tf_hs(s), (half_t*)x2b, (const float*)latent, B, C, H * W);
   TF_LAUNCH_CHECK();
   return TF_OK;
 }

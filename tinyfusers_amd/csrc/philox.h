@@ -1,6 +1,6 @@
-// The device normal generator shared by csrc/sampler.hip and csrc/img2img.hip: Philox4x32-10 (Salmon et al. 2011, Random123), key = the
-// 64-bit seed, counter = (q, global image index, step, tag); the q-th counter of an image gives its NCHW elements 4q .. 4q+3 through two
-// Box-Muller pairs.  Tags: 0 the initial latent, 1 the ancestral noise of a step, 2 the known region of an inpainting step.
+// The device normal generator of csrc/sampler.hip: Philox4x32-10 (Salmon et al. 2011, Random123), key = the 64-bit seed, counter = (q, global
+// image index, step, tag); the q-th counter of an image gives its NCHW elements 4q .. 4q+3 through two Box-Muller pairs.  The tags are
+// listed at the top of csrc/sampler.hip.
 #pragma once
 #include "common.h"
 

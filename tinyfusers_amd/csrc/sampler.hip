@@ -1,28 +1,27 @@
-// Samplers beyond the reference's sigma = 0 DDIM update (variants/sd.py:14-25): the device-side normal generator and the fused
-// CFG + sampler update of tinyfusers_amd/variants/samplers.py.  Own translation unit: no existing kernel's code changes.
+// The sampler side of the captured step for every mode of tinyfusers_amd/variants/sd.py (the CFG pair, the inpainting blend, the concat
+// checkpoints' two or three guidance groups, the guidance-free single branch): the device-side normal generator, the parameter launch, the
+// step's HEAD (the latent stacked for the UNet: variants/sd.py:31) and its TAIL (guidance combine + sampler update, generalising
+// variants/sd.py:14-25 and :27-46; the coefficient rows are tinyfusers_amd/variants/samplers.py's).  Each kernel exists once; the C entries
+// differ in what their parameters mean and in which argument sets they refuse.
 //
-// Noise is Philox4x32-10 (Salmon et al. 2011, Random123), key = the 64-bit seed, counter = (q, global image index, step, tag); the q-th
-// counter of an image gives its NCHW elements 4q .. 4q+3 through two Box-Muller pairs.  An image's noise therefore depends on the seed, its
-// global index, the step and the tag only -- not on the batch size, the rank that owns it, or whether it is drawn by tf_randn_f32 or inline
-// by the sampler update.  Tags: 0 the initial latent, 1 the ancestral noise of a step (step = schedule index); the generator is in philox.h.
+// Noise is Philox4x32-10 (Salmon et al. 2011, Random123; the generator is in philox.h), key = the 64-bit seed, counter = (q, global image
+// index, step, tag); the q-th counter of an image gives its NCHW elements 4q .. 4q+3 through two Box-Muller pairs.  An image's noise
+// therefore depends on the seed, its global index, the step and the tag only -- not on the batch size, the rank that owns it, or whether it
+// is drawn by tf_randn_f32 or inline by the sampler update.  Tags:
+//   0  the initial latent: tf_randn_f32 and tf_noise_to_level_f32 (step 0) draw the same z, so an img2img image and a text-to-image image of
+//      one seed share their noise
+//   1  the ancestral noise of schedule row `step` (k_sampler_step, every form)
+//   2  the noise that puts the known region of an inpainting step on its trajectory, step = the schedule row (k_sampler_step, MASKED)
 #include "common.h"
 #include "philox.h"
 #include "../../include/tinyfusers_hip.h"
 
-#define SM_BLOCK 256
 enum { TF_SAMPLER_PARAM_WORDS = 8 };   // [0] t [1] a_t [2] a_prev [3] guidance (fp32) | [4] row [5] seed lo [6] seed hi [7] image offset (u32)
 
-static inline int sm_grid(long long nthreads) {
-  long long g = (nthreads + SM_BLOCK - 1) / SM_BLOCK;
-  if (g > 256 * 8) g = 256 * 8;   // grid-stride the rest
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 // out: `images` fp32 NCHW images of n_img elements each; image k is global image image0 + k
-__global__ void __launch_bounds__(SM_BLOCK) k_randn(float* __restrict__ out, long long n_img, int images, u32 k0, u32 k1, u32 image0, u32 step, u32 tag) {
-  const long long nq = (n_img + 3) >> 2, total = nq * images, gs = (long long)gridDim.x * SM_BLOCK;
-  for (long long t = (long long)blockIdx.x * SM_BLOCK + threadIdx.x; t < total; t += gs) {
+__global__ void __launch_bounds__(EW_BLOCK) k_randn(float* __restrict__ out, long long n_img, int images, u32 k0, u32 k1, u32 image0, u32 step, u32 tag) {
+  const long long nq = (n_img + 3) >> 2, total = nq * images, gs = (long long)gridDim.x * EW_BLOCK;
+  for (long long t = (long long)blockIdx.x * EW_BLOCK + threadIdx.x; t < total; t += gs) {
     const int k = (int)(t / nq);
     const long long q = t - (long long)k * nq;
     float z[4];
@@ -32,6 +31,23 @@ __global__ void __launch_bounds__(SM_BLOCK) k_randn(float* __restrict__ out, lon
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       if (j < left) o[j] = z[j];
+  }
+}
+
+// out = sqrt(a) x0 + sqrt(1 - a) z, z the tag-0 normal of global image image0 + k at step 0.  out may alias x0 (each element is read, then
+// written, by the same thread).  One thread per Philox counter: 4 NCHW elements
+__global__ void __launch_bounds__(EW_BLOCK) k_noise_to_level(float* out, const float* x0, long long n_img, int images, float a, u32 k0, u32 k1, u32 image0) {
+  const float sa = sqrtf(a), sn = sqrtf(1.0f - a);
+  const long long nq = (n_img + 3) >> 2, total = nq * images, gs = (long long)gridDim.x * EW_BLOCK;
+  for (long long t = (long long)blockIdx.x * EW_BLOCK + threadIdx.x; t < total; t += gs) {
+    const int k = (int)(t / nq);
+    const long long q = t - (long long)k * nq;
+    float z[4];
+    normal4(k0, k1, (u32)q, image0 + (u32)k, 0u, 0u, z);
+    const long long base = (long long)k * n_img + 4 * q, left = n_img - 4 * q;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (j < left) out[base + j] = sa * x0[base + j] + sn * z[j];
   }
 }
 
@@ -46,54 +62,156 @@ __global__ void __launch_bounds__(256) k_set_sampler_params(float* p, float t, f
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n16; i += (long long)gridDim.x * 256) dst[i] = src[i];
 }
 
-// e = e_u + g (e_c - e_u); x0 = (x - sqrt(1-a_t) e) / sqrt(a_t); x' = c_x x + c_0 x0 + c_1 x0_prev + c_n z; x0_prev <- x0.
-// [c_x, c_0, c_1, c_n] = coeffs[row], row = the schedule index the parameter launch wrote.  x0_prev is read only when c_1 != 0 (a fresh
-// history never reaches the first step) and the noise is drawn only when c_n != 0.  One thread per Philox counter: 4 NCHW elements.
-template <typename T>
-__global__ void __launch_bounds__(SM_BLOCK) k_cfg_sampler(float* __restrict__ lat, const T* __restrict__ eps2, float* __restrict__ x0h,
-                                                          const float* __restrict__ params, const float* __restrict__ coeffs, int rows, int B, int C, int HW) {
+// The head: latent (B,C,HW) f32 [, cond (B,Cc,HW) f32] -> x (G*B, HW, C+Cc) 16-bit NHWC: every group the same [latent | cond] pixels, the
+// cond channels +0 in the groups whose bit of `drop` is set (bits at or above G name no group and are ignored).  Cc == 0: cond is never
+// read.  A pixel is 2 (C+Cc) bytes (18 for the inpainting model), so nothing above the element's own 2-byte alignment holds for a pixel
+// start: one thread per output element of a group, consecutive threads on consecutive addresses.  G is compile-time: the G stores unroll, as
+// the CFG pair's two always did (the launch of the benchmark path), in 19 VGPRs where a runtime loop takes 23.
+template <typename T, int G>
+__global__ void __launch_bounds__(EW_BLOCK) k_latent_stack(T* __restrict__ x, const float* __restrict__ lat, const float* __restrict__ cond, int B, int C, int Cc,
+                                                           int HW, unsigned drop) {
+  const int Ct = C + Cc;
+  const long long n = (long long)B * HW * Ct, gs = (long long)gridDim.x * EW_BLOCK;
+  for (long long i = (long long)blockIdx.x * EW_BLOCK + threadIdx.x; i < n; i += gs) {
+    const int c = (int)(i % Ct);
+    const long long p = i / Ct;
+    const int hw = (int)(p % HW), b = (int)(p / HW);
+    const bool is_cond = c >= C;
+    const T v = is_cond ? (T)cond[((long long)b * Cc + (c - C)) * HW + hw] : (T)lat[((long long)b * C + c) * HW + hw];
+    const T zero = (T)0.0f;
+    for (int g = 0; g < G; ++g) x[(long long)g * n + i] = (is_cond && ((drop >> g) & 1u)) ? zero : v;
+  }
+}
+
+// The tail.  eps = G guidance groups of (B, HW, C) 16-bit NHWC, combined into e:
+//   G = 1  e = eps                                  (params[3], the guidance, is not read)
+//   G = 2  e = e_u + g (e_c - e_u)                  g = params[3]
+//   G = 3  e = e0 + g_T (e2 - e1) + g_I (e1 - e0)   g_T = params[3], g_I = edit[0]
+// then x0 = (x - sqrt(1-a_t) e) / sqrt(a_t); x' = c_x x + c_0 x0 + c_1 x0_prev + c_n z (tag 1); x0_prev <- x0.  [c_x, c_0, c_1, c_n] =
+// coeffs[row], row = the schedule index the parameter launch wrote.  x0_prev is read only when c_1 != 0 (a fresh history never reaches the
+// first step) and the tag-1 noise is drawn only when c_n != 0.  MASKED: then the inpainting blend
+// x' <- m x' + (1 - m) (sqrt(a_s) x0_init + sqrt(1 - a_s) z2), a_s = params[2] (the a_prev of tf_set_sampler_params), z2 the tag-2 normal at
+// step = row, always drawn.  m = 1 leaves x' as it is (1 x' + 0); m = 0 at the last step (a_s = 1) gives x0_init exactly.  mask (B, 1, H, W)
+// fp32.  G and MASKED are compile-time, and every form keeps these expressions in this order: -ffp-contract=fast contracts by expression
+// shape, and the sampled trajectories are compared bit for bit.  One thread per Philox counter: 4 NCHW elements.
+template <typename T, int G, bool MASKED>
+__global__ void __launch_bounds__(EW_BLOCK) k_sampler_step(float* __restrict__ lat, const T* __restrict__ eps, float* __restrict__ x0h,
+                                                           const float* __restrict__ params, const float* __restrict__ coeffs, int rows,
+                                                           const float* __restrict__ edit, const float* __restrict__ x0i, const float* __restrict__ mask,
+                                                           int B, int C, int HW) {
   const u32* w = reinterpret_cast<const u32*>(params);
-  const float a_t = params[1], g = params[3];
+  const float a_t = params[1], a_s = params[2];
+  const float g = G >= 2 ? params[3] : 0.f, gi = G == 3 ? edit[0] : 0.f;
   u32 row = w[4];
   if (row >= (u32)rows) row = (u32)rows - 1;                     // memory safety only: the host entry writes a row of the schedule
   const u32 k0 = w[5], k1 = w[6], image0 = w[7];
   const float cx = coeffs[4 * row], c0 = coeffs[4 * row + 1], c1 = coeffs[4 * row + 2], cn = coeffs[4 * row + 3];
   const float s1 = sqrtf(1.0f - a_t), r = sqrtf(a_t);
-  const long long n_img = (long long)C * HW, n = n_img * B, nq = (n_img + 3) >> 2, total = nq * B, gs = (long long)gridDim.x * SM_BLOCK;
-  for (long long t = (long long)blockIdx.x * SM_BLOCK + threadIdx.x; t < total; t += gs) {
+  const float ra = sqrtf(a_s), rn = sqrtf(1.0f - a_s);
+  const long long n_img = (long long)C * HW, n = n_img * B, nq = (n_img + 3) >> 2, total = nq * B, gs = (long long)gridDim.x * EW_BLOCK;
+  for (long long t = (long long)blockIdx.x * EW_BLOCK + threadIdx.x; t < total; t += gs) {
     const int b = (int)(t / nq);
     const long long q = t - (long long)b * nq;
-    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    float z[4] = {0.f, 0.f, 0.f, 0.f}, z2[4] = {0.f, 0.f, 0.f, 0.f};
     if (cn != 0.f) normal4(k0, k1, (u32)q, image0 + (u32)b, row, 1u, z);
+    if (MASKED) normal4(k0, k1, (u32)q, image0 + (u32)b, row, 2u, z2);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const long long e = 4 * q + j;
       if (e >= n_img) break;
       const int c = (int)(e / HW), hw = (int)(e - (long long)c * HW);
       const long long i = (long long)b * n_img + e, je = ((long long)b * HW + hw) * C + c;
-      const float eu = (float)eps2[je], ec = (float)eps2[n + je];
-      const float ee = eu + g * (ec - eu);
+      float ee;
+      if (G == 1) {
+        ee = (float)eps[je];
+      } else if (G == 2) {
+        const float eu = (float)eps[je], ec = (float)eps[n + je];
+        ee = eu + g * (ec - eu);
+      } else {
+        const float e0 = (float)eps[je], e1 = (float)eps[n + je], e2 = (float)eps[2 * n + je];
+        ee = e0 + g * (e2 - e1) + gi * (e1 - e0);
+      }
       const float x = lat[i];
       const float x0 = (x - s1 * ee) / r;
       float xn = cx * x + c0 * x0;
       if (c1 != 0.f) xn += c1 * x0h[i];
       if (cn != 0.f) xn += cn * z[j];
+      if (MASKED) {
+        const float m = mask[(long long)b * HW + hw];
+        const float kn = ra * x0i[i] + rn * z2[j];
+        xn = m * xn + (1.0f - m) * kn;
+      }
       lat[i] = xn;
       x0h[i] = x0;
     }
   }
 }
 
+// The head's launch, and the argument rule of each of its three entries in front of it.
 template <typename T>
-static int cfg_sampler_step(const char* name, void* latent, const void* eps2, void* x0_hist, const void* params, const void* coeffs, int rows, int B, int C, int H, int W,
-                            tfStream_t s) {
-  TF_REQUIRE(latent && eps2 && x0_hist && params && coeffs && rows >= 1 && B > 0 && C > 0 && H > 0 && W > 0, "%s: bad arguments (rows=%d B=%d C=%d H=%d W=%d)", name, rows, B, C, H, W);
-  const long long n_img = (long long)C * H * W;
-  TF_REQUIRE(n_img <= (1LL << 32), "%s: %lld elements per image exceed the 2^32 Philox counters of an image", name, n_img);
-  hipLaunchKernelGGL(k_cfg_sampler<T>, dim3(sm_grid(((n_img + 3) >> 2) * B)), dim3(SM_BLOCK), 0, tf_hs(s), (float*)latent, (const T*)eps2, (float*)x0_hist,
-                     (const float*)params, (const float*)coeffs, rows, B, C, H * W);
+static int latent_stack(void* x_out, const void* latent, const void* cond, int B, int C, int Cc, int H, int W, int groups, unsigned drop_bits, tfStream_t s) {
+  const long long n = (long long)B * H * W * (C + Cc);
+  void (*k)(T*, const float*, const float*, int, int, int, int, unsigned) =
+      groups == 3 ? k_latent_stack<T, 3> : groups == 2 ? k_latent_stack<T, 2> : k_latent_stack<T, 1>;
+  hipLaunchKernelGGL(k, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, tf_hs(s), (T*)x_out, (const float*)latent, (const float*)cond, B, C, Cc, H * W, drop_bits);
   TF_LAUNCH_CHECK();
   return TF_OK;
+}
+
+// what the two entries that take conditioning channels ask of the sizes and of x_out
+static int stack_limits(const char* name, const void* x_out, int C, int Cc, int H, int W) {
+  TF_REQUIRE((long long)H * W < (1LL << 31) && (long long)C + Cc < (1LL << 16), "%s: %lld pixels of %lld channels", name, (long long)H * W, (long long)C + Cc);
+  TF_REQUIRE(((uintptr_t)x_out & 1) == 0, "%s: x_out must be 2-byte aligned", name);
+  return TF_OK;
+}
+
+// the CFG pair of the latent alone; H == 0 or W == 0 is accepted and writes nothing
+template <typename T>
+static int cfg_duplicate(const char* name, void* x2b, const void* latent, int B, int C, int H, int W, tfStream_t s) {
+  TF_REQUIRE(x2b && latent && B > 0 && C > 0 && H >= 0 && W >= 0, "%s: bad arguments", name);
+  return latent_stack<T>(x2b, latent, nullptr, B, C, 0, H, W, 2, 0u, s);
+}
+
+template <typename T>
+static int cfg_concat(const char* name, void* x_out, const void* latent, const void* cond, int B, int C, int Cc, int H, int W, int groups, unsigned drop_bits,
+                      tfStream_t s) {
+  TF_REQUIRE(x_out && latent && cond && B > 0 && C > 0 && Cc > 0 && H > 0 && W > 0, "%s: bad arguments (B=%d C=%d Cc=%d H=%d W=%d)", name, B, C, Cc, H, W);
+  TF_REQUIRE(groups == 2 || groups == 3, "%s: groups=%d (2 or 3)", name, groups);
+  if (const int e = stack_limits(name, x_out, C, Cc, H, W)) return e;
+  return latent_stack<T>(x_out, latent, cond, B, C, Cc, H, W, groups, drop_bits, s);
+}
+
+template <typename T>
+static int latent_stack1(const char* name, void* x_out, const void* latent, const void* cond, int B, int C, int Cc, int H, int W, tfStream_t s) {
+  TF_REQUIRE(x_out && latent && B > 0 && C > 0 && Cc >= 0 && H > 0 && W > 0, "%s: bad arguments (B=%d C=%d Cc=%d H=%d W=%d)", name, B, C, Cc, H, W);
+  TF_REQUIRE((cond != nullptr) == (Cc > 0), "%s: cond is %s with Cc=%d (cond == NULL iff Cc == 0)", name, cond ? "set" : "NULL", Cc);
+  if (const int e = stack_limits(name, x_out, C, Cc, H, W)) return e;
+  return latent_stack<T>(x_out, latent, cond, B, C, Cc, H, W, 1, 0u, s);
+}
+
+// The tail's launch: the arguments every entry shares, then the instance of (G, mask set).  own_ptrs: the pointers only this entry requires
+// are set (part of "bad arguments"); broken_rule: NULL, or the text of the entry's own rule that the arguments break.
+template <typename T>
+static int sampler_step(const char* name, int G, void* latent, const void* eps, void* x0_hist, const void* params, const void* coeffs, int rows, const void* edit,
+                        const void* x0_init, const void* mask, bool own_ptrs, const char* broken_rule, int B, int C, int H, int W, tfStream_t s) {
+  TF_REQUIRE(latent && eps && x0_hist && params && coeffs && own_ptrs && rows >= 1 && B > 0 && C > 0 && H > 0 && W > 0, "%s: bad arguments (rows=%d B=%d C=%d H=%d W=%d)",
+             name, rows, B, C, H, W);
+  TF_REQUIRE(!broken_rule, "%s: bad arguments (%s)", name, broken_rule);
+  const long long n_img = (long long)C * H * W;
+  TF_REQUIRE(n_img <= (1LL << 32), "%s: %lld elements per image exceed the 2^32 Philox counters of an image", name, n_img);
+  void (*k)(float*, const T*, float*, const float*, const float*, int, const float*, const float*, const float*, int, int, int) =
+      G == 3 ? k_sampler_step<T, 3, false>
+      : G == 2 ? (mask ? k_sampler_step<T, 2, true> : k_sampler_step<T, 2, false>)
+               : (mask ? k_sampler_step<T, 1, true> : k_sampler_step<T, 1, false>);
+  hipLaunchKernelGGL(k, dim3(ew_grid(((n_img + 3) >> 2) * B)), dim3(EW_BLOCK), 0, tf_hs(s), (float*)latent, (const T*)eps, (float*)x0_hist, (const float*)params,
+                     (const float*)coeffs, rows, (const float*)edit, (const float*)x0_init, (const float*)mask, B, C, H * W);
+  TF_LAUNCH_CHECK();
+  return TF_OK;
+}
+
+// tf_sampler_step1_*: both of x0_init and mask (the masked form) or neither
+static inline const char* step1_rule(const void* x0_init, const void* mask) {
+  return (x0_init != nullptr) == (mask != nullptr) ? nullptr : "x0_init and mask go together: both set for the masked form, both NULL for the plain one";
 }
 
 extern "C" {
@@ -103,8 +221,23 @@ int tf_randn_f32(void* out, int images, long long per_image, unsigned seed_lo, u
              images, per_image, image_offset, step, tag);
   TF_REQUIRE(per_image <= (1LL << 32), "tf_randn_f32: %lld elements per image exceed the 2^32 Philox counters of an image", per_image);
   if (images == 0 || per_image == 0) return TF_OK;
-  hipLaunchKernelGGL(k_randn, dim3(sm_grid(((per_image + 3) >> 2) * images)), dim3(SM_BLOCK), 0, tf_hs(s), (float*)out, per_image, images, seed_lo, seed_hi,
+  hipLaunchKernelGGL(k_randn, dim3(ew_grid(((per_image + 3) >> 2) * images)), dim3(EW_BLOCK), 0, tf_hs(s), (float*)out, per_image, images, seed_lo, seed_hi,
                      (u32)image_offset, (u32)step, (u32)tag);
+  TF_LAUNCH_CHECK();
+  return TF_OK;
+}
+
+int tf_noise_to_level_f32(void* out, const void* x0, int images, long long per_image, float a, unsigned seed_lo, unsigned seed_hi, int image_offset,
+                          tfStream_t s) {
+  TF_REQUIRE(out && x0 && images >= 0 && per_image >= 0 && image_offset >= 0, "tf_noise_to_level_f32: bad arguments (images=%d per_image=%lld offset=%d)",
+             images, per_image, image_offset);
+  TF_REQUIRE(a > 0.0f && a <= 1.0f, "tf_noise_to_level_f32: the level a = %g must lie in (0, 1]", (double)a);
+  TF_REQUIRE(per_image <= (1LL << 32), "tf_noise_to_level_f32: %lld elements per image exceed the 2^32 Philox counters of an image", per_image);
+  TF_REQUIRE(out == x0 || (const char*)out + images * per_image * 4 <= (const char*)x0 || (const char*)x0 + images * per_image * 4 <= (const char*)out,
+             "tf_noise_to_level_f32: out and x0 overlap without being the same array");
+  if (images == 0 || per_image == 0) return TF_OK;
+  hipLaunchKernelGGL(k_noise_to_level, dim3(ew_grid(((per_image + 3) >> 2) * images)), dim3(EW_BLOCK), 0, tf_hs(s), (float*)out, (const float*)x0,
+                     per_image, images, a, seed_lo, seed_hi, (u32)image_offset);
   TF_LAUNCH_CHECK();
   return TF_OK;
 }
@@ -124,12 +257,72 @@ int tf_set_sampler_params(void* step_params, float timestep, float a_t, float a_
   return TF_OK;
 }
 
+int tf_cfg_duplicate_f16(void* x2b, const void* latent, int B, int C, int H, int W, tfStream_t s) {
+  return cfg_duplicate<half_t>("tf_cfg_duplicate_f16", x2b, latent, B, C, H, W, s);
+}
+
+int tf_cfg_duplicate_bf16(void* x2b, const void* latent, int B, int C, int H, int W, tfStream_t s) {
+  return cfg_duplicate<bf16_t>("tf_cfg_duplicate_bf16", x2b, latent, B, C, H, W, s);
+}
+
+int tf_cfg_concat_f16(void* x_out, const void* latent, const void* cond, int B, int C, int Cc, int H, int W, int groups, unsigned drop_bits, tfStream_t s) {
+  return cfg_concat<half_t>("tf_cfg_concat_f16", x_out, latent, cond, B, C, Cc, H, W, groups, drop_bits, s);
+}
+
+int tf_cfg_concat_bf16(void* x_out, const void* latent, const void* cond, int B, int C, int Cc, int H, int W, int groups, unsigned drop_bits, tfStream_t s) {
+  return cfg_concat<bf16_t>("tf_cfg_concat_bf16", x_out, latent, cond, B, C, Cc, H, W, groups, drop_bits, s);
+}
+
+int tf_latent_stack1_f16(void* x_out, const void* latent, const void* cond, int B, int C, int Cc, int H, int W, tfStream_t s) {
+  return latent_stack1<half_t>("tf_latent_stack1_f16", x_out, latent, cond, B, C, Cc, H, W, s);
+}
+
+int tf_latent_stack1_bf16(void* x_out, const void* latent, const void* cond, int B, int C, int Cc, int H, int W, tfStream_t s) {
+  return latent_stack1<bf16_t>("tf_latent_stack1_bf16", x_out, latent, cond, B, C, Cc, H, W, s);
+}
+
 int tf_cfg_sampler_step_f32(void* latent, const void* eps2, void* x0_hist, const void* params, const void* coeffs, int rows, int B, int C, int H, int W, tfStream_t s) {
-  return cfg_sampler_step<half_t>("tf_cfg_sampler_step_f32", latent, eps2, x0_hist, params, coeffs, rows, B, C, H, W, s);
+  return sampler_step<half_t>("tf_cfg_sampler_step_f32", 2, latent, eps2, x0_hist, params, coeffs, rows, nullptr, nullptr, nullptr, true, nullptr, B, C, H, W, s);
 }
 
 int tf_cfg_sampler_step_bf16(void* latent, const void* eps2, void* x0_hist, const void* params, const void* coeffs, int rows, int B, int C, int H, int W, tfStream_t s) {
-  return cfg_sampler_step<bf16_t>("tf_cfg_sampler_step_bf16", latent, eps2, x0_hist, params, coeffs, rows, B, C, H, W, s);
+  return sampler_step<bf16_t>("tf_cfg_sampler_step_bf16", 2, latent, eps2, x0_hist, params, coeffs, rows, nullptr, nullptr, nullptr, true, nullptr, B, C, H, W, s);
+}
+
+int tf_cfg_sampler_step_masked_f32(void* latent, const void* eps2, void* x0_hist, const void* params, const void* coeffs, int rows, const void* x0_init,
+                                   const void* mask, int B, int C, int H, int W, tfStream_t s) {
+  return sampler_step<half_t>("tf_cfg_sampler_step_masked_f32", 2, latent, eps2, x0_hist, params, coeffs, rows, nullptr, x0_init, mask, x0_init && mask, nullptr, B, C,
+                              H, W, s);
+}
+
+int tf_cfg_sampler_step_masked_bf16(void* latent, const void* eps2, void* x0_hist, const void* params, const void* coeffs, int rows, const void* x0_init,
+                                    const void* mask, int B, int C, int H, int W, tfStream_t s) {
+  return sampler_step<bf16_t>("tf_cfg_sampler_step_masked_bf16", 2, latent, eps2, x0_hist, params, coeffs, rows, nullptr, x0_init, mask, x0_init && mask, nullptr, B, C,
+                              H, W, s);
+}
+
+int tf_cfg3_sampler_step_f32(void* latent, const void* eps3, void* x0_hist, const void* step_params, const void* coeffs, int rows, const void* edit_params,
+                             int B, int C, int H, int W, tfStream_t s) {
+  return sampler_step<half_t>("tf_cfg3_sampler_step_f32", 3, latent, eps3, x0_hist, step_params, coeffs, rows, edit_params, nullptr, nullptr, edit_params != nullptr,
+                              nullptr, B, C, H, W, s);
+}
+
+int tf_cfg3_sampler_step_bf16(void* latent, const void* eps3, void* x0_hist, const void* step_params, const void* coeffs, int rows, const void* edit_params,
+                              int B, int C, int H, int W, tfStream_t s) {
+  return sampler_step<bf16_t>("tf_cfg3_sampler_step_bf16", 3, latent, eps3, x0_hist, step_params, coeffs, rows, edit_params, nullptr, nullptr, edit_params != nullptr,
+                              nullptr, B, C, H, W, s);
+}
+
+int tf_sampler_step1_f32(void* latent, const void* eps, void* x0_hist, const void* step_params, const void* coeffs, int rows, const void* x0_init, const void* mask,
+                         int B, int C, int H, int W, tfStream_t s) {
+  return sampler_step<half_t>("tf_sampler_step1_f32", 1, latent, eps, x0_hist, step_params, coeffs, rows, nullptr, x0_init, mask, true, step1_rule(x0_init, mask), B, C,
+                              H, W, s);
+}
+
+int tf_sampler_step1_bf16(void* latent, const void* eps, void* x0_hist, const void* step_params, const void* coeffs, int rows, const void* x0_init, const void* mask,
+                          int B, int C, int H, int W, tfStream_t s) {
+  return sampler_step<bf16_t>("tf_sampler_step1_bf16", 1, latent, eps, x0_hist, step_params, coeffs, rows, nullptr, x0_init, mask, true, step1_rule(x0_init, mask), B, C,
+                              H, W, s);
 }
 
 }  // extern "C"

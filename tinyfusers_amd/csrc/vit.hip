@@ -9,14 +9,8 @@
 #include "common.h"
 #include "../../include/tinyfusers_hip.h"
 
-#define VIT_BLOCK 256
+#define VIT_BLOCK EW_BLOCK     // (k_vit_patchify and k_gelu_erf launch on ew_grid)
 #define VIT_LN_MAXV 5          // k_layer_norm's register form (csrc/norm.hip): a lane holds <= 5 vectors of 8, D <= 2560
-static inline int vit_grid(long long nvec) {
-  long long g = ceil_div_ll(nvec, VIT_BLOCK);
-  if (g > 256 * 8) g = 256 * 8;
-  if (g < 1) g = 1;
-  return (int)g;
-}
 
 struct Norm3 { float scale[3], shift[3]; };
 
@@ -142,9 +136,9 @@ int tf_vit_patchify_u8_16(int dtype, void* out, const void* image_u8, int B, int
   const long long nvec = (long long)B * (S / P) * (S / P) * (Kpad >> 3);
   TfProfScope prof_(TF_PROF_FAM_VIT_ELEMENTWISE, (double)B * S * S * 3.0 + (double)nvec * 16.0, tf_hs(s));    // the image in, the patch matrix out
   if (dtype == TF_DTYPE_BF16)
-    hipLaunchKernelGGL(k_vit_patchify<bf16_t>, dim3(vit_grid(nvec)), dim3(VIT_BLOCK), 0, tf_hs(s), (bf16_t*)out, (const unsigned char*)image_u8, S, P, Kpad, nvec, nm);
+    hipLaunchKernelGGL(k_vit_patchify<bf16_t>, dim3(ew_grid(nvec)), dim3(VIT_BLOCK), 0, tf_hs(s), (bf16_t*)out, (const unsigned char*)image_u8, S, P, Kpad, nvec, nm);
   else
-    hipLaunchKernelGGL(k_vit_patchify<half_t>, dim3(vit_grid(nvec)), dim3(VIT_BLOCK), 0, tf_hs(s), (half_t*)out, (const unsigned char*)image_u8, S, P, Kpad, nvec, nm);
+    hipLaunchKernelGGL(k_vit_patchify<half_t>, dim3(ew_grid(nvec)), dim3(VIT_BLOCK), 0, tf_hs(s), (half_t*)out, (const unsigned char*)image_u8, S, P, Kpad, nvec, nm);
   TF_LAUNCH_CHECK();
   return TF_OK;
 }
@@ -178,8 +172,8 @@ int tf_gelu_erf_16(int dtype, void* y, const void* x, long long n, tfStream_t s)
   TF_REQUIRE(VIT_ALIGNED16(y) && VIT_ALIGNED16(x), "tf_gelu_erf_16: y and x must be 16-byte aligned");
   if (n == 0) return TF_OK;
   TfProfScope prof_(TF_PROF_FAM_VIT_ELEMENTWISE, (double)n * 4.0, tf_hs(s));
-  if (dtype == TF_DTYPE_BF16) hipLaunchKernelGGL(k_gelu_erf<bf16_t>, dim3(vit_grid(n >> 3)), dim3(VIT_BLOCK), 0, tf_hs(s), (bf16_t*)y, (const bf16_t*)x, n);
-  else hipLaunchKernelGGL(k_gelu_erf<half_t>, dim3(vit_grid(n >> 3)), dim3(VIT_BLOCK), 0, tf_hs(s), (half_t*)y, (const half_t*)x, n);
+  if (dtype == TF_DTYPE_BF16) hipLaunchKernelGGL(k_gelu_erf<bf16_t>, dim3(ew_grid(n >> 3)), dim3(VIT_BLOCK), 0, tf_hs(s), (bf16_t*)y, (const bf16_t*)x, n);
+  else hipLaunchKernelGGL(k_gelu_erf<half_t>, dim3(ew_grid(n >> 3)), dim3(VIT_BLOCK), 0, tf_hs(s), (half_t*)y, (const half_t*)x, n);
   TF_LAUNCH_CHECK();
   return TF_OK;
 }

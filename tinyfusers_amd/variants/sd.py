@@ -17,7 +17,7 @@ runs inside the same captured step: its residuals enter the UNet's skip connecti
 LoRA adapters (storage/lora.py; ``load_lora``, ``set_adapters``, ``adapters``, ``unload_lora``) are merged on the device into fresh weight buffers
 (tf_lora_merge_16, one launch per touched module, from the kept base weight); a compiled model re-captures its step.
 ``compile(..., cfg=False)`` is the guidance-free step of few-step samplers (samplers.LCM with an LCM-LoRA): ONE guidance group -- the UNet runs
-on B images against the context alone, between tf_latent_stack1_* and tf_sampler_step1_* (csrc/single.hip).
+on B images against the context alone, between tf_latent_stack1_* and tf_sampler_step1_* (csrc/sampler.hip).
 
 How the object is laid out.  Everything ``compile`` / ``start`` / ``set_context`` / ``set_adapters`` keep on the model is declared, with its
 "not compiled" value, in ``_reset_state``: ``__init__`` runs all of it, ``compile`` the per-compile part, so a re-compile with other flags drops the
