@@ -188,7 +188,8 @@ int tf_gemm_tune_trace(int on);
 int tf_gemm_tune_trace_dump(const char* path);
 /* test / tuning hook, kernel SELECTION only (every setting computes the same result): bits 3/4 force the deep/wide ring, 5/6 the
  * n-fastest/m-fastest block order, 7 (128) the patch variant of the 3x3 convolutions (k_igemm_patch), 8 (256) the variant whose consumer
- * waves issue part of the weight loads, each where the shape is eligible; 9 (512) the 256-row ping-pong kernel k_igemm_pp (with
+ * waves issue part of the weight loads, each where the shape is eligible (a LayerNorm-folded linear fails under bit 7: the patch kernel has no
+ * fold, and the deep ring it gives way to is for the geometries it refuses); 9 (512) the 256-row ping-pong kernel k_igemm_pp (with
  * tf_gemm_force_config(256, BN, split), BN in {128, 160, 256}: fails where it cannot take the launch), 10 (1024) the persistent short-K
  * kernel k_gemm_c4, 11 (2048) the patch form of the ping-pong kernel k_igemm_pp3 (3x3 / stride 1 convolutions on 96 / 48 / 24-pixel output rows, with
  * tf_gemm_force_config(192, BN, 1): the tile width is the instance's own; fails where it cannot take the launch), 13 (8192) the ping-pong kernel's

@@ -222,6 +222,9 @@ static int resolve(const GemmP& p, void* workspace, size_t workspace_bytes, int 
     t.variant = (blocks > 256 && p.ktiles / t.c.splitk <= 24) ? V_WIDE : V_RING;
   }
   if (g_force_variant >= 0 && !(p.gi_part && p.S == 3)) t.variant = g_force_variant;
+  // k_igemm_patch has no LayerNorm fold (patch_setup): asked for by name on a folded launch it says so, like the families with a fallback in
+  // settle_variant -- the deep ring it quietly runs instead is for the convolution geometries it refuses, not for another epilogue
+  if (g_force_variant == V_PATCH && p.ln_colsum) { tf_set_error("run_gemm: the patch kernel cannot run this launch (the LayerNorm fold; M=%d N=%d K=%d)", p.M, p.N, p.K); return TF_E_UNSUPPORTED; }
   int rc = settle_variant(p, &t, force_bm != 0, workspace != nullptr, stats_heard);
   if (rc) return rc;
   if (g_force_order >= 0) t.order = g_force_order;
