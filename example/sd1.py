@@ -15,6 +15,7 @@ BASELINE config 3: full 50-step sampler, batch 1, end-to-end img/s.
     python -m example.sd1 --steps 20 --sampler dpmpp2m --control-image edges.npy [--control-ckpt control_v11p_sd15_canny.safetensors] [--control-scale 1.0]   # ControlNet
     python -m example.sd1 --steps 20 --sampler dpmpp2m --lora style.safetensors:0.8 --lora lcm.safetensors:1:0   # LoRA adapters, FILE[:w[:w_te]], merged on the device
     python -m example.sd1 --steps 4 --sampler lcm --no-cfg --lora lcm.safetensors:1:0   # few-step sampling: the LCM sampler on the guidance-free single-branch step
+    python -m example.sd1 --steps 20 --sampler dpmpp2m --freeu 0.9,0.2,1.5,1.6   # FreeU: s1,s2,b1,b2 (the values usually quoted for SD-1.5)
     python -m example.sd1 --steps 20 --sampler dpmpp2m --ip-adapter ip-adapter_sd15.safetensors --ip-embeds e.npy [--ip-scale 0.6]   # IP-Adapter: an image prompt, as CLIP image embeddings (1, 1024)
     python -m example.sd1 --steps 20 --sampler dpmpp2m --ip-adapter ip-adapter_sd15.safetensors --ip-image x.npy [--clip-vision image_encoder.safetensors]   # ... or as the picture itself, uint8 (224, 224, 3): the CLIP ViT-H tower runs on the device
 With --ckpt the configuration is read off the checkpoint's conv_in (4, 9 or 8 input channels); --concat picks it on synthetic weights.
@@ -68,7 +69,20 @@ if __name__ == "__main__":
     ap.add_argument("--clip-vision", default="", help="with --ip-image: the CLIP image encoder's checkpoint (CLIPVisionModelWithProjection .safetensors / .bin); "
                                                       "default: synthetic ViT-H weights")
     ap.add_argument("--ip-scale", type=float, default=None, help="with --ip-adapter: the adapter's strength (default 1.0)")
+    ap.add_argument("--freeu", default=None, metavar="S1,S2,B1,B2",
+                    help="FreeU inside the captured step (needs --sampler): the Fourier filter's scale on the skips and the backbone factor of decoder stages 1 and 2; "
+                         "0.9,0.2,1.5,1.6 are the values usually quoted for SD-1.5")
     args = ap.parse_args()
+    freeu = None
+    if args.freeu is not None:
+        if not args.sampler:
+            ap.error("--freeu needs --sampler")
+        try:
+            freeu = tuple(float(v) for v in args.freeu.split(","))
+        except ValueError:
+            freeu = ()
+        if len(freeu) != 4 or not all(np.isfinite(freeu)):
+            ap.error(f"--freeu {args.freeu}: expected four finite floats S1,S2,B1,B2")
     if (args.ip_embeds or args.ip_image or args.clip_vision or args.ip_scale is not None) and args.ip_adapter is None:
         ap.error("--ip-embeds, --ip-image, --clip-vision and --ip-scale need --ip-adapter")
     if args.ip_adapter is not None:
@@ -292,7 +306,9 @@ if __name__ == "__main__":
         print(f"sampler {schedule.sampler}: {len(schedule.timesteps)} steps, timesteps {schedule.timesteps[0]} .. {schedule.timesteps[-1]}"
               + (f" (strength {strength}{', inpainting' if mask is not None else ''})" if init_image is not None else ""))
         model.compile(unconditional_context, context, latent, sampler=schedule, inpaint=mask is not None, concat=concat, control=bool(args.control_image),
-                      cfg=not args.no_cfg, ip_adapter=args.ip_adapter is not None)
+                      cfg=not args.no_cfg, ip_adapter=args.ip_adapter is not None, freeu=freeu is not None)
+        if freeu is not None:
+            model.set_freeu(*freeu)                              # four device scalars: they stay until the next set_freeu / start(freeu=)
     else:
         model.compile(unconditional_context, context, latent)
     times = []

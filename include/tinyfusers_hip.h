@@ -627,6 +627,23 @@ int tf_vit_embed_ln_16(int dtype, void* out, const void* patch_out, const void* 
  * does not cancel in the negative tail -- within 1 ulp of the 16-bit type of the correctly rounded value for every finite input.  y == x allowed. */
 int tf_gelu_erf_16(int dtype, void* y, const void* x, long long n, tfStream_t stream);
 
+/* ---- FreeU (csrc/freeu.hip; Si et al. 2023 as diffusers' apply_freeu / fourier_filter state it): in front of the channel concat of
+ * vision/unet.py:72 -- cat(x, saved.pop()) -- in the first two decoder stages, the skip goes through a Fourier filter and the first half of x's
+ * channels is scaled, inside the captured step. */
+typedef struct { void* dst; const void* src; int B; int H; int W; int C; int scale_index; } tfFreeuEntry;
+/* ONE launch for up to 8 NHWC (B,H,W,C) 16-bit tensors of `dtype`: dst_i = fourier_filter(src_i, threshold 1, scale s_i), s_i =
+ * scales[scale_index_i] -- fftn over (H, W), the four bins (u, v) in {0, -1}^2 times s, ifftn, real part -- in its closed form: per (image,
+ * channel) plane x, y = x + (s - 1) / (H W) sum_q S_q t_q with the twiddles t = (1, cos a, sin a, cos b, sin b, cos(a + b), sin(a + b)), a = 2 pi
+ * i / H, b = 2 pi j / W, and the seven fp32 sums S_q = sum_ij x t_q, combined in a fixed order (no atomics: deterministic).  table: a HOST array of
+ * n_entries tfFreeuEntry, copied into the kernel arguments by the call (a captured graph node owns its copy); C a positive multiple of 8, H >= 2,
+ * W >= 2, H + W <= 256, every pointer 16-byte aligned -- an error naming the entry otherwise.  scales: fp32 ON THE DEVICE, read when the kernel
+ * runs.  s_i == 1 leaves dst_i = src_i bit for bit (-0, infinities and NaN payloads included).  dst_i may be src_i */
+int tf_freeu_skip_16(int dtype, const void* table, int n_entries, const void* scales_f32, tfStream_t s);
+/* x (rows, C) 16-bit: dst[r, c] = round16(b * src[r, c]) for c < C / 2, b = scales[scale_index] read on the device: one fp32 multiply, one
+ * rounding.  The second half of the channels is copied when dst != src and not touched when dst == src.  b == 1 copies the bits.  C a positive
+ * multiple of 16; 16-byte aligned pointers */
+int tf_freeu_backbone_16(int dtype, void* dst, const void* src, long long rows, int C, const void* scales_f32, int scale_index, tfStream_t s);
+
 /* ---- ControlNet (csrc/control.hip; vision/controlnet.py): a second copy of the encoder half of vision/unet.py:51-76 whose 13 outputs are
  * added to what the UNet saves for its skip concats (vision/unet.py:72) and to its middle block's output, inside the captured step. */
 typedef struct { void* dst; const void* skip; const void* residual; long long n; } tfControlEntry;

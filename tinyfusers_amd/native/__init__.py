@@ -7,4 +7,4 @@ Same conventions as the reference: every C entry returns an int status and calle
 is located relative to ``__file__`` (fixes SURVEY D9) and loading fails loudly -- there is no CPU
 fallback anywhere in this package.
 """
-from .hip import hip, lib, check, LIB_PATH, declared_symbols, ControlEntry, LoraEntry  # noqa: F401
+from .hip import hip, lib, check, LIB_PATH, declared_symbols, ControlEntry, FreeuEntry, LoraEntry  # noqa: F401

@@ -102,6 +102,12 @@ class ControlEntry(ctypes.Structure):
     _fields_ = [("dst", ctypes.c_void_p), ("skip", ctypes.c_void_p), ("residual", ctypes.c_void_p), ("n", ctypes.c_longlong)]
 
 
+class FreeuEntry(ctypes.Structure):
+    """tfFreeuEntry of include/tinyfusers_hip.h: one (dst, src, B, H, W, C, scale index) row of tf_freeu_skip_16's host table."""
+    _fields_ = [("dst", ctypes.c_void_p), ("src", ctypes.c_void_p), ("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("C", ctypes.c_int),
+                ("scale_index", ctypes.c_int)]
+
+
 class LoraEntry(ctypes.Structure):
     """tfLoraEntry of include/tinyfusers_hip.h: one (up (N, rp), down_t (Kd, rp), rp, scale) row of tf_lora_merge_16's host table."""
     _fields_ = [("up", ctypes.c_void_p), ("down_t", ctypes.c_void_p), ("rp", ctypes.c_int), ("scale", ctypes.c_float)]

@@ -79,6 +79,17 @@ def ip_scales(ip_scale, n_attn, who="start"):
     return scales
 
 
+def freeu_scales(values, who="set_freeu"):
+    """(s1, s2, b1, b2) -> the 4 fp32 words of the FreeU scale buffer (one whole 4-word write): four finite floats, anything else raises."""
+    try:
+        sc = np.asarray(values, dtype=np.float32)
+    except (TypeError, ValueError):
+        sc = None
+    if sc is None or sc.shape != (4,) or not np.isfinite(sc).all():
+        raise ValueError(f"StableDiffusion.{who}: FreeU takes four finite floats (s1, s2, b1, b2), got {values!r}")
+    return np.ascontiguousarray(sc)
+
+
 def ip_embeds(x, batch, width):
     """start(ip_image_embeds=): a host float (B, E) array (or one row for every image) -> fp32 (B, E)."""
     if isinstance(x, DeviceArray):
@@ -91,10 +102,24 @@ def ip_embeds(x, batch, width):
     return np.ascontiguousarray(np.broadcast_to(e, (batch, width)))
 
 
-def check_compile(cin, has_control_net, config, latent, sampler, inpaint, concat, control, cfg=True, ip_adapter=False, has_ip_adapter=False):
-    """compile()'s refusals, before any device work: ``cin`` the UNet's in_channels, ``config`` the package's config module."""
+def check_compile(cin, has_control_net, config, latent, sampler, inpaint, concat, control, cfg=True, ip_adapter=False, has_ip_adapter=False,
+                  freeu=False, freeu_plan=()):
+    """compile()'s refusals, before any device work: ``cin`` the UNet's in_channels, ``config`` the package's config module, ``freeu_plan`` the
+    UNet's vision/unet.py::freeu_stages rows (stage, block, backbone channels, skip channels, latent size divisor)."""
     def refuse(exc, text):
         raise exc(f"StableDiffusion.compile: {text}")
+    if freeu:
+        if sampler is None:
+            refuse(ValueError, "freeu=True needs a sampler schedule (sampler=<Schedule>)")
+        if config.cfg_parallel:
+            refuse(UnsupportedSamplerConfig, "a FreeU model has no two-chain CFG form (TF_CFG_PARALLEL)")
+        if config.dtype == "fp8":
+            refuse(UnsupportedSamplerConfig, "freeu=True runs in the fp16 and the bf16 step, not under the fp8 policy (config.set_dtype('fp8'))")
+        for stage, block, ch, cskip, div in freeu_plan:
+            h, w = (int(latent.shape[2]) // div, int(latent.shape[3]) // div) if latent is not None else (2, 2)
+            if ch % 16 or cskip % 8 or h < 2 or w < 2:
+                refuse(ValueError, f"freeu=True: output block {block} (stage {stage + 1}) concatenates a backbone of {ch} channels and a skip of {cskip} at "
+                                   f"{h} x {w} -- the FreeU kernels need backbone channels in multiples of 16, skip channels in multiples of 8 and planes of at least 2 x 2")
     if ip_adapter:
         if not has_ip_adapter:
             refuse(ValueError, "ip_adapter=True needs an adapter: attach_ip_adapter(IPAdapter.load(unet, FILE)) first")

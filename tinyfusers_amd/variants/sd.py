@@ -18,6 +18,8 @@ LoRA adapters (storage/lora.py; ``load_lora``, ``set_adapters``, ``adapters``, `
 (tf_lora_merge_16, one launch per touched module, from the kept base weight); a compiled model re-captures its step.
 ``compile(..., cfg=False)`` is the guidance-free step of few-step samplers (samplers.LCM with an LCM-LoRA): ONE guidance group -- the UNet runs
 on B images against the context alone, between tf_latent_stack1_* and tf_sampler_step1_* (csrc/sampler.hip).
+``compile(..., freeu=True)`` is FreeU inside the captured step (csrc/freeu.hip; ``set_freeu``, ``start(freeu=)``): Fourier-filtered skips and a
+scaled backbone in front of the concats of the first two decoder stages, four device scalars that change without a re-capture.
 
 How the object is laid out.  Everything ``compile`` / ``start`` / ``set_context`` / ``set_adapters`` keep on the model is declared, with its
 "not compiled" value, in ``_reset_state``: ``__init__`` runs all of it, ``compile`` the per-compile part, so a re-compile with other flags drops the
@@ -33,7 +35,7 @@ import numpy as np
 from .. import config
 from ..native import hip
 from ..storage.tensor import Branch, DeviceArray, Stream, _sh, asarray, bfloat16, dtag, pool, use_stream
-from ..vision.unet import SD15, SD15_EDIT, SD15_INPAINT, StepParams, UNetModel
+from ..vision.unet import SD15, SD15_EDIT, SD15_INPAINT, StepParams, UNetModel, freeu_stages
 from . import inputs
 from .samplers import UnsupportedSamplerConfig, get_alphas_cumprod  # noqa: F401  (get_alphas_cumprod: variants/sd.py:61-65, re-exported)
 
@@ -93,6 +95,7 @@ class StableDiffusion:
         self._x0_init = self._mask = None        # inpaint=True: the clean latent and the (B,1,h,w) mask
         self._cond = self._edit = None           # concat=: the conditioning channels; [0] g_I of the three-branch update
         self._hint_emb = self._control_scales = None                 # control=True
+        self._freeu, self._freeu_scales = False, None                # freeu=True: the device fp32 words [s1, s2, b1, b2]
         self._ip, self._ip_model_compiled, self._ip_kv, self._ip_scales, self._ip_keep = False, None, None, None, None     # the adapter the step captured, ip_adapter=True: image-token K|V (G B, T, kv_n), the scales
         self._seed, self._image_offset, self._cursor = (0, 0), 0, 0  # what start() sets, step_sampler advances
         self._kv_all = self._kv_key = self._ckv_all = self._emb_cur = self._emb_key = self._keep_row = None     # hoisted K|V and time-embedding row
@@ -346,7 +349,7 @@ class StableDiffusion:
 
     # -- whole-step HIP graph ------------------------------------------------------------------------
     def compile(self, unconditional_context, context, latent, stream=None, warmup=2, timesteps=None, sampler=None, inpaint=False, concat=None, control=False,
-                cfg=True, ip_adapter=False):
+                cfg=True, ip_adapter=False, freeu=False):
         """Capture one denoising step for these (static) buffers into a HIP graph.  Afterwards
         ``step(timestep, a_t, a_prev, guidance)`` updates ``latent`` in place with one graph launch.
 
@@ -398,21 +401,33 @@ class StableDiffusion:
         computes.  Combines with cfg=False, inpaint=True, concat="inpaint", control=True, LoRA, bf16; not with concat="edit", TF_CFG_PARALLEL or
         the fp8 policy.  (The warm-up steps run every dual instance once before the capture: its first launch sets a function attribute.)
 
+        ``freeu=True`` (with a sampler only): FreeU (Si et al. 2023, as diffusers' ``enable_freeu`` states it) inside the captured step -- in front
+        of the concats of the first two decoder stages one launch (tf_freeu_skip_16) puts the 2 (num_res_blocks + 1) skip tensors through the
+        Fourier filter, behind the encoder and behind tf_control_add_16 where there is one, and one launch per block (tf_freeu_backbone_16) scales
+        the first half of the backbone's channels.  The model owns the device fp32 words [s1, s2, b1, b2], all ones; ``set_freeu`` and
+        ``start(freeu=)`` change them without a re-capture.  At all ones both kernels copy their input's bits, yet the step is NOT bit for bit
+        the freeu=False step: the tensors FreeU makes carry no GroupNorm statistics, so those concats' GroupNorms compute their own (two passes
+        over the stored 16-bit values) where the plain step merges the fp32 partials its producing convolutions emitted -- the same numbers up
+        to fp32 summation order and the 16-bit rounding of the producer's output.  Combines with cfg=False, inpaint=True, both concat= modes,
+        control=True, ip_adapter=True, LoRA, bf16; not with TF_CFG_PARALLEL or the fp8 policy.
+
         The arguments are remembered: ``set_adapters`` (LoRA) on a compiled model swaps weight handles and calls ``compile`` again with the same ones."""
         inputs.check_compile(self.model.diffusion_model.cfg.in_channels, self.control_model is not None, config, latent, sampler, inpaint, concat, control, cfg,
-                             ip_adapter=ip_adapter, has_ip_adapter=self._ip_model is not None)
+                             ip_adapter=ip_adapter, has_ip_adapter=self._ip_model is not None, freeu=freeu,
+                             freeu_plan=freeu_stages(self.model.diffusion_model.cfg) if freeu else ())
         if ip_adapter and warmup < 1:
             raise ValueError("StableDiffusion.compile: ip_adapter=True needs warmup >= 1 (the first launch of an attention instance cannot be captured)")
         if sampler is not None:
             timesteps = sampler.timesteps
         self._reset_state()
         self._compile_args = dict(unconditional_context=unconditional_context, context=context, latent=latent, warmup=warmup, timesteps=timesteps,
-                                  sampler=sampler, inpaint=inpaint, concat=concat, control=control, cfg=cfg, ip_adapter=ip_adapter)
+                                  sampler=sampler, inpaint=inpaint, concat=concat, control=control, cfg=cfg, ip_adapter=ip_adapter, freeu=freeu)
         self._stream = stream or Stream()
         self._latent, self._unc, self._ctx = latent, unconditional_context, context
         self._sched, self._inpaint, self._concat, self._control = sampler, bool(inpaint), concat, bool(control)
         self._groups = 3 if concat == "edit" else 2 if cfg else 1
         self._ip = bool(ip_adapter)
+        self._freeu = bool(freeu)
         self._ip_model_compiled = self._ip_model if self._ip else None
         if sampler is not None:
             with use_stream(self._stream):
@@ -440,6 +455,8 @@ class StableDiffusion:
         if self._control:
             self._hint_emb = DeviceArray.zeros((self._groups * b, self.control_model.cfg.model_channels, h, w), _step_dtype(), "nhwc")
             self._control_scales = DeviceArray.from_numpy(np.ones((16,), np.float32), np.float32, "row")     # one per residual; 16: whole 4-word writes
+        if self._freeu:
+            self._freeu_scales = DeviceArray.from_numpy(np.ones((4,), np.float32), np.float32, "row")      # [s1, s2, b1, b2]: one 4-word write
         if self._ip:
             ad = self._ip_model_compiled
             self._ip_kv = DeviceArray.zeros((self._groups * b, ad.num_tokens, ad.kv_layout()[1]), _step_dtype(), "row")
@@ -511,7 +528,7 @@ class StableDiffusion:
         unet, cn, row, ctx = self.model.diffusion_model, self.control_model, self._emb_cur, self._ctx2
         ip = (self._ip_model_compiled, self._ip_kv, self._ip_scales) if self._ip else None
         if not self._control:
-            return unet(x2, sp, ctx, shared=None if row is None else (None, row, self._kv_all), ip=ip)     # (step() has put this timestep's row into _emb_cur)
+            return unet(x2, sp, ctx, shared=None if row is None else (None, row, self._kv_all), ip=ip, freeu=self._freeu_scales)     # (step() has put this timestep's row into _emb_cur)
         # the UNet's encoder, then the ControlNet on the same stacked latent, then the seam (UNetModel.__call__ calls `residuals` behind its
         # middle block); each model reads its own view of the hoisted row [UNet's | ControlNet's]
         shared_u = shared_c = None
@@ -520,7 +537,7 @@ class StableDiffusion:
             shared_u = (None, row.view((1, nu), "row"), self._kv_all)
             shared_c = (None, row.view((1, row.shape[1] - nu), "row", nu), self._ckv_all)
         residuals = lambda: cn(x2, self._hint_emb, sp, ctx, shared=shared_c)
-        return unet(x2, sp, ctx, shared=shared_u, control=(residuals, self._control_scales), ip=ip)
+        return unet(x2, sp, ctx, shared=shared_u, control=(residuals, self._control_scales), ip=ip, freeu=self._freeu_scales)
 
     def _unet_two_chains(self, x2, sp):
         """config.cfg_parallel: the unconditional and the conditional half of the CFG pair (variants/sd.py:31-32) as two independent UNet chains: one
@@ -610,7 +627,7 @@ class StableDiffusion:
 
     def start(self, seed=None, noise=None, image_offset=0, init_image=None, init_latent=None, mask=None, cond_image=None, cond_mask=None,
               cond_latent=None, image_guidance=None, control_image=None, control_hint=None, control_scale=None, ip_image_embeds=None, ip_image=None,
-              ip_scale=None):
+              ip_scale=None, freeu=None):
         """A new image batch for the compiled sampler: sets the latent in place and rewinds the schedule.  ``seed``: the initial latent is
         drawn on the device (tag 0; image b is global image image_offset + b), and the ancestral noise of every step comes from the same seed
         (tag 1); ``noise``: a host (B,C,H,W) array for the initial latent instead (the ancestral noise then uses ``seed``, default 0).
@@ -639,8 +656,12 @@ class StableDiffusion:
         published convention); the image tokens' K|V is projected here, outside the graph.  ``ip_scale``: one float or one per cross-attention (adapter
         order: down, up, mid); 1 when not given.  ``ip_image`` (uint8 (B | 1, S, S, 3), host or device, S the tower's image size: 224 for ViT-H; resized
         and cropped by the caller) instead of ``ip_image_embeds``: the attached CLIP vision tower (``attach_clip_vision``) computes the embeddings on
-        the device, ordered into the sampler stream; [0 | embeddings] for the CFG pair is built there too.  Without a tower it is refused."""
+        the device, ordered into the sampler stream; [0 | embeddings] for the CFG pair is built there too.  Without a tower it is refused.
+
+        A FreeU model (compile(..., freeu=True)): ``freeu=(s1, s2, b1, b2)`` writes the four scalars as ``set_freeu`` does; without it they keep
+        their values."""
         self._require_sampler("start")
+        fu = self._check_freeu(freeu, "start")
         ipa = self._check_ip(ip_image_embeds, ip_image, ip_scale)
         ctrl = self._check_control(control_image, control_hint, control_scale)
         cond = self._check_cond(cond_image, cond_mask, cond_latent, image_guidance)
@@ -652,7 +673,29 @@ class StableDiffusion:
             self._write_control(*ctrl)
         if ipa is not None:
             self._write_ip(*ipa)
+        if fu is not None:
+            self._write_freeu(fu)
         return self._latent
+
+    def _check_freeu(self, values, who):
+        """(s1, s2, b1, b2) checked against the compiled model before anything changes: None when not given, else the 4 fp32 words."""
+        if values is None:
+            return None
+        if not self._freeu:
+            raise ValueError(f"StableDiffusion.{who}: " + ("freeu= needs" if who == "start" else "needs") + " a model compiled with freeu=True")
+        return inputs.freeu_scales(values, who)
+
+    def _write_freeu(self, scales):
+        with use_stream(self._stream, ordered=False):                    # stream-ordered: the values travel as kernel arguments
+            hip.tf_set_step_params(self._freeu_scales.ptr, *(float(v) for v in scales), _sh())
+
+    def set_freeu(self, s1=1.0, s2=1.0, b1=1.0, b2=1.0):
+        """FreeU's four scalars from the next step on -- s1, s2: the Fourier filter's scale on the skips of decoder stage 1 and 2; b1, b2: the
+        factor on the first half of the backbone's channels there -- four finite floats, checked before anything is written.  The captured step
+        reads them from the device, so nothing is captured again.  All ones: the un-FreeU'd model's result up to the GroupNorm statistics path
+        (``compile``).  The values usually quoted for SD-1.5 are s1 = 0.9, s2 = 0.2, b1 = 1.5, b2 = 1.6 (the authors' suggestion, not tuned here)."""
+        self._require_sampler("set_freeu")
+        self._write_freeu(self._check_freeu((s1, s2, b1, b2), "set_freeu"))
 
     def _check_ip(self, ip_image_embeds, ip_image, ip_scale):
         """start()'s adapter arguments, checked against the compiled model before anything changes: None for a model without ip_adapter=True,

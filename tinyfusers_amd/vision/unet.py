@@ -14,6 +14,8 @@ Step-level batching that the reference does not do (results unchanged):
 
 The encoder half (block plan, batched projections, the walk over input_blocks and middle_block) lives in ``encoder_plan`` / ``StepModel``: a
 ControlNet (vision/controlnet.py) is a second copy of it, and ``UNetModel.__call__(control=...)`` takes its residuals in (``control_add``).
+``UNetModel.__call__(freeu=...)`` is FreeU in front of the concats of the first two decoder stages (``freeu_stages``, ``freeu_skips``,
+``freeu_backbone``).
 """
 import ctypes
 from dataclasses import dataclass, replace
@@ -24,7 +26,7 @@ import numpy as np
 from ..attention.attention import SpatialTransformer, _concat_rows
 from ..ff.group_norm import GroupNorm
 from ..ff.linear import Linear, gemv_f16, linear_f16
-from ..native import ControlEntry, hip
+from ..native import ControlEntry, FreeuEntry, hip
 from .. import config
 from ..storage.tensor import Branch, DeviceArray, Tensor, _sh, asarray, bfloat16, dtag, is_bfloat16
 from .conv2d import Conv2d
@@ -235,24 +237,27 @@ class StepModel:
             return bb(x)
         return run
 
-    def _encode(self, run, x, br=None, concat_stats=True, residual=None):
+    def _encode(self, run, x, br=None, concat_stats=True, residual=None, replaced=0):
         """input_blocks and middle_block over x: (the middle block's output, what every input block saves for the skip concats).  concat_stats:
         the saved tensors and the output enter the output path's concats as they are -- their producers emit the statistics those concats'
-        GroupNorms merge (config.concat_stats).  residual: added to the first module's (conv_in's) output."""
+        GroupNorms merge (config.concat_stats).  residual: added to the first module's (conv_in's) output.  replaced: the last ``replaced`` saved
+        tensors and the output are replaced before their concats read them (FreeU): their producers are not asked for concat statistics."""
         saved_inputs = []
         joined = br is None
         seq = [bb for b in self.input_blocks for bb in b] + list(self.middle_block)
-        ends = set()                                # indices after which the tensor is also saved for a skip concat
+        ends = []                                   # indices after which the tensor is also saved for a skip concat
         i = 0
         for b in self.input_blocks:
             i += len(b)
-            ends.add(i - 1)
+            ends.append(i - 1)
+        kept = set(ends[:len(ends) - replaced]) if replaced else set(ends)
+        ends = set(ends)
         for i, bb in enumerate(seq):
             nxt = seq[i + 1] if i + 1 < len(seq) else None     # the middle block's output enters a concat
             if not joined and isinstance(bb, SpatialTransformer):
                 br.join(); joined = True            # first consumer of kv_all
             # tensors saved for (or entering) the output path's concat carry 32-group statistics when the concat is an equal split
-            want = concat_stats and config.concat_stats and (i in ends or nxt is None) and x.size <= config.concat_stats_max_elems
+            want = concat_stats and config.concat_stats and (i in kept or (nxt is None and not replaced)) and x.size <= config.concat_stats_max_elems
             x = run(x, bb, nxt, force_gn=32 if want else 0, residual=residual if i == 0 else None)
             if i in ends:
                 saved_inputs.append(x)
@@ -279,6 +284,55 @@ def control_add(skips, residuals, scales):
         outs.append(o)
     hip.tf_control_add_16(dtag(skips[0].dtype), ctypes.cast(table, ctypes.c_void_p), len(skips), scales.ptr, _sh())
     return outs
+
+
+def freeu_stages(cfg):
+    """FreeU's stage -> block map (diffusers' up_blocks[0] and up_blocks[1]): with n = num_res_blocks + 1, stage k is output_blocks[k n : (k + 1) n].
+    -> [(stage, output block, backbone channels, skip channels, latent size divisor)] for the 2n blocks, in block order.  (The authors' LDM code
+    keys on the backbone's channel count, 1280 / 640, which names other blocks; this follows diffusers.)"""
+    mc, nlev, n = cfg.model_channels, len(cfg.channel_mult), cfg.num_res_blocks + 1
+    if nlev < 2:
+        raise ValueError(f"freeu_stages: FreeU needs two decoder stages, {cfg} has {nlev}")
+    chans = [mc]                                    # what encoder_plan's input blocks save
+    for lev, mult in enumerate(cfg.channel_mult):
+        chans += [mc * mult] * cfg.num_res_blocks + ([mc * mult] if lev != nlev - 1 else [])
+    ch, plan = chans[-1], []
+    for k, lev in enumerate((nlev - 1, nlev - 2)):
+        for i in range(n):
+            plan.append((k, k * n + i, ch, chans.pop(), 2 ** lev))
+            ch = mc * cfg.channel_mult[lev]
+    return plan
+
+
+def freeu_skips(skips, stages, scales):
+    """new_i = fourier_filter(skip_i, threshold 1, scale s[stage_i]) for every tensor of ``skips`` in ONE launch (tf_freeu_skip_16; s: words 0 and
+    1 of the device fp32 array ``scales`` = [s1, s2, b1, b2]).  The new tensors carry no GroupNorm statistics (.gn) and no normalised twin
+    (.normed) -- control_add's rule: those of the skips describe the tensors before the filter."""
+    if len(skips) != len(stages) or not 1 <= len(skips) <= 8:
+        raise ValueError(f"freeu_skips: {len(stages)} stages for {len(skips)} skip tensors (1 to 8)")
+    if scales.dtype != np.float32 or scales.size < 4:
+        raise ValueError(f"freeu_skips: scales must hold the 4 fp32 values [s1, s2, b1, b2], got {scales}")
+    table, outs = (FreeuEntry * len(skips))(), []
+    for e, k, st in zip(table, skips, stages):
+        if k.layout != "nhwc" or k.dtype.itemsize != 2 or dtag(k.dtype) != dtag(skips[0].dtype) or k.shape[1] % 8 or k.shape[2] < 2 or k.shape[3] < 2:
+            raise ValueError(f"freeu_skips: the skip tensor {k} is not 16-bit NHWC with C a multiple of 8, H >= 2 and W >= 2")
+        o = DeviceArray.empty(k.shape, k.dtype, k.layout)
+        e.dst, e.src, e.scale_index = o.ptr, k.ptr, st
+        e.B, e.C, e.H, e.W = k.shape
+        o._base = k                                       # (referenced while the launch is queued)
+        outs.append(o)
+    hip.tf_freeu_skip_16(dtag(skips[0].dtype), ctypes.cast(table, ctypes.c_void_p), len(skips), scales.ptr, _sh())
+    return outs
+
+
+def freeu_backbone(x, stage, scales):
+    """x[:, :C/2] *= b[stage] (word 2 + stage of ``scales``), in place: one launch over half the tensor (tf_freeu_backbone_16).  -> a new handle
+    on the same memory without .gn / .normed, which describe the tensor before the scaling."""
+    n, c, h, w = x.shape
+    if x.layout != "nhwc" or x.dtype.itemsize != 2 or c % 16:
+        raise ValueError(f"freeu_backbone: the backbone tensor {x} is not 16-bit NHWC with C a multiple of 16")
+    hip.tf_freeu_backbone_16(dtag(x.dtype), x.ptr, x.ptr, n * h * w, c, scales.ptr, 2 + stage, _sh())
+    return x.view(x.shape, x.layout)
 
 
 class UNetModel(StepModel):
@@ -313,25 +367,35 @@ class UNetModel(StepModel):
             raise ValueError("UNetModel.ip_slots: the adapter was built for another UNet")
         return {id(st): (offs[k], k) for k, (_, _, st) in enumerate(paths)}
 
-    def __call__(self, x, timesteps=None, context=None, shared=None, control=None, ip=None):
+    def __call__(self, x, timesteps=None, context=None, shared=None, control=None, ip=None, freeu=None):
         """control = (residuals, scales): a ControlNet's len(input_blocks) + 1 residual tensors (or a callable that returns them, called behind
         the middle block) and the device fp32 array of their strengths.  Behind the middle block one launch (control_add) makes new skip tensors
         and a new middle output, skip_i + s_i residual_i, which carry no statistics: the output path's concat GroupNorms then compute theirs
         (ff/group_norm.py::_gn, the explicit path), and no producer is asked for concat statistics.  None: the step as it always was.
         ip = (adapter, kv_ip_all, scales): an IP-Adapter (storage/ip_adapter.py), its context_kv of the image tokens (b, T, kv_n) and a device fp32
-        array with one strength per cross-attention in adapter order: every cross-attention becomes the dual launch.  None: the plain launches."""
+        array with one strength per cross-attention in adapter order: every cross-attention becomes the dual launch.  None: the plain launches.
+        freeu = a device fp32 array [s1, s2, b1, b2]: FreeU on the 2n blocks of the first two decoder stages (``freeu_stages``).  Behind the
+        encoder -- and behind control_add, so the filter reads the skip as the concat would have read it -- one launch (``freeu_skips``) replaces
+        their 2n skip tensors, and in front of each of those blocks one launch (``freeu_backbone``) scales the first half of x's channels.  What
+        FreeU makes carries no statistics: those 2n concat GroupNorms compute theirs, the producers of what enters them are not asked for concat
+        statistics, and the later blocks keep their apply-only concats.  None: the step as it always was, launch for launch."""
         emb, emb_all, kv_all, br = self._shared(timesteps, context, shared)
+        fu = freeu_stages(self.cfg) if freeu is not None else []
         if ip is not None:
             adapter, kv_ip, scales = ip
             if kv_ip.shape[0] != x.shape[0] or kv_ip.shape[2] != adapter.kv_layout()[1] or scales.dtype != np.float32 or scales.size < len(adapter.paths):
                 raise ValueError(f"UNetModel: ip K|V {kv_ip.shape} / scales {scales.shape} do not fit a batch of {x.shape[0]} and {len(adapter.paths)} cross-attentions")
             ip = (kv_ip, self.ip_slots(adapter), adapter.kv_layout()[1], scales)
         run = self._runner(emb, emb_all, kv_all, context, ip)
-        x, saved_inputs = self._encode(run, x, br, concat_stats=control is None)
+        x, saved_inputs = self._encode(run, x, br, concat_stats=control is None, replaced=len(fu))
         if control is not None:
             residuals, scales = control
             *saved_inputs, x = control_add(saved_inputs + [x], residuals() if callable(residuals) else residuals, scales)
+        if fu:
+            saved_inputs[-len(fu):] = freeu_skips(saved_inputs[-len(fu):], [st for st, *_ in reversed(fu)], freeu)     # (popped from the end: block order reversed)
         for bi, b in enumerate(self.output_blocks):
+            if bi < len(fu):
+                x = freeu_backbone(x, fu[bi][0], freeu)
             x = (x, saved_inputs.pop())            # channel concat (unet.py:72), consumed un-materialised
             for j, bb in enumerate(b):
                 last = bi == len(self.output_blocks) - 1 and j == len(b) - 1
@@ -340,7 +404,7 @@ class UNetModel(StepModel):
                 # the output enters the next concat: emit its statistics in sub-groups as wide as the 32 groups of the saved partner
                 # (32 sub-groups for an equal split, 64 for the 2:1 splits), so that the concat's GroupNorm is apply-only
                 fg = 0
-                if control is None and config.concat_stats and nxt is None and saved_inputs and saved_inputs[-1].size <= config.concat_stats_max_elems:
+                if control is None and bi + 1 >= len(fu) and config.concat_stats and nxt is None and saved_inputs and saved_inputs[-1].size <= config.concat_stats_max_elems:
                     c2 = saved_inputs[-1].shape[1]
                     sub = c2 // 32
                     if c2 % 32 == 0 and sub >= 4 and cout % sub == 0 and ((cout + c2) // 32) % sub == 0 and cout // sub <= 256:

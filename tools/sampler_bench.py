@@ -3,7 +3,7 @@
 tf_cfg_sampler_step_f32) against the DDIM step (tf_cfg_ddim_step_f32), 100 graph replays each, alternated over several rounds; and the
 config-3 end-to-end img/s (CLIP x2 -> steps -> VAE decode, batch 1) at 20 DPM++2M steps against 50 DDIM steps.
 
-    python tools/sampler_bench.py [--replays 100] [--rounds 5] [--images 3] [--dpm-steps 20] [--inpaint] [--concat inpaint|edit] [--control] [--lora] [--lcm] [--ip-adapter]
+    python tools/sampler_bench.py [--replays 100] [--rounds 5] [--images 3] [--dpm-steps 20] [--inpaint] [--concat inpaint|edit] [--control] [--lora] [--lcm] [--ip-adapter] [--freeu]
 --inpaint adds the masked DPM++2M step (tf_cfg_sampler_step_masked_f32, a model compiled with inpaint=True on the same shape, half the
 latent repainted) to the alternation, and the VAE encoder's time for a 512^2 image (StableDiffusion.encode_image).
 --concat adds the DPM++2M step of a concat-conditioned UNet (SD15_INPAINT: 9 input channels, two CFG groups; SD15_EDIT: 8 input channels, three
@@ -26,6 +26,10 @@ over the launches' device time) next to add_16_gb_s, lora_recapture_ms (set_adap
 cfg=False (dpmpp2m_nocfg_step_ms) next to the cfg=True one of the same rounds, the LCM step in both modes (lcm_step_ms, lcm_nocfg_step_ms), the
 ratios with the rounds' own spread next to them, and the end-to-end img/s of 4 LCM steps with cfg=False (e2e_lcm4_nocfg: one CLIP pass, the
 sampler, the VAE decode) against the DPM++2M run.
+--freeu adds the FreeU step (compile(..., freeu=True): the same UNet weights) to the alternation at the values usually quoted for SD-1.5 (0.9, 0.2,
+1.5, 1.6) and at all ones, next to the plain step of the same rounds with the rounds' spread; the library entries one eager step of each calls
+(step_entries, and which entries differ); and microseconds per launch of tf_freeu_skip_16 on the step's six skip shapes and of
+tf_freeu_backbone_16 on its two backbone shapes; written to profiles/sampler_bench_freeu.json as well.
 Prints one JSON line."""
 import argparse
 import contextlib
@@ -73,6 +77,62 @@ def control_add_bench(T, hip, model, timed, args):
     c, d = float(np.median(ms["ctl"])), float(np.median(ms["add"]))
     return {"control_add_bytes": nbytes, "control_add_us": round(1e3 * c, 2), "control_add_gb_s": round(nbytes / c / 1e6, 1),
             "add_16_us": round(1e3 * d, 2), "add_16_gb_s": round(nbytes / d / 1e6, 1)}
+
+
+def step_entries(T, model):
+    """{entry: calls} of one eager step of a compiled model: every library entry it calls that is not a copy, an allocation, a host-side query or
+    stream / event / graph plumbing.  (An entry is one kernel launch except where it says otherwise: a split-K GEMM adds its reduce, a GroupNorm that computes its
+    own statistics is a statistics and an apply kernel.)"""
+    from tinyfusers_amd.native import declared_symbols, hip as H
+    counts, saved = {}, {}
+    for name in declared_symbols():
+        fn = getattr(H, name)
+        saved[name] = fn
+
+        def rec(*a, _fn=fn, _name=name):
+            counts[_name] = counts.get(_name, 0) + 1
+            return _fn(*a)
+        setattr(H, name, rec)
+    try:
+        with T.use_stream(model._stream):
+            model._eager_step(model._params)
+        model.synchronize()
+    finally:
+        for name, fn in saved.items():
+            setattr(H, name, fn)
+    plumbing = ("tf_mem", "tf_malloc", "tf_stream", "tf_event", "tf_graph", "tf_last_error", "tf_pool", "tf_prof", "tf_gemm_tune", "tf_gemm_autotune")
+    queries = ("_workspace", "_partial_bytes", "_admits")                 # host-side questions: no launch
+    return {k: v for k, v in counts.items() if k != "tf_free" and not k.startswith(plumbing) and not k.endswith(queries)}
+
+
+def freeu_kernel_bench(T, hip, model, timed, args):
+    """tf_freeu_skip_16 on the six SD-1.5 skip shapes of a CFG step (one launch, 4.3 MB in and out) and tf_freeu_backbone_16 in place on the two
+    backbone shapes: microseconds per launch, medians of --rounds rounds of --replays launches on the model's stream."""
+    import ctypes
+    from tinyfusers_amd.native import FreeuEntry
+    shapes = [(2, 8, 8, 1280)] * 3 + [(2, 16, 16, 1280)] * 2 + [(2, 16, 16, 640)]
+    with T.use_stream(model._stream):
+        src = [T.DeviceArray.from_numpy(np.random.default_rng(i).standard_normal((b, c, h, w)).astype(np.float32), np.float16, "nhwc") for i, (b, h, w, c) in enumerate(shapes)]
+        dst = [T.DeviceArray.empty(a.shape, a.dtype, "nhwc") for a in src]
+        scales = T.DeviceArray.from_numpy(np.asarray([0.9, 0.2, 1.5, 1.6], np.float32), np.float32, "row")
+    table = (FreeuEntry * 6)()
+    for i, (e, d, a, (b, h, w, c)) in enumerate(zip(table, dst, src, shapes)):
+        e.dst, e.src, e.B, e.H, e.W, e.C, e.scale_index = d.ptr, a.ptr, b, h, w, c, i // 3
+
+    def skip(n):
+        for _ in range(n):
+            hip.tf_freeu_skip_16(0, ctypes.cast(table, ctypes.c_void_p), 6, scales.ptr, model._stream.handle)
+
+    def backbone(a, idx):
+        def run(n):
+            for _ in range(n):
+                hip.tf_freeu_backbone_16(0, a.ptr, a.ptr, a.shape[0] * a.shape[2] * a.shape[3], a.shape[1], scales.ptr, idx, model._stream.handle)
+        return run
+    out = {}
+    for key, fn in (("freeu_skip_6_us", skip), ("freeu_backbone_8x8_us", backbone(dst[0], 2)), ("freeu_backbone_16x16_us", backbone(dst[3], 3))):
+        fn(20)
+        out[key] = round(1e3 * float(np.median([timed(model, fn, args.replays) for _ in range(args.rounds)])), 3)
+    return out
 
 
 def synthetic_lora(targets, rank, seed):
@@ -290,6 +350,7 @@ def main():
     ap.add_argument("--control", action="store_true", help="also time the ControlNet-conditioned step against the plain one, start(control_image=), and k_control_add")
     ap.add_argument("--lora", action="store_true", help="also time the LoRA merge (tf_lora_merge_16), the re-capture and the adapted step, for rank 16 and rank 128")
     ap.add_argument("--ip-adapter", action="store_true", help="also time the IP-Adapter step (fused dual attention) against the plain one and against a composed two-launch form")
+    ap.add_argument("--freeu", action="store_true", help="also time the FreeU step (compile(..., freeu=True)) at the quoted values and at all ones against the plain one, and count the entries of both steps")
     ap.add_argument("--lcm", action="store_true", help="also time the guidance-free step (cfg=False) against the CFG step for DPM++2M and LCM, and LCM-4 cfg=False end to end")
     args = ap.parse_args()
 
@@ -396,6 +457,14 @@ def main():
             m.compile(unc if cfg_on else None, ctx, lat_f, sampler=sched, cfg=cfg_on)
             m.start(seed=1234)
             few[key] = (m, lat_f, sched, 7.5 if cfg_on else None)
+    if args.freeu:
+        for key, vals in (("dpmpp2m_freeu", (0.9, 0.2, 1.5, 1.6)), ("dpmpp2m_freeu_ones", (1.0, 1.0, 1.0, 1.0))):
+            m = StableDiffusion()
+            update_state(m.model.diffusion_model, state, "")
+            lat_f = m.latent_from_numpy(noise)
+            m.compile(unc, ctx, lat_f, sampler=dpm_sched, freeu=True)
+            m.start(seed=1234, freeu=vals)
+            few[key] = (m, lat_f, dpm_sched, 7.5)
     lat0 = T.DeviceArray.from_numpy(noise, np.float32, "row")
     ts, al, ap_ = ddim_sched.timesteps, ddim_sched.alphas, ddim_sched.alphas_prev
 
@@ -571,6 +640,20 @@ def main():
                       "lcm_over_dpmpp2m": round(med["lcm"] / med["dpmpp2m"], 4),
                       "round_spread": {k: round(spread(k), 4) for k in ("dpmpp2m", "dpmpp2m_nocfg", "lcm", "lcm_nocfg")}})
 
+    if args.freeu:
+        spread_ms = lambda k: round(max(step_ms[k]) - min(step_ms[k]), 4)
+        for k in ("dpmpp2m_freeu", "dpmpp2m_freeu_ones"):
+            assert np.isfinite(few[k][1].numpy()).all(), k
+        entries = {k: step_entries(T, m) for k, m in (("dpmpp2m", dpm_m), ("dpmpp2m_freeu", few["dpmpp2m_freeu"][0]))}
+        extra.update({"dpmpp2m_freeu_step_ms": round(med["dpmpp2m_freeu"], 4), "dpmpp2m_freeu_ones_step_ms": round(med["dpmpp2m_freeu_ones"], 4),
+                      "freeu_over_plain": round(med["dpmpp2m_freeu"] / med["dpmpp2m"], 4), "freeu_ones_over_plain": round(med["dpmpp2m_freeu_ones"] / med["dpmpp2m"], 4),
+                      "freeu_round_spread_ms": {k: spread_ms(k) for k in ("dpmpp2m", "dpmpp2m_freeu", "dpmpp2m_freeu_ones")},
+                      "step_entries": {k: sum(v.values()) for k, v in entries.items()},
+                      "step_entries_freeu_minus_plain": {k: entries["dpmpp2m_freeu"].get(k, 0) - entries["dpmpp2m"].get(k, 0)
+                                                         for k in sorted(set(entries["dpmpp2m"]) | set(entries["dpmpp2m_freeu"]))
+                                                         if entries["dpmpp2m_freeu"].get(k, 0) != entries["dpmpp2m"].get(k, 0)},
+                      **freeu_kernel_bench(T, hip, few["dpmpp2m_freeu"][0], timed, args)})
+
     def e2e(model, steps, sample, uncond=True):
         recs = []
         for n in range(args.images + 1):
@@ -615,6 +698,9 @@ def main():
     print(json.dumps(out))
     if args.ip_adapter:
         with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sampler_bench_ip_adapter.json"), "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+    if args.freeu:
+        with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sampler_bench_freeu.json"), "w") as f:
             f.write(json.dumps(out, indent=1) + "\n")
     del arena
 
