@@ -16,6 +16,7 @@ BASELINE config 3: full 50-step sampler, batch 1, end-to-end img/s.
     python -m example.sd1 --steps 20 --sampler dpmpp2m --lora style.safetensors:0.8 --lora lcm.safetensors:1:0   # LoRA adapters, FILE[:w[:w_te]], merged on the device
     python -m example.sd1 --steps 4 --sampler lcm --no-cfg --lora lcm.safetensors:1:0   # few-step sampling: the LCM sampler on the guidance-free single-branch step
     python -m example.sd1 --steps 20 --sampler dpmpp2m --freeu 0.9,0.2,1.5,1.6   # FreeU: s1,s2,b1,b2 (the values usually quoted for SD-1.5)
+    python -m example.sd1 --steps 20 --sampler dpmpp2m --pag 3.0 --pag-layers mid   # perturbed-attention guidance next to CFG (with --no-cfg: instead of it)
     python -m example.sd1 --steps 20 --sampler dpmpp2m --ip-adapter ip-adapter_sd15.safetensors --ip-embeds e.npy [--ip-scale 0.6]   # IP-Adapter: an image prompt, as CLIP image embeddings (1, 1024)
     python -m example.sd1 --steps 20 --sampler dpmpp2m --ip-adapter ip-adapter_sd15.safetensors --ip-image x.npy [--clip-vision image_encoder.safetensors]   # ... or as the picture itself, uint8 (224, 224, 3): the CLIP ViT-H tower runs on the device
 With --ckpt the configuration is read off the checkpoint's conv_in (4, 9 or 8 input channels); --concat picks it on synthetic weights.
@@ -72,7 +73,16 @@ if __name__ == "__main__":
     ap.add_argument("--freeu", default=None, metavar="S1,S2,B1,B2",
                     help="FreeU inside the captured step (needs --sampler): the Fourier filter's scale on the skips and the backbone factor of decoder stages 1 and 2; "
                          "0.9,0.2,1.5,1.6 are the values usually quoted for SD-1.5")
+    ap.add_argument("--pag", type=float, default=None, metavar="SCALE",
+                    help="perturbed-attention guidance inside the captured step (needs --sampler): one more guidance group whose self-attention is the identity "
+                         "in the selected transformers; 3.0 is the scale usually quoted")
+    ap.add_argument("--pag-layers", default="mid", help="with --pag: the transformers to perturb, comma-separated: down, mid, up, all, LDM paths (input_blocks.4, "
+                                                        "middle_block, output_blocks.7) or indices in execution order (default: mid)")
+    ap.add_argument("--pag-adaptive", type=float, default=0.0, metavar="A", help="with --pag: the adaptive scale a of s_t = max(0, s - a (1000 - t)) (default 0)")
     args = ap.parse_args()
+    if args.pag is not None and not args.sampler:
+        ap.error("--pag needs --sampler")
+    pag_layers = [int(v) if v.lstrip("-").isdigit() else v for v in args.pag_layers.split(",") if v]
     freeu = None
     if args.freeu is not None:
         if not args.sampler:
@@ -306,7 +316,9 @@ if __name__ == "__main__":
         print(f"sampler {schedule.sampler}: {len(schedule.timesteps)} steps, timesteps {schedule.timesteps[0]} .. {schedule.timesteps[-1]}"
               + (f" (strength {strength}{', inpainting' if mask is not None else ''})" if init_image is not None else ""))
         model.compile(unconditional_context, context, latent, sampler=schedule, inpaint=mask is not None, concat=concat, control=bool(args.control_image),
-                      cfg=not args.no_cfg, ip_adapter=args.ip_adapter is not None, freeu=freeu is not None)
+                      cfg=not args.no_cfg, ip_adapter=args.ip_adapter is not None, freeu=freeu is not None, pag=args.pag is not None)
+        if args.pag is not None:
+            model.set_pag(args.pag, pag_layers, args.pag_adaptive)   # 16 device words and two host scalars: they stay until the next set_pag / start(pag=)
         if freeu is not None:
             model.set_freeu(*freeu)                              # four device scalars: they stay until the next set_freeu / start(freeu=)
     else:

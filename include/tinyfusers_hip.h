@@ -360,6 +360,18 @@ int tf_sdpa_dual_16(int dtype, void* o, const void* q, const void* k, const void
                     long long v_sb, long long v_sh, long long v_st, long long k2_sb, long long k2_sh, long long k2_st, long long v2_sb, long long v2_sh,
                     long long v2_st, long long o_sb, long long o_sh, long long o_st, tfStream_t s);
 int tf_sdpa_dual_instance(int dtype, int B, int NH, int Tq, int Tk, int Tk2, int HS, long long k_st, long long v_st, long long k2_st, long long v2_st);
+/* ---- perturbed-attention guidance in ONE launch: the self-attention of attention/attention.py:35-41 in which the batch entries [pag_b0, pag_b1) take
+ * the identity in place of the softmax, o[b, h, t, :] = v[b, h, t, :] (the bits, through the launch's own v and o strides), while *pag_flag_dev -- one
+ * fp32 ON THE DEVICE, read when the kernel runs -- is not zero; q and k of those entries are then not read.  Every other entry, and every entry while the
+ * word is zero, gets tf_sdpa_16's result bit for bit (its unsplit LDS-DMA kernel of the same family; no causal form).  A captured launch follows the
+ * word without a re-capture.  Arguments as tf_sdpa_16; an empty range is legal (plain attention).  Head sizes 40, 64, 80, 128 and 160; the launch runs
+ * the family tf_sdpa_instance names with the split forms left out (TF_SDPA_INST_DMA16 / _DMA32 / _DMA32_W8), and tf_sdpa_pag_instance answers with that
+ * rule, host code only.  A head size without an LDS-DMA kernel, a slice of 2 GiB or more (TF_E_UNSUPPORTED), a range outside [0, B] or a NULL flag
+ * (TF_E_ARG) return with a message before the device is touched.  Profiled in family 4 as the plain launch. */
+int tf_sdpa_pag_16(int dtype, void* o, const void* q, const void* k, const void* v, int B, int NH, int Tq, int Tk, int HS, long long q_sb, long long q_sh,
+                   long long q_st, long long k_sb, long long k_sh, long long k_st, long long v_sb, long long v_sh, long long v_st, long long o_sb, long long o_sh,
+                   long long o_st, int pag_b0, int pag_b1, const float* pag_flag_dev, tfStream_t s);
+int tf_sdpa_pag_instance(int dtype, int B, int NH, int Tq, int Tk, int HS, long long k_st, long long v_st, int pag_b0, int pag_b1);
 /* row softmax over (N, C) fp32 -- Device.softmax (storage/device.py:129-157; softmax_func.cu:22-113) */
 int tf_softmax_rows_f32(void* out, const void* inp, int N, int C, tfStream_t s);
 /* softmax step of the UNFUSED attention (attention/sdpa.py:63-75 as the reference runs it: scale * matmul, + mask (:67-68: bool ->
@@ -592,6 +604,20 @@ int tf_sampler_step1_f32(void* latent, const void* eps, void* x0_hist, const voi
                          int B, int C, int H, int W, tfStream_t s);
 int tf_sampler_step1_bf16(void* latent, const void* eps, void* x0_hist, const void* step_params, const void* coeffs, int rows, const void* x0_init, const void* mask,
                           int B, int C, int H, int W, tfStream_t s);
+
+/* ---- perturbed-attention guidance on the sampler above (variants/sd.py compile(..., pag=True)): a third guidance group [uncond ; perturbed ; cond]
+ * next to the CFG pair of variants/sd.py:31, combined by the three-branch expression at g_I = g, g_T = g + s:
+ * e0 + g_T (e2 - e1) + g_I (e1 - e0) = e_u + g (e_c - e_u) + s (e_c - e_p). */
+/* tf_cfg_duplicate_* (variants/sd.py:31) for THREE copies of the latent alone: latent (B,C,H,W) f32 NCHW -> x3b (3B,C,H,W) NHWC 16-bit, every group
+ * rounded as tf_cfg_duplicate_* rounds it; H == 0 or W == 0 writes nothing */
+int tf_latent_stack3_f16(void* x3b, const void* latent, int B, int C, int H, int W, tfStream_t s);
+int tf_latent_stack3_bf16(void* x3b, const void* latent, int B, int C, int H, int W, tfStream_t s);
+/* tf_cfg3_sampler_step_* then the blend of tf_cfg_sampler_step_masked_* (x' <- m x' + (1-m)(sqrt(a_s) x0_init + sqrt(1-a_s) z2), tag 2); edit_params,
+ * x0_init and mask all set */
+int tf_cfg3_sampler_step_masked_f32(void* latent, const void* eps3, void* x0_hist, const void* step_params, const void* coeffs, int rows, const void* edit_params,
+                                    const void* x0_init, const void* mask, int B, int C, int H, int W, tfStream_t s);
+int tf_cfg3_sampler_step_masked_bf16(void* latent, const void* eps3, void* x0_hist, const void* step_params, const void* coeffs, int rows, const void* edit_params,
+                                     const void* x0_init, const void* mask, int B, int C, int H, int W, tfStream_t s);
 
 /* ---- LoRA adapters (csrc/lora.hip; storage/lora.py, variants/sd.py:set_adapters): the reference has no adapters -- its weights come from
  * update_state alone (storage/checkpoint.py).  Every weight is a row matrix (N, Kd) of 16-bit elements: a Linear (out, in), a conv in KRSC

@@ -17,7 +17,7 @@ from ..ff.nn import FeedForward
 from ..native import hip
 from ..storage.tensor import DeviceArray, _sh, is_bfloat16
 from ..vision.conv2d import Conv2d, _conv
-from .sdpa import sdpa_dual_strided, sdpa_strided
+from .sdpa import sdpa_dual_strided, sdpa_pag_strided, sdpa_strided
 
 
 def _concat_rows(ws):
@@ -98,13 +98,17 @@ class CrossAttention:
         """(b, tk, 2C) fused K|V projection of the context (computed once per UNet call by the model)."""
         return linear_f16(context, self._fused_weights(False))
 
-    def __call__(self, x, context=None, residual=None, kv=None, ln=None, ip=None):
+    def __call__(self, x, context=None, residual=None, kv=None, ln=None, ip=None, pag=None):
         """ln: a LayerNorm to apply to x first, folded into the q (or q|k|v) projection (x is then the RAW input).
         ip = (KVSlice, scale_ptr), cross-attention only: decoupled cross-attention over a second K|V set (an IP-Adapter's image tokens, (b, T <= 64,
         ld) with this block's k | v at the slice's columns) -- out = softmax(q K^T / sqrt d) V + s softmax(q K_ip^T / sqrt d) V_ip in the ONE launch
-        sdpa_dual_strided, s the fp32 at the device address scale_ptr; nothing else in the block changes."""
+        sdpa_dual_strided, s the fp32 at the device address scale_ptr; nothing else in the block changes.
+        pag = (flag_ptr, (b0, b1)), self-attention only: perturbed-attention guidance -- while the fp32 at the device address flag_ptr is not zero,
+        the batch entries [b0, b1) take the identity in place of the softmax (out = to_out(v)), in the ONE launch sdpa_pag_strided."""
         if ip is not None and context is None and kv is None:
             raise ValueError("CrossAttention: ip= is for cross-attention (context= or kv=), not self-attention")
+        if pag is not None and (context is not None or kv is not None):
+            raise ValueError("CrossAttention: pag= is for self-attention, not cross-attention (context= or kv=)")
         b, t, _ = x.shape
         nh, hs = self.num_heads, self.head_size
         c = nh * hs
@@ -147,7 +151,9 @@ class CrossAttention:
             os_ = (nh * t * hs, t * hs, hs)      # (b,h,t,d) contiguous, then read as (b, t, h*d): attention.py:38-39
         else:
             os_ = (t * c, hs, c)                 # LDM-intended merge
-        if ip is None:
+        if pag is not None:
+            sdpa_pag_strided(o, q, k, v, pag[0], pag[1], b, nh, t, tk, hs, qs, ks, ks, os_)
+        elif ip is None:
             sdpa_strided(o, q, k, v, b, nh, t, tk, hs, qs, ks, ks, os_)
         else:
             kv2, scale_ptr = ip
@@ -175,16 +181,17 @@ class BasicTransformerBlock:
         self.norm2 = LayerNorm(dim, init=init)
         self.norm3 = LayerNorm(dim, init=init)
 
-    def __call__(self, x, context=None, kv=None, defer_ff2=False, ip=None):
-        """defer_ff2: stop after GEGLU and return (hidden (b, t, 4*dim), x): the caller folds ff.net[2] into what follows.  ip: CrossAttention's, for attn2."""
+    def __call__(self, x, context=None, kv=None, defer_ff2=False, ip=None, pag=None):
+        """defer_ff2: stop after GEGLU and return (hidden (b, t, 4*dim), x): the caller folds ff.net[2] into what follows.  ip: CrossAttention's, for attn2;
+        pag: CrossAttention's, for attn1."""
         if config.fuse_layer_norm and x.shape[-1] % 64 == 0:
-            x = self.attn1(x, residual=x, ln=self.norm1)
+            x = self.attn1(x, residual=x, ln=self.norm1, pag=pag)
             x = self.attn2(x, context=context, residual=x, kv=kv, ln=self.norm2, ip=ip)
             if defer_ff2:
                 return self.ff.net[0](x, ln=self.norm3), x
             x = self.ff(x, residual=x, ln=self.norm3)
             return x
-        x = self.attn1(self.norm1(x), residual=x)
+        x = self.attn1(self.norm1(x), residual=x, pag=pag)
         x = self.attn2(self.norm2(x), context=context, residual=x, kv=kv, ip=ip)
         if defer_ff2:
             return self.ff.net[0](self.norm3(x)), x
@@ -217,21 +224,22 @@ class SpatialTransformer:
             self._fold = (key, DeviceArray.from_numpy(wf.reshape(c, -1, 1, 1), po.weight.dtype), DeviceArray.from_numpy(bf, po.bias.dtype, layout="row"))
         return self._fold[1], self._fold[2]
 
-    def __call__(self, x, context=None, kv=None, out_gn=0, out_norm=None, ip=None):
-        """ip: CrossAttention's (KVSlice, scale_ptr), handed to every block's cross-attention."""
+    def __call__(self, x, context=None, kv=None, out_gn=0, out_norm=None, ip=None, pag=None):
+        """ip: CrossAttention's (KVSlice, scale_ptr), handed to every block's cross-attention; pag: CrossAttention's (flag_ptr, batch range), handed to
+        every block's self-attention."""
         b, c, h, w = x.shape
         x_in = x
         x = self.proj_in(x, gn_in=(self.norm, False))    # GroupNorm -> 1x1 conv (attention.py:66-68) as one launch where the statistics came with x
         x = x.tokens()                                   # (b, hw, c): free re-view of NHWC (attention.py:71)
         if config.fold_proj_out and config.dtype != "fp8" and c % 8 == 0 and self.proj_out.weight.shape[0] == c:   # (fp8: the FeedForward runs in e4m3, proj_out stays fp16)
             for block in self.transformer_blocks[:-1]:
-                x = block(x, context=context, kv=kv, ip=ip)
-            hid, x2 = self.transformer_blocks[-1](x, context=context, kv=kv, defer_ff2=True, ip=ip)
+                x = block(x, context=context, kv=kv, ip=ip, pag=pag)
+            hid, x2 = self.transformer_blocks[-1](x, context=context, kv=kv, defer_ff2=True, ip=ip, pag=pag)
             wf, bf = self._ff2_proj_out()
             pair = (hid.image(b, hid.shape[-1], h, w), x2.image(b, c, h, w))
             return _conv(pair, wf, bf, [0, 0], [1, 1], [1, 1], residual=x_in, gn=out_gn, out_norm=out_norm)
         for block in self.transformer_blocks:
-            x = block(x, context=context, kv=kv, ip=ip)
+            x = block(x, context=context, kv=kv, ip=ip, pag=pag)
         x = x.image(b, c, h, w)                          # attention.py:74
         return self.proj_out(x, residual=x_in, gn=out_gn, out_norm=out_norm)   # + x_in fused (attention.py:75)
 

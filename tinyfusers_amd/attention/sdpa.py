@@ -45,6 +45,26 @@ def sdpa_dual_instance(dtype, B, NH, Tq, Tk, Tk2, HS, k_st=None, v_st=None, k2_s
     return SDPA_INSTANCES[rc]
 
 
+def sdpa_pag_strided(o, q, k, v, flag_ptr, batch_range, B, NH, Tq, Tk, HS, qs, ks, vs, os_):
+    """Raw launch of self-attention under perturbed-attention guidance (tf_sdpa_pag_16), sdpa_strided's conventions plus: ``batch_range`` = (b0, b1)
+    and ``flag_ptr``, the DEVICE address of one fp32 word read when the kernel runs -- while it is not zero the batch entries [b0, b1) get o = v
+    (the identity in place of the softmax, v's bits through the v and o strides given here); every other entry, and every entry while it is zero,
+    gets sdpa_strided's unsplit result bit for bit.  HS in {40, 64, 80, 128, 160}; no causal form."""
+    assert dtag(q.dtype) == dtag(k.dtype) == dtag(v.dtype) == dtag(o.dtype), "sdpa_pag: q / k / v / o must hold the same 16-bit type"
+    hip.tf_sdpa_pag_16(dtag(q.dtype), o.ptr, q.ptr, k.ptr, v.ptr, B, NH, Tq, Tk, HS, *qs, *ks, *vs, *os_, int(batch_range[0]), int(batch_range[1]), flag_ptr, _sh())
+    return o
+
+
+def sdpa_pag_instance(dtype, B, NH, Tq, Tk, HS, k_st=None, v_st=None, batch_range=(0, 0)):
+    """The kernel family sdpa_pag_strided's launch of that shape runs (tf_sdpa_pag_instance: the launcher's own rule, no device needed): "dma16",
+    "dma32" or "dma32_w8" -- sdpa_instance's answer with the split forms left out.  A shape or a batch range the launch would refuse raises."""
+    k_st, v_st = HS if k_st is None else k_st, HS if v_st is None else v_st
+    rc = lib.tf_sdpa_pag_instance(dtag(dtype), B, NH, Tq, Tk, HS, k_st, v_st, int(batch_range[0]), int(batch_range[1]))
+    if rc not in SDPA_INSTANCES:
+        check(rc, "tf_sdpa_pag_instance")
+    return SDPA_INSTANCES[rc]
+
+
 def _is_causal_mask(m, tq, tk):
     m = np.asarray(m)
     if m.shape[-2:] != (tq, tk):

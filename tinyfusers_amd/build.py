@@ -23,12 +23,12 @@ ASAN_FLAGS = ["-fsanitize=address,undefined", "-fno-gpu-sanitize", "-fno-omit-fr
 # the GEMM family is one translation unit per kernel family (gemm_k_*.hip) so that its instances compile in parallel; the largest first
 SOURCES = ["gemm_k_pp16.hip", "gemm_k_pp16_bf16.hip", "gemm_k_pp8.hip", "gemm_k_igemm_128.hip", "gemm_k_igemm_128_bf16.hip", "gemm_k_igemm_64.hip", "gemm_k_igemm_64_bf16.hip",
            "gemm_k_igemm_160.hip", "gemm_k_igemm_160_bf16.hip", "gemm_k_patch.hip", "gemm_k_patch_bf16.hip", "sdpa.hip", "sdpa_bf16.hip", "sdpa_split.hip", "sdpa_split_bf16.hip",
-           "sdpa_dual.hip", "sdpa_dual_bf16.hip", "gemm_k_igemm8.hip", "gemm_k_c4.hip", "gemm_k_c4_bf16.hip", "gemm_k_c8.hip", "gemm_k_c8_bf16.hip", "gemm_k_ar.hip", "gemm_k_ar_bf16.hip", "gemm_k_pp3.hip", "gemm_k_pp3_bf16.hip", "gemm.hip", "gemm_reduce.hip", "norm.hip", "elementwise.hip", "runtime.hip", "sgemm.hip",
+           "sdpa_dual.hip", "sdpa_dual_bf16.hip", "sdpa_pag.hip", "sdpa_pag_bf16.hip", "gemm_k_igemm8.hip", "gemm_k_c4.hip", "gemm_k_c4_bf16.hip", "gemm_k_c8.hip", "gemm_k_c8_bf16.hip", "gemm_k_ar.hip", "gemm_k_ar_bf16.hip", "gemm_k_pp3.hip", "gemm_k_pp3_bf16.hip", "gemm.hip", "gemm_reduce.hip", "norm.hip", "elementwise.hip", "runtime.hip", "sgemm.hip",
            "comm.hip", "rtc.hip", "sampler.hip", "img2img.hip", "control.hip", "lora.hip", "vit.hip", "freeu.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function", "-ffp-contract=fast"]
 # sdpa.hip: keep the MFMA accumulators in VGPRs (the softmax reads every score: no v_accvgpr_read traffic) and drop
 # the NaN-canonicalising v_max in front of every fmaxf on MFMA outputs (scores are never NaN; -inf masks still work)
-SDPA_UNITS = ["sdpa.hip", "sdpa_bf16.hip", "sdpa_split.hip", "sdpa_split_bf16.hip", "sdpa_dual.hip", "sdpa_dual_bf16.hip"]     # sdpa.hip itself and the units that #include it
+SDPA_UNITS = ["sdpa.hip", "sdpa_bf16.hip", "sdpa_split.hip", "sdpa_split_bf16.hip", "sdpa_dual.hip", "sdpa_dual_bf16.hip", "sdpa_pag.hip", "sdpa_pag_bf16.hip"]     # sdpa.hip itself and the units that #include it
 EXTRA = {s: ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans"] for s in SDPA_UNITS}
 
 
@@ -70,7 +70,7 @@ def build(force=False, verbose=False, ablation=False, tag=None, defs=(), asan_ho
         src = os.path.join(CSRC, s)
         obj = os.path.join(objdir, s.replace(".hip", ".o"))
         objs.append(obj)
-        twin = [os.path.join(CSRC, "sdpa.hip")] if s in SDPA_UNITS else [os.path.join(CSRC, s.replace("_bf16.hip", ".hip"))] if s.endswith("_bf16.hip") else []
+        twin = [os.path.join(CSRC, "sdpa.hip"), os.path.join(CSRC, s.replace("_bf16.hip", ".hip"))] if s in SDPA_UNITS else [os.path.join(CSRC, s.replace("_bf16.hip", ".hip"))] if s.endswith("_bf16.hip") else []
         if force or _stale(obj, [src] + twin + headers):
             jobs.append([hipcc] + FLAGS + (["-DTF_ABLATION"] if ablation else []) + (ASAN_FLAGS if asan_host else []) + list(defs) + EXTRA.get(s, []) + ["-c", src, "-o", obj])
 

@@ -86,7 +86,8 @@ __global__ void __launch_bounds__(EW_BLOCK) k_latent_stack(T* __restrict__ x, co
 // The tail.  eps = G guidance groups of (B, HW, C) 16-bit NHWC, combined into e:
 //   G = 1  e = eps                                  (params[3], the guidance, is not read)
 //   G = 2  e = e_u + g (e_c - e_u)                  g = params[3]
-//   G = 3  e = e0 + g_T (e2 - e1) + g_I (e1 - e0)   g_T = params[3], g_I = edit[0]
+//   G = 3  e = e0 + g_T (e2 - e1) + g_I (e1 - e0)   g_T = params[3], g_I = edit[0]  (an edit model's [x|0, unc ; x|c, unc ; x|c, ctx]; perturbed-
+//          attention guidance's [uncond ; perturbed ; cond] at g_I = g, g_T = g + s: e_u + g (e_c - e_u) + s (e_c - e_p))
 // then x0 = (x - sqrt(1-a_t) e) / sqrt(a_t); x' = c_x x + c_0 x0 + c_1 x0_prev + c_n z (tag 1); x0_prev <- x0.  [c_x, c_0, c_1, c_n] =
 // coeffs[row], row = the schedule index the parameter launch wrote.  x0_prev is read only when c_1 != 0 (a fresh history never reaches the
 // first step) and the tag-1 noise is drawn only when c_n != 0.  MASKED: then the inpainting blend
@@ -147,7 +148,7 @@ __global__ void __launch_bounds__(EW_BLOCK) k_sampler_step(float* __restrict__ l
   }
 }
 
-// The head's launch, and the argument rule of each of its three entries in front of it.
+// The head's launch, and the argument rule of each of its four entries in front of it.
 template <typename T>
 static int latent_stack(void* x_out, const void* latent, const void* cond, int B, int C, int Cc, int H, int W, int groups, unsigned drop_bits, tfStream_t s) {
   const long long n = (long long)B * H * W * (C + Cc);
@@ -170,6 +171,14 @@ template <typename T>
 static int cfg_duplicate(const char* name, void* x2b, const void* latent, int B, int C, int H, int W, tfStream_t s) {
   TF_REQUIRE(x2b && latent && B > 0 && C > 0 && H >= 0 && W >= 0, "%s: bad arguments", name);
   return latent_stack<T>(x2b, latent, nullptr, B, C, 0, H, W, 2, 0u, s);
+}
+
+// three guidance groups of the latent alone (perturbed-attention guidance on a 4-channel UNet): cfg_duplicate's rule, which tf_cfg_concat_* (Cc > 0,
+// cond set) cannot express
+template <typename T>
+static int latent_stack3(const char* name, void* x3b, const void* latent, int B, int C, int H, int W, tfStream_t s) {
+  TF_REQUIRE(x3b && latent && B > 0 && C > 0 && H >= 0 && W >= 0, "%s: bad arguments", name);
+  return latent_stack<T>(x3b, latent, nullptr, B, C, 0, H, W, 3, 0u, s);
 }
 
 template <typename T>
@@ -200,7 +209,7 @@ static int sampler_step(const char* name, int G, void* latent, const void* eps, 
   const long long n_img = (long long)C * H * W;
   TF_REQUIRE(n_img <= (1LL << 32), "%s: %lld elements per image exceed the 2^32 Philox counters of an image", name, n_img);
   void (*k)(float*, const T*, float*, const float*, const float*, int, const float*, const float*, const float*, int, int, int) =
-      G == 3 ? k_sampler_step<T, 3, false>
+      G == 3 ? (mask ? k_sampler_step<T, 3, true> : k_sampler_step<T, 3, false>)
       : G == 2 ? (mask ? k_sampler_step<T, 2, true> : k_sampler_step<T, 2, false>)
                : (mask ? k_sampler_step<T, 1, true> : k_sampler_step<T, 1, false>);
   hipLaunchKernelGGL(k, dim3(ew_grid(((n_img + 3) >> 2) * B)), dim3(EW_BLOCK), 0, tf_hs(s), (float*)latent, (const T*)eps, (float*)x0_hist, (const float*)params,
@@ -311,6 +320,26 @@ int tf_cfg3_sampler_step_bf16(void* latent, const void* eps3, void* x0_hist, con
                               int B, int C, int H, int W, tfStream_t s) {
   return sampler_step<bf16_t>("tf_cfg3_sampler_step_bf16", 3, latent, eps3, x0_hist, step_params, coeffs, rows, edit_params, nullptr, nullptr, edit_params != nullptr,
                               nullptr, B, C, H, W, s);
+}
+
+int tf_latent_stack3_f16(void* x3b, const void* latent, int B, int C, int H, int W, tfStream_t s) {
+  return latent_stack3<half_t>("tf_latent_stack3_f16", x3b, latent, B, C, H, W, s);
+}
+
+int tf_latent_stack3_bf16(void* x3b, const void* latent, int B, int C, int H, int W, tfStream_t s) {
+  return latent_stack3<bf16_t>("tf_latent_stack3_bf16", x3b, latent, B, C, H, W, s);
+}
+
+int tf_cfg3_sampler_step_masked_f32(void* latent, const void* eps3, void* x0_hist, const void* step_params, const void* coeffs, int rows, const void* edit_params,
+                                    const void* x0_init, const void* mask, int B, int C, int H, int W, tfStream_t s) {
+  return sampler_step<half_t>("tf_cfg3_sampler_step_masked_f32", 3, latent, eps3, x0_hist, step_params, coeffs, rows, edit_params, x0_init, mask,
+                              edit_params && x0_init && mask, nullptr, B, C, H, W, s);
+}
+
+int tf_cfg3_sampler_step_masked_bf16(void* latent, const void* eps3, void* x0_hist, const void* step_params, const void* coeffs, int rows, const void* edit_params,
+                                     const void* x0_init, const void* mask, int B, int C, int H, int W, tfStream_t s) {
+  return sampler_step<bf16_t>("tf_cfg3_sampler_step_masked_bf16", 3, latent, eps3, x0_hist, step_params, coeffs, rows, edit_params, x0_init, mask,
+                              edit_params && x0_init && mask, nullptr, B, C, H, W, s);
 }
 
 int tf_sampler_step1_f32(void* latent, const void* eps, void* x0_hist, const void* step_params, const void* coeffs, int rows, const void* x0_init, const void* mask,

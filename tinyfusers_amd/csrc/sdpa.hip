@@ -23,6 +23,9 @@
 #ifndef TF_TU_DUAL
 #define TF_TU_DUAL 0       // 1: the dual (two key sets) instances only (sdpa_dual.hip / sdpa_dual_bf16.hip), for the same reason
 #endif
+#ifndef TF_TU_PAG
+#define TF_TU_PAG 0        // 1: the shared part of this file only; sdpa_pag.hip / sdpa_pag_bf16.hip put the perturbed-attention instances behind their #include
+#endif
 
 struct SdpaP {
   const half_t* q; const half_t* k; const half_t* v; half_t* o;
@@ -517,7 +520,9 @@ extern "C" int tf_sdpa_dual_16(int dtype, void* o, const void* q, const void* k,
   return dtype == TF_DTYPE_BF16 ? tfk_sdpa_dual_bf16(pd, rule, st) : tfk_sdpa_dual(pd, rule, st);
 }
 #endif
-#else   // neither: everything below is the unsplit units' (sdpa.hip, sdpa_bf16.hip)
+#elif TF_TU_PAG
+// (sdpa_pag.hip: k_sdpa_pag and tf_sdpa_pag_16 follow its #include of this file)
+#else   // none of them: everything below is the unsplit units' (sdpa.hip, sdpa_bf16.hip)
 
 template <int HS, int QT, int DBG = 0, int NW = 4, bool BF = false>        // DBG: compile-time ablation mask (tools/sdpa_dbg.py; bits as SdpaP::dbg); BF: bfloat16 q / k / v / o (sdpa_bf16.hip)
 __global__ void __launch_bounds__(NW * 64) k_sdpa_dma(const SdpaP p) {

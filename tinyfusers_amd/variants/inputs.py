@@ -90,6 +90,63 @@ def freeu_scales(values, who="set_freeu"):
     return np.ascontiguousarray(sc)
 
 
+PAG_WORDS = 16            # vision/unet.py::PAG_WORDS: the flag array of perturbed-attention guidance, one 64-byte write
+
+
+def pag_layer_words(layers, table, who="set_pag"):
+    """set_pag's ``layers`` -> the PAG_WORDS fp32 flag words (1 = this SpatialTransformer's self-attention is perturbed).  ``table``: the UNet's
+    vision/unet.py::pag_layers paths in execution order.  A layer is an index into the table, an LDM path ("input_blocks.4", "middle_block",
+    "output_blocks.7"; a trailing ".1" -- the transformer's place inside its block -- is accepted), one of the shorthands "down" / "mid" / "up" /
+    "all", or a list of any of these (an empty list: no layer).  Everything is checked before the words are returned: an unknown name, or an index
+    or a block without a transformer, raises ValueError."""
+    def refuse(item):
+        raise ValueError(f"StableDiffusion.{who}: pag layer {item!r} names no SpatialTransformer of this UNet (an index below {len(table)}, one of "
+                         f"{', '.join(table)}, or 'down' / 'mid' / 'up' / 'all')")
+    groups = {"down": "input_blocks.", "mid": "middle_block", "up": "output_blocks.", "all": ""}
+    items = list(layers) if isinstance(layers, (list, tuple)) else [layers]
+    words = np.zeros((PAG_WORDS,), np.float32)
+    for item in items:
+        if isinstance(item, (bool, np.bool_)):
+            refuse(item)
+        if isinstance(item, (int, np.integer)):
+            if not 0 <= int(item) < len(table):
+                refuse(item)
+            words[int(item)] = 1.0
+        elif isinstance(item, str) and item in groups:
+            words[[i for i, p in enumerate(table) if p.startswith(groups[item])]] = 1.0
+        elif isinstance(item, str):
+            path = item if item in table or not item.endswith(".1") else item[:-2]
+            if path not in table:
+                refuse(item)
+            words[table.index(path)] = 1.0
+        else:
+            refuse(item)
+    return words
+
+
+def pag_values(scale, adaptive, who="set_pag"):
+    """(scale, adaptive scale) of perturbed-attention guidance as two finite floats >= 0, or ValueError."""
+    try:
+        s, a = float(scale), float(adaptive)
+    except (TypeError, ValueError):
+        s = a = float("nan")
+    if not (np.isfinite(s) and np.isfinite(a) and s >= 0 and a >= 0):
+        raise ValueError(f"StableDiffusion.{who}: the PAG scale and adaptive scale are finite floats >= 0, got {scale!r}, {adaptive!r}")
+    return s, a
+
+
+def pag_scale_at(scale, adaptive, timestep):
+    """s_t = max(0, s - a (1000 - t)): the perturbed-attention guidance scale at a timestep, as diffusers' PAG pipelines state it."""
+    return max(0.0, float(scale) - float(adaptive) * (1000.0 - float(timestep)))
+
+
+def pag_guidance_words(guidance, s_t, cfg=True):
+    """The two scalars the existing tails read, from the CFG scale g and s_t: (the parameter block's guidance word, the edit word or None).
+    With CFG the groups are [uncond ; perturbed ; cond] and the three-group tail's e0 + g_T (e2 - e1) + g_I (e1 - e0) at g_T = g + s_t, g_I = g is
+    e_u + g (e_c - e_u) + s_t (e_c - e_p); without, [perturbed ; cond] and the pair tail's e_p + (1 + s_t)(e_c - e_p) is e_c + s_t (e_c - e_p)."""
+    return (float(guidance) + float(s_t), float(guidance)) if cfg else (1.0 + float(s_t), None)
+
+
 def ip_embeds(x, batch, width):
     """start(ip_image_embeds=): a host float (B, E) array (or one row for every image) -> fp32 (B, E)."""
     if isinstance(x, DeviceArray):
@@ -103,11 +160,23 @@ def ip_embeds(x, batch, width):
 
 
 def check_compile(cin, has_control_net, config, latent, sampler, inpaint, concat, control, cfg=True, ip_adapter=False, has_ip_adapter=False,
-                  freeu=False, freeu_plan=()):
+                  freeu=False, freeu_plan=(), pag=False, pag_table=()):
     """compile()'s refusals, before any device work: ``cin`` the UNet's in_channels, ``config`` the package's config module, ``freeu_plan`` the
-    UNet's vision/unet.py::freeu_stages rows (stage, block, backbone channels, skip channels, latent size divisor)."""
+    UNet's vision/unet.py::freeu_stages rows (stage, block, backbone channels, skip channels, latent size divisor), ``pag_table`` its
+    vision/unet.py::pag_layers paths."""
     def refuse(exc, text):
         raise exc(f"StableDiffusion.compile: {text}")
+    if pag:
+        if sampler is None:
+            refuse(ValueError, "pag=True needs a sampler schedule (sampler=<Schedule>)")
+        if concat == "edit":
+            refuse(ValueError, "pag=True and concat='edit' together are not supported (InstructPix2Pix runs three guidance groups already: the perturbed one would be a fourth)")
+        if config.cfg_parallel:
+            refuse(UnsupportedSamplerConfig, "perturbed-attention guidance has no two-chain CFG form (TF_CFG_PARALLEL)")
+        if config.dtype == "fp8":
+            refuse(UnsupportedSamplerConfig, "pag=True runs in the fp16 and the bf16 step, not under the fp8 policy (config.set_dtype('fp8'))")
+        if len(pag_table) > PAG_WORDS:
+            refuse(ValueError, f"pag=True: this UNet has {len(pag_table)} SpatialTransformers, the flag array holds {PAG_WORDS}")
     if freeu:
         if sampler is None:
             refuse(ValueError, "freeu=True needs a sampler schedule (sampler=<Schedule>)")

@@ -20,6 +20,8 @@ LoRA adapters (storage/lora.py; ``load_lora``, ``set_adapters``, ``adapters``, `
 on B images against the context alone, between tf_latent_stack1_* and tf_sampler_step1_* (csrc/sampler.hip).
 ``compile(..., freeu=True)`` is FreeU inside the captured step (csrc/freeu.hip; ``set_freeu``, ``start(freeu=)``): Fourier-filtered skips and a
 scaled backbone in front of the concats of the first two decoder stages, four device scalars that change without a re-capture.
+``compile(..., pag=True)`` is perturbed-attention guidance inside the captured step (csrc/sdpa_pag.hip; ``set_pag``, ``start(pag=)``): one more
+guidance group whose self-attentions are the identity in the selected transformers, combined by the tails that exist.
 
 How the object is laid out.  Everything ``compile`` / ``start`` / ``set_context`` / ``set_adapters`` keep on the model is declared, with its
 "not compiled" value, in ``_reset_state``: ``__init__`` runs all of it, ``compile`` the per-compile part, so a re-compile with other flags drops the
@@ -35,7 +37,7 @@ import numpy as np
 from .. import config
 from ..native import hip
 from ..storage.tensor import Branch, DeviceArray, Stream, _sh, asarray, bfloat16, dtag, pool, use_stream
-from ..vision.unet import SD15, SD15_EDIT, SD15_INPAINT, StepParams, UNetModel, freeu_stages
+from ..vision.unet import SD15, SD15_EDIT, SD15_INPAINT, StepParams, UNetModel, freeu_stages, pag_layers
 from . import inputs
 from .samplers import UnsupportedSamplerConfig, get_alphas_cumprod  # noqa: F401  (get_alphas_cumprod: variants/sd.py:61-65, re-exported)
 
@@ -91,6 +93,8 @@ class StableDiffusion:
         self._stream = None                      # the sampler stream; None: never compiled
         self._latent = self._unc = self._ctx = self._ctx2 = None     # the caller's latent and contexts; the private stacked context
         self._sched, self._inpaint, self._concat, self._control, self._groups = None, False, None, False, 2      # the mode
+        self._cfg = True                         # cfg=False: no unconditional group (one group; with pag=True [perturbed ; cond])
+        self._pag, self._pag_flags, self._pag_scale, self._pag_edit_g = False, None, (3.0, 0.0), None     # pag=True: the 16 layer words; (scale, adaptive scale); the g the edit word holds
         self._coeffs = self._x0_hist = None      # sampler: coefficient table, fp32 x0 history
         self._x0_init = self._mask = None        # inpaint=True: the clean latent and the (B,1,h,w) mask
         self._cond = self._edit = None           # concat=: the conditioning channels; [0] g_I of the three-branch update
@@ -301,6 +305,17 @@ class StableDiffusion:
         _entry16("tf_latent_stack1", "f16")(x.ptr, self._latent.ptr, self._cond.ptr if cc else None, b, c, cc, h, w, _sh())
         return x
 
+    def _latent_stack3(self):
+        """variants/sd.py:31 for the three guidance groups of pag=True on a 4-channel UNet: the latent three times, NHWC in the step's 16-bit type."""
+        b, c, h, w = self._latent.shape
+        x = DeviceArray.empty((3 * b, c, h, w), _step_dtype(), "nhwc")
+        _entry16("tf_latent_stack3", "f16")(x.ptr, self._latent.ptr, b, c, h, w, _sh())
+        return x
+
+    def _cond_groups(self):
+        """How many of the last guidance groups read the conditional inputs: the conditional group, and in front of it pag=True's perturbed one."""
+        return 2 if self._pag else 1
+
     def _cfg_concat(self):
         """variants/sd.py:31 for a concat-conditioned UNet: [latent | cond] for every guidance group, NHWC in the step's 16-bit type; an edit
         model's first group (bit 0 of drop_bits) reads zeros in place of the conditioning."""
@@ -311,12 +326,14 @@ class StableDiffusion:
         return x
 
     @staticmethod
-    def _stack_context(unconditional_context, context, groups=2):
-        """[unc ; ctx], or for the three guidance branches of an edit model [unc ; unc ; ctx]; one group (cfg=False): ctx alone, unc is not read."""
+    def _stack_context(unconditional_context, context, groups=2, cond_groups=1):
+        """[unc ; ctx], or for the three guidance branches of an edit model [unc ; unc ; ctx]; one group (cfg=False): ctx alone, unc is not read.
+        cond_groups = 2 (pag=True): the last TWO groups read ctx -- [unc ; ctx ; ctx], or [ctx ; ctx] without CFG: the perturbed group runs on the
+        conditional inputs."""
         b, t, d = context.shape
         ctx = DeviceArray.empty((groups * b, t, d), context.dtype, "row")
         for g in range(groups):
-            src = context if g == groups - 1 else unconditional_context
+            src = context if g >= groups - cond_groups else unconditional_context
             hip.tf_memcpy_async(ctx.ptr + g * context.nbytes, src.ptr, context.nbytes, 3, _sh())
         if config.is_bf16():
             from ..ff.linear import to_bf16
@@ -349,7 +366,7 @@ class StableDiffusion:
 
     # -- whole-step HIP graph ------------------------------------------------------------------------
     def compile(self, unconditional_context, context, latent, stream=None, warmup=2, timesteps=None, sampler=None, inpaint=False, concat=None, control=False,
-                cfg=True, ip_adapter=False, freeu=False):
+                cfg=True, ip_adapter=False, freeu=False, pag=False):
         """Capture one denoising step for these (static) buffers into a HIP graph.  Afterwards
         ``step(timestep, a_t, a_prev, guidance)`` updates ``latent`` in place with one graph launch.
 
@@ -411,21 +428,37 @@ class StableDiffusion:
         to fp32 summation order and the 16-bit rounding of the producer's output.  Combines with cfg=False, inpaint=True, both concat= modes,
         control=True, ip_adapter=True, LoRA, bf16; not with TF_CFG_PARALLEL or the fp8 policy.
 
+        ``pag=True`` (with a sampler only): perturbed-attention guidance (Ahn et al. 2024, as diffusers' PAG pipelines state it).  One more
+        guidance group, the perturbed one, runs the UNet on the conditional inputs (the prompt's context, an IP-Adapter's image tokens, the
+        concat="inpaint" channels, the control hint) with the self-attention of the selected SpatialTransformers replaced by the identity,
+        attn1(x) = to_out(to_v(norm1(x))): the groups are [uncond ; perturbed ; cond] (three) and, with cfg=False, [perturbed ; cond] (two).  Every
+        self-attention of the UNet becomes tf_sdpa_pag_16 -- one launch either way, the same number of graph nodes as the step without PAG --
+        which reads its layer's word of a 16-word device array when it runs; a ControlNet runs all groups unperturbed.  The combine is
+        e = e_u + g (e_c - e_u) + s_t (e_c - e_p) (cfg=False: e_c + s_t (e_c - e_p)), s_t = max(0, s - a (1000 - t)), through the tails that
+        exist: the three-group expression at g_I = g, g_T = g + s_t, the pair expression at guidance 1 + s_t -- the scale travels in the guidance
+        word of the parameter launch and in the edit word, so a replay has no launch more.  ``set_pag`` / ``start(pag=)`` change scale, layers and
+        adaptive scale without a re-capture; after compile they are 3.0, "mid" and 0.  With no layer selected e_p is e_c bit for bit; at scale 0
+        the step is the pag=False step up to the tail's rounding.  Combines with cfg=False, inpaint=True, concat="inpaint", control=True,
+        ip_adapter=True, freeu=True, LoRA, bf16; not with concat="edit" (a fourth group), TF_CFG_PARALLEL or the fp8 policy.  The UNet's head sizes
+        must be among 40, 64, 80, 128 and 160 (the LDS-DMA attention families; SD-1.5: 40, 80, 160).
+
         The arguments are remembered: ``set_adapters`` (LoRA) on a compiled model swaps weight handles and calls ``compile`` again with the same ones."""
         inputs.check_compile(self.model.diffusion_model.cfg.in_channels, self.control_model is not None, config, latent, sampler, inpaint, concat, control, cfg,
                              ip_adapter=ip_adapter, has_ip_adapter=self._ip_model is not None, freeu=freeu,
-                             freeu_plan=freeu_stages(self.model.diffusion_model.cfg) if freeu else ())
-        if ip_adapter and warmup < 1:
-            raise ValueError("StableDiffusion.compile: ip_adapter=True needs warmup >= 1 (the first launch of an attention instance cannot be captured)")
+                             freeu_plan=freeu_stages(self.model.diffusion_model.cfg) if freeu else (), pag=pag,
+                             pag_table=pag_layers(self.model.diffusion_model.cfg) if pag else ())
+        if (ip_adapter or pag) and warmup < 1:
+            raise ValueError(f"StableDiffusion.compile: {'ip_adapter' if ip_adapter else 'pag'}=True needs warmup >= 1 (the first launch of an attention instance cannot be captured)")
         if sampler is not None:
             timesteps = sampler.timesteps
         self._reset_state()
         self._compile_args = dict(unconditional_context=unconditional_context, context=context, latent=latent, warmup=warmup, timesteps=timesteps,
-                                  sampler=sampler, inpaint=inpaint, concat=concat, control=control, cfg=cfg, ip_adapter=ip_adapter, freeu=freeu)
+                                  sampler=sampler, inpaint=inpaint, concat=concat, control=control, cfg=cfg, ip_adapter=ip_adapter, freeu=freeu, pag=pag)
         self._stream = stream or Stream()
         self._latent, self._unc, self._ctx = latent, unconditional_context, context
         self._sched, self._inpaint, self._concat, self._control = sampler, bool(inpaint), concat, bool(control)
-        self._groups = 3 if concat == "edit" else 2 if cfg else 1
+        self._cfg, self._pag = bool(cfg), bool(pag)
+        self._groups = 3 if concat == "edit" else (2 if cfg else 1) + (1 if pag else 0)
         self._ip = bool(ip_adapter)
         self._freeu = bool(freeu)
         self._ip_model_compiled = self._ip_model if self._ip else None
@@ -450,13 +483,16 @@ class StableDiffusion:
             self._mask = DeviceArray.from_numpy(np.ones((b, 1, h, w), np.float32), np.float32, "row")
         if self._concat is not None:
             self._cond = DeviceArray.zeros((b, inputs.CONCAT_CHANNELS[self._concat], h, w), np.float32, "row")
-            self._edit = DeviceArray.zeros((4,), np.float32, "row")      # [0] g_I, the image guidance of the three-branch update
+        if self._concat is not None or self._groups == 3:
+            self._edit = DeviceArray.zeros((4,), np.float32, "row")      # [0] g_I, the image guidance of the three-branch update (pag=True: the CFG scale g)
             hip.tf_set_step_params(self._edit.ptr, 1.5, 0.0, 0.0, 0.0, _sh())
         if self._control:
             self._hint_emb = DeviceArray.zeros((self._groups * b, self.control_model.cfg.model_channels, h, w), _step_dtype(), "nhwc")
             self._control_scales = DeviceArray.from_numpy(np.ones((16,), np.float32), np.float32, "row")     # one per residual; 16: whole 4-word writes
         if self._freeu:
             self._freeu_scales = DeviceArray.from_numpy(np.ones((4,), np.float32), np.float32, "row")      # [s1, s2, b1, b2]: one 4-word write
+        if self._pag:
+            self._pag_flags = DeviceArray.from_numpy(inputs.pag_layer_words("mid", pag_layers(self.model.diffusion_model.cfg)), np.float32, "row")
         if self._ip:
             ad = self._ip_model_compiled
             self._ip_kv = DeviceArray.zeros((self._groups * b, ad.num_tokens, ad.kv_layout()[1]), _step_dtype(), "row")
@@ -465,7 +501,7 @@ class StableDiffusion:
     def _hoist(self, sp, timesteps):
         """The private stacked context and -- config.hoist_step_invariants -- what depends on it or on the timestep alone: the K|V projections and
         the buffer ``_emb_cur`` the captured step reads its time-embedding row from, with the rows of ``timesteps`` computed up front."""
-        self._ctx2 = self._stack_context(self._unc, self._ctx, self._groups)
+        self._ctx2 = self._stack_context(self._unc, self._ctx, self._groups, self._cond_groups())
         if not config.hoist_step_invariants or config.cfg_parallel:
             return
         self._kv_all, self._kv_key = self.model.diffusion_model.context_kv(self._ctx2), self._weights_key()
@@ -518,7 +554,8 @@ class StableDiffusion:
 
     def _eager_step(self, sp):
         """One step, launch by launch -- what ``_capture`` records: the stacked input, the UNet, the tail that updates the latent."""
-        x2 = self._latent_stack1() if self._groups == 1 else self._cfg_concat() if self._concat else self._cfg_duplicate(self._latent)
+        x2 = self._latent_stack1() if self._groups == 1 else self._cfg_concat() if self._concat else self._latent_stack3() if self._groups == 3 \
+            else self._cfg_duplicate(self._latent)
         outs = self._unet_two_chains(x2, sp) if config.cfg_parallel else (self._unet(x2, sp),)
         self._tail(sp, *outs[:2])
         self._keep = (x2,) + outs       # graph nodes reference these blocks: keep them out of the pool
@@ -527,8 +564,10 @@ class StableDiffusion:
         """The UNet's output for the stacked input: plain, from the hoisted row and K|V, or controlled."""
         unet, cn, row, ctx = self.model.diffusion_model, self.control_model, self._emb_cur, self._ctx2
         ip = (self._ip_model_compiled, self._ip_kv, self._ip_scales) if self._ip else None
+        b = self._latent.shape[0]
+        pag = (self._pag_flags, ((self._groups - 2) * b, (self._groups - 1) * b)) if self._pag else None      # the group in front of the conditional one
         if not self._control:
-            return unet(x2, sp, ctx, shared=None if row is None else (None, row, self._kv_all), ip=ip, freeu=self._freeu_scales)     # (step() has put this timestep's row into _emb_cur)
+            return unet(x2, sp, ctx, shared=None if row is None else (None, row, self._kv_all), ip=ip, freeu=self._freeu_scales, pag=pag)     # (step() has put this timestep's row into _emb_cur)
         # the UNet's encoder, then the ControlNet on the same stacked latent, then the seam (UNetModel.__call__ calls `residuals` behind its
         # middle block); each model reads its own view of the hoisted row [UNet's | ControlNet's]
         shared_u = shared_c = None
@@ -537,7 +576,7 @@ class StableDiffusion:
             shared_u = (None, row.view((1, nu), "row"), self._kv_all)
             shared_c = (None, row.view((1, row.shape[1] - nu), "row", nu), self._ckv_all)
         residuals = lambda: cn(x2, self._hint_emb, sp, ctx, shared=shared_c)
-        return unet(x2, sp, ctx, shared=shared_u, control=(residuals, self._control_scales), ip=ip, freeu=self._freeu_scales)
+        return unet(x2, sp, ctx, shared=shared_u, control=(residuals, self._control_scales), ip=ip, freeu=self._freeu_scales, pag=pag)
 
     def _unet_two_chains(self, x2, sp):
         """config.cfg_parallel: the unconditional and the conditional half of the CFG pair (variants/sd.py:31-32) as two independent UNet chains: one
@@ -555,7 +594,8 @@ class StableDiffusion:
 
     def _tail(self, sp, out, out_c=None):
         """The step's last launch, by mode: CFG combine + the DDIM update (from two chains: tf_cfg_ddim_step2_f32), or the sampler update of the
-        schedule's row -- three-branch for an edit model, masked for inpaint=True, single-branch (tf_sampler_step1_*, both forms) for cfg=False."""
+        schedule's row -- three-branch for an edit model and for pag=True with CFG, masked for inpaint=True, single-branch (tf_sampler_step1_*, both
+        forms) for cfg=False without PAG; pag=True with cfg=False ends in the pair's tails on [perturbed ; cond]."""
         lat, (b, c, h, w) = self._latent, self._latent.shape
         if out_c is not None:
             return hip.tf_cfg_ddim_step2_f32(lat.ptr, out.ptr, out_c.ptr, sp.dev.ptr, b, c, h, w, _sh())
@@ -564,7 +604,8 @@ class StableDiffusion:
         if self._groups == 1:
             extra = (self._x0_init.ptr, self._mask.ptr) if self._inpaint else (None, None)
             return _entry16("tf_sampler_step1", "f32")(lat.ptr, out.ptr, self._x0_hist.ptr, sp.dev.ptr, self._coeffs.ptr, len(self._sched.timesteps), *extra, b, c, h, w, _sh())
-        stem, extra = ("tf_cfg3_sampler_step", (self._edit.ptr,)) if self._concat == "edit" else \
+        stem, extra = ("tf_cfg3_sampler_step_masked", (self._edit.ptr, self._x0_init.ptr, self._mask.ptr)) if self._groups == 3 and self._inpaint else \
+                      ("tf_cfg3_sampler_step", (self._edit.ptr,)) if self._groups == 3 else \
                       ("tf_cfg_sampler_step_masked", (self._x0_init.ptr, self._mask.ptr)) if self._inpaint else ("tf_cfg_sampler_step", ())
         _entry16(stem, "f32")(lat.ptr, out.ptr, self._x0_hist.ptr, sp.dev.ptr, self._coeffs.ptr, len(self._sched.timesteps), *extra, b, c, h, w, _sh())
 
@@ -627,7 +668,7 @@ class StableDiffusion:
 
     def start(self, seed=None, noise=None, image_offset=0, init_image=None, init_latent=None, mask=None, cond_image=None, cond_mask=None,
               cond_latent=None, image_guidance=None, control_image=None, control_hint=None, control_scale=None, ip_image_embeds=None, ip_image=None,
-              ip_scale=None, freeu=None):
+              ip_scale=None, freeu=None, pag=None):
         """A new image batch for the compiled sampler: sets the latent in place and rewinds the schedule.  ``seed``: the initial latent is
         drawn on the device (tag 0; image b is global image image_offset + b), and the ancestral noise of every step comes from the same seed
         (tag 1); ``noise``: a host (B,C,H,W) array for the initial latent instead (the ancestral noise then uses ``seed``, default 0).
@@ -659,8 +700,12 @@ class StableDiffusion:
         the device, ordered into the sampler stream; [0 | embeddings] for the CFG pair is built there too.  Without a tower it is refused.
 
         A FreeU model (compile(..., freeu=True)): ``freeu=(s1, s2, b1, b2)`` writes the four scalars as ``set_freeu`` does; without it they keep
-        their values."""
+        their values.
+
+        A PAG model (compile(..., pag=True)): ``pag=(scale, layers)`` or ``(scale, layers, adaptive)`` sets what ``set_pag`` sets; without it they
+        keep their values."""
         self._require_sampler("start")
+        pg = self._check_pag(pag, "start")
         fu = self._check_freeu(freeu, "start")
         ipa = self._check_ip(ip_image_embeds, ip_image, ip_scale)
         ctrl = self._check_control(control_image, control_hint, control_scale)
@@ -675,7 +720,38 @@ class StableDiffusion:
             self._write_ip(*ipa)
         if fu is not None:
             self._write_freeu(fu)
+        if pg is not None:
+            self._write_pag(*pg)
         return self._latent
+
+    def _check_pag(self, pag, who):
+        """(scale, layers[, adaptive]) checked against the compiled model before anything changes: None when not given, else (the 16 fp32 layer
+        words, (scale, adaptive scale))."""
+        if pag is None:
+            return None
+        if not self._pag:
+            raise ValueError(f"StableDiffusion.{who}: " + ("pag= needs" if who == "start" else "needs") + " a model compiled with pag=True")
+        if not isinstance(pag, (tuple, list)) or len(pag) not in (2, 3):
+            raise ValueError(f"StableDiffusion.{who}: pag takes (scale, layers) or (scale, layers, adaptive), got {pag!r}")
+        values = inputs.pag_values(pag[0], pag[2] if len(pag) == 3 else 0.0, who)
+        return inputs.pag_layer_words(pag[1], pag_layers(self.model.diffusion_model.cfg), who), values
+
+    def _write_pag(self, words, values):
+        """The layer words -- one 64-byte write, four 4-word parameter launches on the sampler stream, behind every step already queued -- and the
+        scales, which stay on the host: step_sampler folds them into the guidance word of its parameter launch."""
+        with use_stream(self._stream, ordered=False):                    # stream-ordered: the values travel as kernel arguments
+            for q in range(4):
+                hip.tf_set_step_params(self._pag_flags.ptr + 16 * q, *(float(v) for v in words[4 * q:4 * q + 4]), _sh())
+        self._pag_scale = values
+
+    def set_pag(self, scale=3.0, layers="mid", adaptive=0.0):
+        """Perturbed-attention guidance from the next step on.  ``scale``: s; ``adaptive``: a of s_t = max(0, s - a (1000 - t)); ``layers``: the
+        SpatialTransformers whose self-attention the perturbed group replaces by the identity -- indices in execution order (SD-1.5: input_blocks
+        0-5, middle_block 6, output_blocks 7-15), LDM paths ("input_blocks.4", "middle_block", "output_blocks.7"), the shorthands "down", "mid",
+        "up", "all", or a list of any of these ([]: none, then e_p = e_c).  All of it is checked before anything is written.  The captured step
+        reads the layer words from the device and the scale from the words its parameter launch carries: nothing is captured again."""
+        self._require_sampler("set_pag")
+        self._write_pag(*self._check_pag((scale, layers, adaptive), "set_pag"))
 
     def _check_freeu(self, values, who):
         """(s1, s2, b1, b2) checked against the compiled model before anything changes: None when not given, else the 4 fp32 words."""
@@ -739,7 +815,8 @@ class StableDiffusion:
             if embeds.dtype == np.uint8:
                 dev = self._ip_rows_from_images(embeds, b, ad.embed_dim)
             else:
-                dev = DeviceArray.from_numpy(np.concatenate([np.zeros_like(embeds)] * (self._groups - 1) + [embeds]), _step_dtype(), "row")
+                cg = self._cond_groups()
+                dev = DeviceArray.from_numpy(np.concatenate([np.zeros_like(embeds)] * (self._groups - cg) + [embeds] * cg), _step_dtype(), "row")
             tokens = ad.tokens(dev)
             kv = ad.context_kv(tokens)
             assert kv.shape == self._ip_kv.shape and kv.dtype == self._ip_kv.dtype, (kv.shape, self._ip_kv.shape)
@@ -760,10 +837,11 @@ class StableDiffusion:
         emb = self._clip_vision(images)
         per = e * emb.dtype.itemsize
         dev = DeviceArray.empty((self._groups * b, e), emb.dtype, "row")
-        lead = (self._groups - 1) * b
+        lead = (self._groups - self._cond_groups()) * b
         if lead:
             hip.tf_memset_async(dev.ptr, 0, lead * per, _sh())
-        hip.tf_memcpy_async(dev.ptr + lead * per, emb.ptr, b * per, 3, _sh())
+        for g in range(self._cond_groups()):                               # (pag=True: the perturbed group reads the image prompt too)
+            hip.tf_memcpy_async(dev.ptr + (lead + g * b) * per, emb.ptr, b * per, 3, _sh())
         self._ip_tower_keep = (images, emb)
         return dev
 
@@ -968,7 +1046,7 @@ class StableDiffusion:
 
     def _guidance(self, guidance, what):
         """The guidance scale of ``run`` / ``step_sampler`` as a float; a model compiled with cfg=False takes None or 1.0 only."""
-        if self._groups != 1:
+        if self._cfg:
             if guidance is None:
                 raise TypeError(f"StableDiffusion.{what}: a model compiled with cfg=True needs its guidance scale")
             return float(guidance)
@@ -988,9 +1066,15 @@ class StableDiffusion:
         if not 0 <= i < n:
             raise IndexError(f"StableDiffusion.step_sampler: step {i} outside the schedule's {n} steps")
         t = sched.timesteps[i]
-        self._advance(t, eager, lambda dst, src, nbytes: hip.tf_set_sampler_params(
-            self._params.dev.ptr, float(t), float(sched.alphas[i]), float(sched.alphas_prev[i]), guidance, i, self._seed[0], self._seed[1],
-            self._image_offset, dst, src, nbytes, _sh()))
+        word, edit = (guidance, None) if not self._pag else inputs.pag_guidance_words(guidance, inputs.pag_scale_at(*self._pag_scale, t), self._cfg)
+
+        def set_params(dst, src, nbytes):
+            if edit is not None and edit != self._pag_edit_g:            # pag=True with CFG: g_I = g, written when the CFG scale changes, not per step
+                hip.tf_set_step_params(self._edit.ptr, edit, 0.0, 0.0, 0.0, _sh())
+                self._pag_edit_g = edit
+            hip.tf_set_sampler_params(self._params.dev.ptr, float(t), float(sched.alphas[i]), float(sched.alphas_prev[i]), word, i, self._seed[0], self._seed[1],
+                                      self._image_offset, dst, src, nbytes, _sh())
+        self._advance(t, eager, set_params)
         self._cursor = i + 1
 
     def run(self, guidance=None, eager=False):
@@ -1051,7 +1135,7 @@ class StableDiffusion:
         ``context`` alone: ``unconditional_context`` may be None."""
         self._require_compiled("set_context")
         with use_stream(self._stream):
-            new = self._stack_context(unconditional_context, context, self._groups)       # (in the step's 16-bit type)
+            new = self._stack_context(unconditional_context, context, self._groups, self._cond_groups())       # (in the step's 16-bit type)
             assert new.nbytes == self._ctx2.nbytes, "set_context: the contexts must have the shape the step was compiled for"
             hip.tf_memcpy_async(self._ctx2.ptr, new.ptr, new.nbytes, 3, _sh())
             self._ctx_tmp = new                                    # (referenced until the copy has run)

@@ -15,7 +15,8 @@ Step-level batching that the reference does not do (results unchanged):
 The encoder half (block plan, batched projections, the walk over input_blocks and middle_block) lives in ``encoder_plan`` / ``StepModel``: a
 ControlNet (vision/controlnet.py) is a second copy of it, and ``UNetModel.__call__(control=...)`` takes its residuals in (``control_add``).
 ``UNetModel.__call__(freeu=...)`` is FreeU in front of the concats of the first two decoder stages (``freeu_stages``, ``freeu_skips``,
-``freeu_backbone``).
+``freeu_backbone``).  ``UNetModel.__call__(pag=...)`` is perturbed-attention guidance: one batch range of every selected SpatialTransformer's
+self-attention takes the identity (``pag_layers``; attention/sdpa.py::sdpa_pag_strided).
 """
 import ctypes
 from dataclasses import dataclass, replace
@@ -205,8 +206,10 @@ class StepModel:
             kv_all = self.context_kv(context)                                         # every attn2's K|V of the context
         return emb, emb_all, kv_all, br
 
-    def _runner(self, emb, emb_all, kv_all, context, ip=None):
+    def _runner(self, emb, emb_all, kv_all, context, ip=None, pag=None):
         bt = self._prepare()
+        # pag = (flags, (b0, b1)): the device fp32 array with one word per SpatialTransformer in execution order, and the perturbed batch range
+        pag_idx = {id(st): i for i, st in enumerate(self._all(SpatialTransformer))} if pag is not None else None
         # ip = (kv_ip_all (b, T, kv_n), {id(SpatialTransformer): (column offset, scale index)}, kv_n, scales): an IP-Adapter's image-token K|V
         # for every cross-attention and the device fp32 array of their strengths (UNetModel.__call__(ip=))
 
@@ -227,7 +230,8 @@ class StepModel:
                 if ip is not None:
                     off, idx = ip[1][id(bb)]
                     bip = (KVSlice(ip[0], off, c, ip[2]), ip[3].ptr + 4 * idx)
-                return bb(x, context, kv=KVSlice(kv_all, bt["kv_off"][id(bb)], c, bt["kv_n"]), out_gn=gn, out_norm=on, ip=bip)
+                bpag = (pag[0].ptr + 4 * pag_idx[id(bb)], pag[1]) if pag is not None else None
+                return bb(x, context, kv=KVSlice(kv_all, bt["kv_off"][id(bb)], c, bt["kv_n"]), out_gn=gn, out_norm=on, ip=bip, pag=bpag)
             if isinstance(bb, (Downsample, Upsample)):
                 return bb(x, out_gn=gn, out_norm=on)
             if isinstance(bb, Conv2d):
@@ -284,6 +288,30 @@ def control_add(skips, residuals, scales):
         outs.append(o)
     hip.tf_control_add_16(dtag(skips[0].dtype), ctypes.cast(table, ctypes.c_void_p), len(skips), scales.ptr, _sh())
     return outs
+
+
+PAG_WORDS = 16        # the flag array of perturbed-attention guidance: one fp32 word per SpatialTransformer, one 64-byte write
+
+
+def pag_layers(cfg):
+    """The LDM paths of the UNet's SpatialTransformers in execution order -- input blocks, middle block, output blocks: the order of the flag words of
+    ``UNetModel.__call__(pag=)``.  SD-1.5: input_blocks 1, 2, 4, 5, 7, 8 (words 0-5), middle_block (6), output_blocks 3 .. 11 (7-15).  From the channel
+    plan alone (encoder_plan's and UNetModel's walk), so that the layer names of ``set_pag`` are checked without a model."""
+    nlev, paths, i = len(cfg.channel_mult), [], 1
+    for lev in range(nlev):
+        for _ in range(cfg.num_res_blocks):
+            if lev in cfg.attention_levels:
+                paths.append(f"input_blocks.{i}")
+            i += 1
+        i += lev != nlev - 1                          # the Downsample block
+    paths.append("middle_block")
+    i = 0
+    for lev in reversed(range(nlev)):
+        for _ in range(cfg.num_res_blocks + 1):
+            if lev in cfg.attention_levels:
+                paths.append(f"output_blocks.{i}")
+            i += 1
+    return paths
 
 
 def freeu_stages(cfg):
@@ -367,7 +395,7 @@ class UNetModel(StepModel):
             raise ValueError("UNetModel.ip_slots: the adapter was built for another UNet")
         return {id(st): (offs[k], k) for k, (_, _, st) in enumerate(paths)}
 
-    def __call__(self, x, timesteps=None, context=None, shared=None, control=None, ip=None, freeu=None):
+    def __call__(self, x, timesteps=None, context=None, shared=None, control=None, ip=None, freeu=None, pag=None):
         """control = (residuals, scales): a ControlNet's len(input_blocks) + 1 residual tensors (or a callable that returns them, called behind
         the middle block) and the device fp32 array of their strengths.  Behind the middle block one launch (control_add) makes new skip tensors
         and a new middle output, skip_i + s_i residual_i, which carry no statistics: the output path's concat GroupNorms then compute theirs
@@ -378,7 +406,11 @@ class UNetModel(StepModel):
         encoder -- and behind control_add, so the filter reads the skip as the concat would have read it -- one launch (``freeu_skips``) replaces
         their 2n skip tensors, and in front of each of those blocks one launch (``freeu_backbone``) scales the first half of x's channels.  What
         FreeU makes carries no statistics: those 2n concat GroupNorms compute theirs, the producers of what enters them are not asked for concat
-        statistics, and the later blocks keep their apply-only concats.  None: the step as it always was, launch for launch."""
+        statistics, and the later blocks keep their apply-only concats.  None: the step as it always was, launch for launch.
+        pag = (flags, (b0, b1)): perturbed-attention guidance -- flags a device fp32 array of PAG_WORDS words, one per SpatialTransformer in
+        ``pag_layers`` order; the rows [b0, b1) of x are the perturbed guidance group: in every SpatialTransformer whose word is not zero their
+        self-attention is the identity, attn1(x) = to_out(to_v(norm1(x))), inside the one attention launch (tf_sdpa_pag_16 in place of tf_sdpa_16).
+        The words are read when the kernels run.  None: the plain launches."""
         emb, emb_all, kv_all, br = self._shared(timesteps, context, shared)
         fu = freeu_stages(self.cfg) if freeu is not None else []
         if ip is not None:
@@ -386,7 +418,13 @@ class UNetModel(StepModel):
             if kv_ip.shape[0] != x.shape[0] or kv_ip.shape[2] != adapter.kv_layout()[1] or scales.dtype != np.float32 or scales.size < len(adapter.paths):
                 raise ValueError(f"UNetModel: ip K|V {kv_ip.shape} / scales {scales.shape} do not fit a batch of {x.shape[0]} and {len(adapter.paths)} cross-attentions")
             ip = (kv_ip, self.ip_slots(adapter), adapter.kv_layout()[1], scales)
-        run = self._runner(emb, emb_all, kv_all, context, ip)
+        if pag is not None:
+            flags, (b0, b1) = pag
+            n_st = len(self._all(SpatialTransformer))
+            if flags.dtype != np.float32 or flags.size < n_st or n_st > PAG_WORDS or not 0 <= b0 <= b1 <= x.shape[0]:
+                raise ValueError(f"UNetModel: pag flags {flags} / batch range [{b0}, {b1}) do not fit {n_st} SpatialTransformers (at most {PAG_WORDS}) and a batch of {x.shape[0]}")
+            pag = (flags, (int(b0), int(b1)))
+        run = self._runner(emb, emb_all, kv_all, context, ip, pag)
         x, saved_inputs = self._encode(run, x, br, concat_stats=control is None, replaced=len(fu))
         if control is not None:
             residuals, scales = control

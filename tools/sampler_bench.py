@@ -3,7 +3,7 @@
 tf_cfg_sampler_step_f32) against the DDIM step (tf_cfg_ddim_step_f32), 100 graph replays each, alternated over several rounds; and the
 config-3 end-to-end img/s (CLIP x2 -> steps -> VAE decode, batch 1) at 20 DPM++2M steps against 50 DDIM steps.
 
-    python tools/sampler_bench.py [--replays 100] [--rounds 5] [--images 3] [--dpm-steps 20] [--inpaint] [--concat inpaint|edit] [--control] [--lora] [--lcm] [--ip-adapter] [--freeu]
+    python tools/sampler_bench.py [--replays 100] [--rounds 5] [--images 3] [--dpm-steps 20] [--inpaint] [--concat inpaint|edit] [--control] [--lora] [--lcm] [--ip-adapter] [--freeu] [--pag]
 --inpaint adds the masked DPM++2M step (tf_cfg_sampler_step_masked_f32, a model compiled with inpaint=True on the same shape, half the
 latent repainted) to the alternation, and the VAE encoder's time for a 512^2 image (StableDiffusion.encode_image).
 --concat adds the DPM++2M step of a concat-conditioned UNet (SD15_INPAINT: 9 input channels, two CFG groups; SD15_EDIT: 8 input channels, three
@@ -30,6 +30,10 @@ sampler, the VAE decode) against the DPM++2M run.
 1.5, 1.6) and at all ones, next to the plain step of the same rounds with the rounds' spread; the library entries one eager step of each calls
 (step_entries, and which entries differ); and microseconds per launch of tf_freeu_skip_16 on the step's six skip shapes and of
 tf_freeu_backbone_16 on its two backbone shapes; written to profiles/sampler_bench_freeu.json as well.
+--pag adds the perturbed-attention-guidance step (compile(..., pag=True): the same UNet weights, three guidance groups [uncond ; perturbed ; cond], so
+UNet batch 3 instead of 2) to the alternation at scale 3 on the middle block and on every transformer, next to the plain CFG step of the same rounds
+with the rounds' spread, and the library entries one eager step of each calls (the launch count per step); written to
+profiles/sampler_bench_pag.json as well.
 Prints one JSON line."""
 import argparse
 import contextlib
@@ -351,6 +355,7 @@ def main():
     ap.add_argument("--lora", action="store_true", help="also time the LoRA merge (tf_lora_merge_16), the re-capture and the adapted step, for rank 16 and rank 128")
     ap.add_argument("--ip-adapter", action="store_true", help="also time the IP-Adapter step (fused dual attention) against the plain one and against a composed two-launch form")
     ap.add_argument("--freeu", action="store_true", help="also time the FreeU step (compile(..., freeu=True)) at the quoted values and at all ones against the plain one, and count the entries of both steps")
+    ap.add_argument("--pag", action="store_true", help="also time the perturbed-attention-guidance step (compile(..., pag=True), three guidance groups) against the plain CFG one, and count the entries of both steps")
     ap.add_argument("--lcm", action="store_true", help="also time the guidance-free step (cfg=False) against the CFG step for DPM++2M and LCM, and LCM-4 cfg=False end to end")
     args = ap.parse_args()
 
@@ -464,6 +469,14 @@ def main():
             lat_f = m.latent_from_numpy(noise)
             m.compile(unc, ctx, lat_f, sampler=dpm_sched, freeu=True)
             m.start(seed=1234, freeu=vals)
+            few[key] = (m, lat_f, dpm_sched, 7.5)
+    if args.pag:
+        for key, layers in (("dpmpp2m_pag", "mid"), ("dpmpp2m_pag_all", "all")):
+            m = StableDiffusion()
+            update_state(m.model.diffusion_model, state, "")
+            lat_f = m.latent_from_numpy(noise)
+            m.compile(unc, ctx, lat_f, sampler=dpm_sched, pag=True)
+            m.start(seed=1234, pag=(3.0, layers))
             few[key] = (m, lat_f, dpm_sched, 7.5)
     lat0 = T.DeviceArray.from_numpy(noise, np.float32, "row")
     ts, al, ap_ = ddim_sched.timesteps, ddim_sched.alphas, ddim_sched.alphas_prev
@@ -654,6 +667,19 @@ def main():
                                                          if entries["dpmpp2m_freeu"].get(k, 0) != entries["dpmpp2m"].get(k, 0)},
                       **freeu_kernel_bench(T, hip, few["dpmpp2m_freeu"][0], timed, args)})
 
+    if args.pag:
+        spread_ms = lambda k: round(max(step_ms[k]) - min(step_ms[k]), 4)
+        for k in ("dpmpp2m_pag", "dpmpp2m_pag_all"):
+            assert np.isfinite(few[k][1].numpy()).all(), k
+        entries = {k: step_entries(T, m) for k, m in (("dpmpp2m", dpm_m), ("dpmpp2m_pag", few["dpmpp2m_pag"][0]))}
+        extra.update({"dpmpp2m_pag_step_ms": round(med["dpmpp2m_pag"], 4), "dpmpp2m_pag_all_step_ms": round(med["dpmpp2m_pag_all"], 4),
+                      "pag_over_plain": round(med["dpmpp2m_pag"] / med["dpmpp2m"], 4), "pag_all_over_plain": round(med["dpmpp2m_pag_all"] / med["dpmpp2m"], 4),
+                      "pag_round_spread_ms": {k: spread_ms(k) for k in ("dpmpp2m", "dpmpp2m_pag", "dpmpp2m_pag_all")},
+                      "pag_step_entries": {k: sum(v.values()) for k, v in entries.items()},
+                      "step_entries_pag_minus_plain": {k: entries["dpmpp2m_pag"].get(k, 0) - entries["dpmpp2m"].get(k, 0)
+                                                       for k in sorted(set(entries["dpmpp2m"]) | set(entries["dpmpp2m_pag"]))
+                                                       if entries["dpmpp2m_pag"].get(k, 0) != entries["dpmpp2m"].get(k, 0)}})
+
     def e2e(model, steps, sample, uncond=True):
         recs = []
         for n in range(args.images + 1):
@@ -701,6 +727,9 @@ def main():
             f.write(json.dumps(out, indent=1) + "\n")
     if args.freeu:
         with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sampler_bench_freeu.json"), "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+    if args.pag:
+        with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sampler_bench_pag.json"), "w") as f:
             f.write(json.dumps(out, indent=1) + "\n")
     del arena
 
