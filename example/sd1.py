@@ -19,7 +19,10 @@ BASELINE config 3: full 50-step sampler, batch 1, end-to-end img/s.
     python -m example.sd1 --steps 20 --sampler dpmpp2m --pag 3.0 --pag-layers mid   # perturbed-attention guidance next to CFG (with --no-cfg: instead of it)
     python -m example.sd1 --steps 20 --sampler dpmpp2m --ip-adapter ip-adapter_sd15.safetensors --ip-embeds e.npy [--ip-scale 0.6]   # IP-Adapter: an image prompt, as CLIP image embeddings (1, 1024)
     python -m example.sd1 --steps 20 --sampler dpmpp2m --ip-adapter ip-adapter_sd15.safetensors --ip-image x.npy [--clip-vision image_encoder.safetensors]   # ... or as the picture itself, uint8 (224, 224, 3): the CLIP ViT-H tower runs on the device
-With --ckpt the configuration is read off the checkpoint's conv_in (4, 9 or 8 input channels); --concat picks it on synthetic weights.
+    python -m example.sd1 --sd2 --steps 20 --sampler dpmpp2m --prediction v --cfg-rescale 0.7   # Stable Diffusion 2.x: OpenCLIP context, heads of 64, v-prediction, CFG rescale
+    python -m example.sd1 --ckpt v2-1_768-ema-pruned.safetensors --steps 20 --sampler dpmpp2m --prediction v --cfg-rescale 0.7   # ... from a checkpoint (768-v: --prediction v)
+With --ckpt the configuration is read off the checkpoint: its conv_in (4, 9 or 8 input channels), and SD-2.x when the cross-attention keys read a
+1024-wide context; --concat / --sd2 pick it on synthetic weights.  The parameterisation is NOT in the file: --prediction defaults to eps.
 """
 import argparse
 import os
@@ -79,7 +82,20 @@ if __name__ == "__main__":
     ap.add_argument("--pag-layers", default="mid", help="with --pag: the transformers to perturb, comma-separated: down, mid, up, all, LDM paths (input_blocks.4, "
                                                         "middle_block, output_blocks.7) or indices in execution order (default: mid)")
     ap.add_argument("--pag-adaptive", type=float, default=0.0, metavar="A", help="with --pag: the adaptive scale a of s_t = max(0, s - a (1000 - t)) (default 0)")
+    ap.add_argument("--sd2", action="store_true", help="the Stable Diffusion 2.x configuration on synthetic weights (heads of 64, 1024-wide OpenCLIP context); with --ckpt the checkpoint decides")
+    ap.add_argument("--prediction", choices=["eps", "v"], default="eps",
+                    help="what the UNet predicts (needs --sampler for v): the SD-2.x 768-v checkpoints predict v; a checkpoint file does not say, so the default is eps")
+    ap.add_argument("--cfg-rescale", type=float, default=None, metavar="PHI",
+                    help="CFG rescale inside the captured step (needs --sampler and a guidance pair): the factor phi in [0, 1]; 0.7 is the value usually quoted with v-prediction")
     args = ap.parse_args()
+    if (args.prediction == "v" or args.cfg_rescale is not None) and not args.sampler:
+        ap.error("--prediction v and --cfg-rescale need --sampler")
+    if args.cfg_rescale is not None and not 0.0 <= args.cfg_rescale <= 1.0:
+        ap.error(f"--cfg-rescale {args.cfg_rescale}: expected a factor in [0, 1]")
+    if args.cfg_rescale is not None and ((args.no_cfg and args.pag is None) or args.concat == "edit"):
+        ap.error("--cfg-rescale needs a guidance pair or triple (not --no-cfg without --pag, not an InstructPix2Pix checkpoint)")
+    if args.sd2 and (args.concat == "edit" or args.ip_adapter is not None):
+        ap.error("--sd2 has no InstructPix2Pix configuration and no IP-Adapter")
     if args.pag is not None and not args.sampler:
         ap.error("--pag needs --sampler")
     pag_layers = [int(v) if v.lstrip("-").isdigit() else v for v in args.pag_layers.split(",") if v]
@@ -148,11 +164,11 @@ if __name__ == "__main__":
     from tinyfusers_amd.storage.synth import synth_normal, synth_state_dict
     from tinyfusers_amd.variants.sd import StableDiffusion
 
-    from tinyfusers_amd.vision.unet import SD15, SD15_EDIT, SD15_INPAINT
+    from tinyfusers_amd.vision.unet import SD15, SD15_EDIT, SD15_INPAINT, SD21, SD21_INPAINT
 
     t0 = time.time()
     import io, contextlib
-    concat = args.concat
+    concat, sd2 = args.concat, args.sd2
     if args.ckpt:
         from tinyfusers_amd.storage.unpicker import load_checkpoint
         state = load_checkpoint(args.ckpt)                       # memory-mapped; update_state streams tensor by tensor
@@ -162,6 +178,12 @@ if __name__ == "__main__":
         if concat and cin != {"inpaint": 9, "edit": 8}[concat]:
             sys.exit(f"--concat {concat} does not fit this checkpoint, whose conv_in reads {cin} channels")
         concat = {4: None, 9: "inpaint", 8: "edit"}[cin]
+        to_k = state.get("model.diffusion_model.input_blocks.1.1.transformer_blocks.0.attn2.to_k.weight")
+        sd2 = to_k is not None and int(to_k.shape[1]) == 1024      # the cross-attention reads the OpenCLIP ViT-H context: SD-2.x
+        if sd2 and concat == "edit":
+            sys.exit("--ckpt: an 8-channel UNet with a 1024-wide context is not a supported configuration")
+        if sd2 and args.ip_adapter is not None:
+            sys.exit("--ip-adapter on an SD-2.x checkpoint is not supported")
     if concat:
         what = "an inpainting checkpoint (9 input channels)" if concat == "inpaint" else "an InstructPix2Pix checkpoint (8 input channels)"
         if not args.sampler:
@@ -179,15 +201,18 @@ if __name__ == "__main__":
     if (args.cond_mask and concat != "inpaint") or (args.image_guidance is not None and concat != "edit"):
         ap.error("--cond-mask goes with an inpainting checkpoint, --image-guidance with an InstructPix2Pix one")
     T.ensure_init(0)
-    model = StableDiffusion({None: SD15, "inpaint": SD15_INPAINT, "edit": SD15_EDIT}[concat])
+    model = StableDiffusion({None: SD21, "inpaint": SD21_INPAINT}[concat] if sd2 else {None: SD15, "inpaint": SD15_INPAINT, "edit": SD15_EDIT}[concat])
     if not args.ckpt:
-        state = synth_state_dict(param_shapes(model), 0)       # UNet + VAE decoder + CLIP text encoder, by LDM name
+        state = synth_state_dict({k: v for k, v in param_shapes(model).items() if not k.startswith("cond_stage_model.model.")}, 0)   # UNet + VAE decoder + CLIP text encoder, by LDM name
+        if sd2:                                                # the OpenCLIP tower's names are not synth_tensor's: its own seeded weights
+            from tinyfusers_amd.vae.open_clip_text import LDM_PREFIX, synthetic_state
+            state.update(synthetic_state(model.cond_stage_model.cfg, 0, LDM_PREFIX))
     with contextlib.redirect_stdout(io.StringIO()):
         update_state(model, state, "")
     del state
     if args.control_image:
         from tinyfusers_amd.vision.controlnet import ControlNet
-        net = ControlNet(SD15)
+        net = ControlNet(SD21 if sd2 else SD15)
         if args.control_ckpt:
             from tinyfusers_amd.storage.unpicker import load_checkpoint
             cstate = load_checkpoint(args.control_ckpt)
@@ -229,13 +254,16 @@ if __name__ == "__main__":
     if args.vocab:
         from tinyfusers_amd.tokenizer.clip import ClipTokenizer
         tokenizer = ClipTokenizer(args.vocab)
-        prompt, empty = np.array([tokenizer.encode(args.prompt)]), np.array([tokenizer.encode("")])
+        pad = 0 if sd2 else None                               # SD-2.x pads with id 0 behind the end-of-text token
+        prompt, empty = np.array([tokenizer.encode(args.prompt, pad_id=pad)]), np.array([tokenizer.encode("", pad_id=pad)])
     else:
         rng = np.random.default_rng(args.seed)
         n_words = 9
         prompt = np.full((1, 77), 49407, dtype=np.int64); prompt[0, 0] = 49406; prompt[0, 1:1 + n_words] = rng.integers(0, 49406, n_words)
         empty = np.full((1, 77), 49407, dtype=np.int64); empty[0, 0] = 49406
-    text_model = model.cond_stage_model.transformer.text_model
+        if sd2:
+            prompt[0, 2 + n_words:] = 0; empty[0, 2:] = 0
+    text_model = model.cond_stage_model if sd2 else model.cond_stage_model.transformer.text_model
     text_model(prompt)                                           # first call folds the LayerNorms / fuses q|k|v once
     T.hip.tf_stream_sync(None)
     t0 = time.perf_counter()
@@ -316,7 +344,10 @@ if __name__ == "__main__":
         print(f"sampler {schedule.sampler}: {len(schedule.timesteps)} steps, timesteps {schedule.timesteps[0]} .. {schedule.timesteps[-1]}"
               + (f" (strength {strength}{', inpainting' if mask is not None else ''})" if init_image is not None else ""))
         model.compile(unconditional_context, context, latent, sampler=schedule, inpaint=mask is not None, concat=concat, control=bool(args.control_image),
-                      cfg=not args.no_cfg, ip_adapter=args.ip_adapter is not None, freeu=freeu is not None, pag=args.pag is not None)
+                      cfg=not args.no_cfg, ip_adapter=args.ip_adapter is not None, freeu=freeu is not None, pag=args.pag is not None,
+                      prediction=args.prediction, cfg_rescale=args.cfg_rescale is not None)
+        if args.cfg_rescale is not None:
+            model.set_cfg_rescale(args.cfg_rescale)              # one device word: it stays until the next set_cfg_rescale / start(cfg_rescale=)
         if args.pag is not None:
             model.set_pag(args.pag, pag_layers, args.pag_adaptive)   # 16 device words and two host scalars: they stay until the next set_pag / start(pag=)
         if freeu is not None:

@@ -619,6 +619,25 @@ int tf_cfg3_sampler_step_masked_f32(void* latent, const void* eps3, void* x0_his
 int tf_cfg3_sampler_step_masked_bf16(void* latent, const void* eps3, void* x0_hist, const void* step_params, const void* coeffs, int rows, const void* edit_params,
                                      const void* x0_init, const void* mask, int B, int C, int H, int W, tfStream_t s);
 
+/* ---- SD-2.x sampling (variants/sd.py compile(..., prediction="v", cfg_rescale=True)): the closing launch of the captured step stated ONCE, by
+ * `groups` (1, 2 or 3 guidance groups in eps, combined as tf_sampler_step1_* / tf_cfg_sampler_step_* / tf_cfg3_sampler_step_* combine them) and
+ * `flags` -- the update of variants/sd.py:14-25 behind the CFG combine of variants/sd.py:27-46, which know the eps parameterisation alone.
+ *   bit 0  v-prediction (Salimans & Ho 2022; the 768-v checkpoints): the model output is v and x0 = sqrt(a_t) x - sqrt(1-a_t) e replaces
+ *          x0 = (x - sqrt(1-a_t) e) / sqrt(a_t); nothing else changes -- the coefficient rows are in x0 form
+ *   bit 1  the masked blend of tf_cfg_sampler_step_masked_*: x0_init and mask are both set iff the bit is set
+ *   bit 2  CFG rescale (Lin et al. 2023; diffusers' rescale_noise_cfg): per image over its C H W elements f = std(e_t) / std(e), e_t the LAST
+ *          group (the text group of a pair, of pag=True's [perturbed ; cond] and of its [uncond ; perturbed ; cond]), f = 1 where std(e) == 0;
+ *          e' = phi (e f) + (1 - phi) e, and the update runs on e'.  rescale: ONE fp32 word phi on the device, read when the kernel runs, set iff
+ *          the bit is set; needs groups >= 2.  phi == 0 gives the bits of the call without the bit (finite inputs)
+ * edit_params is set iff groups == 3.  Anything else: TF_E_ARG, the message names the entry and the rule; nothing is launched.
+ * flags 0 and 2 launch the kernel instances of the entries above and return their bits.  With bit 2 it is still ONE launch: one block per
+ * image, two-pass statistics (means first, then squared deviations) summed in a fixed order -- no atomics, and image k's result depends on
+ * neither B nor the other images of the launch; an image's statistics are complete before any of its elements is written. */
+int tf_sampler_tail_f32(void* latent, const void* eps, void* x0_hist, const void* step_params, const void* coeffs, int rows, const void* edit_params,
+                        const void* x0_init, const void* mask, const void* rescale, int B, int C, int H, int W, int groups, unsigned flags, tfStream_t s);
+int tf_sampler_tail_bf16(void* latent, const void* eps, void* x0_hist, const void* step_params, const void* coeffs, int rows, const void* edit_params,
+                         const void* x0_init, const void* mask, const void* rescale, int B, int C, int H, int W, int groups, unsigned flags, tfStream_t s);
+
 /* ---- LoRA adapters (csrc/lora.hip; storage/lora.py, variants/sd.py:set_adapters): the reference has no adapters -- its weights come from
  * update_state alone (storage/checkpoint.py).  Every weight is a row matrix (N, Kd) of 16-bit elements: a Linear (out, in), a conv in KRSC
  * storage (K, R S C); an adapter of it is up (N, r) and down (r, Kd). */

@@ -148,6 +148,171 @@ __global__ void __launch_bounds__(EW_BLOCK) k_sampler_step(float* __restrict__ l
   }
 }
 
+// ---- the tail with v-prediction and CFG rescale: k_sampler_step_rescale<T, G>, the kernel behind every tf_sampler_tail_* call that sets bit 0 or
+// bit 2.  The masked blend, the parameterisation and the rescale are RUN-TIME flags (wave-uniform branches), not template parameters: the library's
+// kernel census is capped (tests/test_abi.py) and 2 x 3 instances fit where 2 x 3 x 2 x 2 do not.  Its arithmetic is therefore STATED, operation by
+// operation (contraction off in the kernel body, fmaf where k_sampler_step's instances fuse), as the twelve k_sampler_step instances compile theirs --
+// read off their assembly, the same in all twelve: e = fma(g, e_c - e_u, e_u) (three groups: fma(g_I, e1 - e0, fma(g_T, e2 - e1, e0))),
+// x0 = fma(-s1, e, x) / r, x' = (c_x x) + (c_0 x0) unfused, then fma(c_1, x0_prev, .), fma(c_n, z, .); the known region fma(ra, x0_init, rn z2) and the
+// blend (m x') + ((1 - m) known) unfused -- so that the eps forms at phi = 0 return k_sampler_step's bits.
+// v-prediction (Salimans & Ho 2022; the SD-2.x 768-v checkpoints): e is v and the x0 line alone changes, x0 = fma(-s1, v, r x).
+// ---- CFG rescale (Lin et al. 2023, "Common Diffusion Noise Schedules and Sample Steps are Flawed" 3.4; diffusers'
+// rescale_noise_cfg): the combined output e is pulled back to the standard deviation of the text group e_t -- the LAST guidance group --
+// per image, over its C H W elements:  f = std(e_t) / std(e) (1 where std(e) == 0),  e' = phi (e f) + (1 - phi) e,  and k_sampler_step's
+// update runs on e'.  phi: one fp32 word on the device.
+// ONE block per image, three sweeps over the image's groups (after the first they come out of L2): the sums of (e - p_e), (e_t - p_t) around
+// the pivots p = the image's element 0 (a constant image sums zeros: its mean is exact and its f is 1), then the sums of the squared
+// deviations from those means (two passes: a mean of 8 sigma costs nothing), then the update.  Every sum has ONE order, whatever the launch:
+// thread t adds the elements of the 8-element chunks t, t + 1024, ... of the image's NHWC memory in element order, a wave adds its lanes by
+// the xor butterfly (wave_sum), and every thread adds the 16 wave partials from LDS in wave order.  No atomics; image k's result depends on
+// image k alone -- not on B, not on what else the launch holds, and not on eps' alignment (the 16-byte loads of the chunked sweeps and the
+// element loads they fall back to feed the same additions).
+enum { RS_BLOCK = 1024, RS_WAVES = RS_BLOCK / 64 };
+
+// e of the header comment of k_sampler_step from the groups' elements at one index, in the operations its instances compile to
+template <int G>
+__device__ __forceinline__ float tail_combine(float e0, float e1, float e2, float g, float gi) {
+  if (G == 1) return e0;
+  if (G == 2) return fmaf(g, e1 - e0, e0);
+  return fmaf(gi, e1 - e0, fmaf(g, e2 - e1, e0));
+}
+
+// up to 8 consecutive 16-bit elements at p as floats (those at or behind `left` are not read and come back 0); vec: one 16-byte load
+template <typename T>
+__device__ __forceinline__ void load8(const T* __restrict__ p, long long left, bool vec, float (&out)[8]) {
+  if (vec) {
+    struct alignas(16) Raw { T v[8]; };
+    const Raw raw = *reinterpret_cast<const Raw*>(p);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) out[j] = (float)raw.v[j];
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) out[j] = j < left ? (float)p[j] : 0.f;
+  }
+}
+
+// (a, b) summed over the block in the fixed order above; every thread gets the two sums.  sh: 2 RS_WAVES floats nothing else uses
+__device__ __forceinline__ void block_sum2(float& a, float& b, float* sh) {
+  a = wave_sum(a);
+  b = wave_sum(b);
+  if ((threadIdx.x & 63) == 0) {
+    sh[2 * (threadIdx.x >> 6)] = a;
+    sh[2 * (threadIdx.x >> 6) + 1] = b;
+  }
+  __syncthreads();
+  float sa = 0.f, sb = 0.f;
+#pragma unroll
+  for (int i = 0; i < RS_WAVES; ++i) {
+    sa += sh[2 * i];
+    sb += sh[2 * i + 1];
+  }
+  a = sa;
+  b = sb;
+}
+
+enum { TAIL_VPRED = 1u, TAIL_MASKED = 2u, TAIL_RESCALE = 4u };          // tf_sampler_tail_*'s flags
+
+// flags & TAIL_RESCALE: the grid is B blocks, block b is image b.  Otherwise: any grid, the threads stride over every image's Philox counters as
+// k_sampler_step's do, and `rescale` is not read.
+template <typename T, int G>
+__global__ void __launch_bounds__(RS_BLOCK) k_sampler_step_rescale(float* __restrict__ lat, const T* __restrict__ eps, float* __restrict__ x0h,
+                                                                   const float* __restrict__ params, const float* __restrict__ coeffs, int rows,
+                                                                   const float* __restrict__ edit, const float* __restrict__ x0i,
+                                                                   const float* __restrict__ mask, const float* __restrict__ rescale, int B, int C, int HW,
+                                                                   unsigned flags) {
+#pragma clang fp contract(off)
+  __shared__ float sh[2][2 * RS_WAVES];
+  const bool vpred = flags & TAIL_VPRED, masked = flags & TAIL_MASKED, resc = (flags & TAIL_RESCALE) && G >= 2;
+  const u32* w = reinterpret_cast<const u32*>(params);
+  const float a_t = params[1], a_s = params[2];
+  const float g = G >= 2 ? params[3] : 0.f, gi = G == 3 ? edit[0] : 0.f;
+  u32 row = w[4];
+  if (row >= (u32)rows) row = (u32)rows - 1;                     // memory safety only: the host entry writes a row of the schedule
+  const u32 k0 = w[5], k1 = w[6], image0 = w[7];
+  const float cx = coeffs[4 * row], c0 = coeffs[4 * row + 1], c1 = coeffs[4 * row + 2], cn = coeffs[4 * row + 3];
+  const float s1 = sqrtf(1.0f - a_t), r = sqrtf(a_t);
+  const float ra = sqrtf(a_s), rn = sqrtf(1.0f - a_s);
+  const long long n_img = (long long)C * HW, n = n_img * B, nq = (n_img + 3) >> 2, nchunk = (n_img + 7) >> 3;
+  float phi = 0.f, f = 1.0f;
+  if (resc) {
+    phi = rescale[0];
+    const T* g0 = eps + (long long)blockIdx.x * n_img;           // this image in group 0; group k is n elements further
+    const bool vec = (n_img & 7) == 0 && ((uintptr_t)eps & 15) == 0;
+    // sweep 1: the means, around the pivots
+    const float pt = (float)g0[(G - 1) * n];
+    const float pe = tail_combine<G>((float)g0[0], (float)g0[G >= 2 ? n : 0], G == 3 ? (float)g0[2 * n] : 0.f, g, gi);
+    float se = 0.f, st = 0.f;
+    for (long long ch = threadIdx.x; ch < nchunk; ch += RS_BLOCK) {
+      const long long left = n_img - 8 * ch;
+      float v0[8], v1[8], v2[8];
+      load8(g0 + 8 * ch, left, vec, v0);
+      load8(g0 + (G >= 2 ? n : 0) + 8 * ch, left, vec, v1);
+      if (G == 3) load8(g0 + 2 * n + 8 * ch, left, vec, v2);
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (j < left) {
+          se += tail_combine<G>(v0[j], v1[j], G == 3 ? v2[j] : 0.f, g, gi) - pe;
+          st += (G == 3 ? v2[j] : v1[j]) - pt;
+        }
+    }
+    block_sum2(se, st, sh[0]);
+    const float me = pe + se / (float)n_img, mt = pt + st / (float)n_img;
+    // sweep 2: the squared deviations
+    float qe = 0.f, qt = 0.f;
+    for (long long ch = threadIdx.x; ch < nchunk; ch += RS_BLOCK) {
+      const long long left = n_img - 8 * ch;
+      float v0[8], v1[8], v2[8];
+      load8(g0 + 8 * ch, left, vec, v0);
+      load8(g0 + (G >= 2 ? n : 0) + 8 * ch, left, vec, v1);
+      if (G == 3) load8(g0 + 2 * n + 8 * ch, left, vec, v2);
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (j < left) {
+          const float de = tail_combine<G>(v0[j], v1[j], G == 3 ? v2[j] : 0.f, g, gi) - me;
+          const float dt = (G == 3 ? v2[j] : v1[j]) - mt;
+          qe = fmaf(de, de, qe);
+          qt = fmaf(dt, dt, qt);
+        }
+    }
+    block_sum2(qe, qt, sh[1]);
+    f = qe > 0.f ? sqrtf(qt / qe) : 1.0f;                        // std(e_t) / std(e): the 1 / (n - 1) of both cancels
+  }
+  // the update: k_sampler_step's loop over Philox counters -- this block's image (rescale), or every image's across the grid
+  const long long first = resc ? (long long)threadIdx.x : (long long)blockIdx.x * RS_BLOCK + threadIdx.x;
+  const long long stride = resc ? (long long)RS_BLOCK : (long long)gridDim.x * RS_BLOCK, total = resc ? nq : nq * B;
+  for (long long t = first; t < total; t += stride) {
+    const int b = resc ? (int)blockIdx.x : (int)(t / nq);
+    const long long q = resc ? t : t - (long long)b * nq;
+    float z[4] = {0.f, 0.f, 0.f, 0.f}, z2[4] = {0.f, 0.f, 0.f, 0.f};
+    if (cn != 0.f) normal4(k0, k1, (u32)q, image0 + (u32)b, row, 1u, z);
+    if (masked) normal4(k0, k1, (u32)q, image0 + (u32)b, row, 2u, z2);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const long long e = 4 * q + j;
+      if (e >= n_img) break;
+      const int c = (int)(e / HW), hw = (int)(e - (long long)c * HW);
+      const long long i = (long long)b * n_img + e, je = ((long long)b * HW + hw) * C + c;
+      float ee = tail_combine<G>((float)eps[je], G >= 2 ? (float)eps[n + je] : 0.f, G == 3 ? (float)eps[2 * n + je] : 0.f, g, gi);
+      if (resc) {
+        const float es = ee * f;
+        ee = phi * es + (1.0f - phi) * ee;                       // (two products and a sum: exact at phi = 0 and at phi = 1)
+      }
+      const float x = lat[i];
+      const float x0 = vpred ? fmaf(-s1, ee, r * x) : fmaf(-s1, ee, x) / r;
+      float xn = cx * x + c0 * x0;
+      if (c1 != 0.f) xn = fmaf(c1, x0h[i], xn);
+      if (cn != 0.f) xn = fmaf(cn, z[j], xn);
+      if (masked) {
+        const float m = mask[(long long)b * HW + hw];
+        const float kn = fmaf(ra, x0i[i], rn * z2[j]);
+        xn = m * xn + (1.0f - m) * kn;
+      }
+      lat[i] = xn;
+      x0h[i] = x0;
+    }
+  }
+}
+
 // The head's launch, and the argument rule of each of its four entries in front of it.
 template <typename T>
 static int latent_stack(void* x_out, const void* latent, const void* cond, int B, int C, int Cc, int H, int W, int groups, unsigned drop_bits, tfStream_t s) {
@@ -202,12 +367,26 @@ static int latent_stack1(const char* name, void* x_out, const void* latent, cons
 // are set (part of "bad arguments"); broken_rule: NULL, or the text of the entry's own rule that the arguments break.
 template <typename T>
 static int sampler_step(const char* name, int G, void* latent, const void* eps, void* x0_hist, const void* params, const void* coeffs, int rows, const void* edit,
-                        const void* x0_init, const void* mask, bool own_ptrs, const char* broken_rule, int B, int C, int H, int W, tfStream_t s) {
+                        const void* x0_init, const void* mask, bool own_ptrs, const char* broken_rule, int B, int C, int H, int W, tfStream_t s,
+                        unsigned flags = 0u, const void* rescale = nullptr) {
   TF_REQUIRE(latent && eps && x0_hist && params && coeffs && own_ptrs && rows >= 1 && B > 0 && C > 0 && H > 0 && W > 0, "%s: bad arguments (rows=%d B=%d C=%d H=%d W=%d)",
              name, rows, B, C, H, W);
   TF_REQUIRE(!broken_rule, "%s: bad arguments (%s)", name, broken_rule);
   const long long n_img = (long long)C * H * W;
   TF_REQUIRE(n_img <= (1LL << 32), "%s: %lld elements per image exceed the 2^32 Philox counters of an image", name, n_img);
+  if (flags & (TAIL_VPRED | TAIL_RESCALE)) {                      // (tf_sampler_tail_* alone sets flags)
+    void (*kr)(float*, const T*, float*, const float*, const float*, int, const float*, const float*, const float*, const float*, int, int, int, unsigned) =
+        G == 3 ? k_sampler_step_rescale<T, 3> : G == 2 ? k_sampler_step_rescale<T, 2> : k_sampler_step_rescale<T, 1>;
+    long long grid = B;                                            // rescale: one block per image
+    if (!(flags & TAIL_RESCALE)) {
+      grid = ceil_div_ll(((n_img + 3) >> 2) * B, RS_BLOCK);
+      if (grid > 512) grid = 512;                                  // (ew_grid's cap in threads)
+    }
+    hipLaunchKernelGGL(kr, dim3((unsigned)grid), dim3(RS_BLOCK), 0, tf_hs(s), (float*)latent, (const T*)eps, (float*)x0_hist, (const float*)params, (const float*)coeffs,
+                       rows, (const float*)edit, (const float*)x0_init, (const float*)mask, (const float*)rescale, B, C, H * W, flags);
+    TF_LAUNCH_CHECK();
+    return TF_OK;
+  }
   void (*k)(float*, const T*, float*, const float*, const float*, int, const float*, const float*, const float*, int, int, int) =
       G == 3 ? (mask ? k_sampler_step<T, 3, true> : k_sampler_step<T, 3, false>)
       : G == 2 ? (mask ? k_sampler_step<T, 2, true> : k_sampler_step<T, 2, false>)
@@ -216,6 +395,27 @@ static int sampler_step(const char* name, int G, void* latent, const void* eps, 
                      (const float*)coeffs, rows, (const float*)edit, (const float*)x0_init, (const float*)mask, B, C, H * W);
   TF_LAUNCH_CHECK();
   return TF_OK;
+}
+
+// tf_sampler_tail_*: the one entry that states every form by `groups` and `flags` (bit 0 v-prediction, bit 1 the masked blend, bit 2 CFG
+// rescale); NULL, or the text of the first pointer / flag rule the arguments break
+static inline const char* tail_rule(const void* edit, const void* x0_init, const void* mask, const void* rescale, int groups, unsigned flags) {
+  if (groups < 1 || groups > 3) return "groups is 1, 2 or 3";
+  if (flags & ~(unsigned)(TAIL_VPRED | TAIL_MASKED | TAIL_RESCALE)) return "flags has bits 0 (v-prediction), 1 (masked blend) and 2 (CFG rescale) only";
+  const bool masked = (flags & TAIL_MASKED) != 0, resc = (flags & TAIL_RESCALE) != 0;
+  if ((x0_init != nullptr) != masked || (mask != nullptr) != masked) return "x0_init and mask are both set iff flags bit 1 (the masked blend) is set";
+  if ((edit != nullptr) != (groups == 3)) return "edit_params is set iff groups == 3";
+  if ((rescale != nullptr) != resc) return "rescale is set iff flags bit 2 (CFG rescale) is set";
+  if (resc && groups == 1) return "CFG rescale (flags bit 2) needs a text group next to another one: groups >= 2";
+  return nullptr;
+}
+
+template <typename T>
+static int sampler_tail(const char* name, void* latent, const void* eps, void* x0_hist, const void* params, const void* coeffs, int rows, const void* edit,
+                        const void* x0_init, const void* mask, const void* rescale, int B, int C, int H, int W, int groups, unsigned flags, tfStream_t s) {
+  const char* rule = tail_rule(edit, x0_init, mask, rescale, groups, flags);
+  return sampler_step<T>(name, rule ? 1 : groups, latent, eps, x0_hist, params, coeffs, rows, edit, x0_init, mask, true, rule, B, C, H, W, s, rule ? 0u : flags,
+                         rescale);
 }
 
 // tf_sampler_step1_*: both of x0_init and mask (the masked form) or neither
@@ -352,6 +552,16 @@ int tf_sampler_step1_bf16(void* latent, const void* eps, void* x0_hist, const vo
                           int B, int C, int H, int W, tfStream_t s) {
   return sampler_step<bf16_t>("tf_sampler_step1_bf16", 1, latent, eps, x0_hist, step_params, coeffs, rows, nullptr, x0_init, mask, true, step1_rule(x0_init, mask), B, C,
                               H, W, s);
+}
+
+int tf_sampler_tail_f32(void* latent, const void* eps, void* x0_hist, const void* step_params, const void* coeffs, int rows, const void* edit_params,
+                        const void* x0_init, const void* mask, const void* rescale, int B, int C, int H, int W, int groups, unsigned flags, tfStream_t s) {
+  return sampler_tail<half_t>("tf_sampler_tail_f32", latent, eps, x0_hist, step_params, coeffs, rows, edit_params, x0_init, mask, rescale, B, C, H, W, groups, flags, s);
+}
+
+int tf_sampler_tail_bf16(void* latent, const void* eps, void* x0_hist, const void* step_params, const void* coeffs, int rows, const void* edit_params,
+                         const void* x0_init, const void* mask, const void* rescale, int B, int C, int H, int W, int groups, unsigned flags, tfStream_t s) {
+  return sampler_tail<bf16_t>("tf_sampler_tail_bf16", latent, eps, x0_hist, step_params, coeffs, rows, edit_params, x0_init, mask, rescale, B, C, H, W, groups, flags, s);
 }
 
 }  // extern "C"

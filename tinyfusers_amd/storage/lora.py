@@ -107,7 +107,7 @@ def text_target_paths(text_model):
 def lora_target_paths(sd):
     """kohya name -> the LDM checkpoint path of the module (param_shapes(sd) lists ``<path>.weight``) for every target of a StableDiffusion."""
     paths = {k: "model.diffusion_model." + p for k, p in unet_target_paths(sd.model.diffusion_model).items()}
-    if sd.cond_stage_model is not None:
+    if hasattr(sd.cond_stage_model, "transformer"):          # the SD-1.x CLIP text encoder; the OpenCLIP tower of SD-2.x has no lora_te_* targets
         paths.update({k: "cond_stage_model.transformer.text_model." + p for k, p in text_target_paths(sd.cond_stage_model.transformer.text_model).items()})
     return paths
 

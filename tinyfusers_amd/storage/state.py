@@ -30,7 +30,8 @@ def _children(node):
 def _slots(root, prefix=""):
     """Yield (dotted name, owner dict, key, current value, module) for every ``weight`` / ``bias`` slot below ``root``.  Private
     attributes (``_x``), scalars and arrays that are not such leaves are not descended into; ``module`` is the object the slot
-    belongs to (``param_shapes`` reads the shape off it)."""
+    belongs to (``param_shapes`` reads the shape off it).  A module whose checkpoint tensors carry other names (OpenCLIP's bare
+    ``positional_embedding``, its fused ``in_proj_weight`` / ``in_proj_bias``) declares them in ``_state_leaves``: {attribute: logical shape}."""
     # Depth first, siblings in declaration order.  Only CYCLES are cut (a public back-reference: a module holding its parent, a compiled graph
     # reachable from the root): a node is skipped when it is one of its own ancestors on the current path.  A module reachable under two names
     # (shared between two parents) is walked under BOTH, so update_state fills it from either key and param_shapes lists both names, as the
@@ -41,7 +42,7 @@ def _slots(root, prefix=""):
         path = path | {id(node)}
         for name, child, owner in _children(node):
             dotted = f"{pre}.{name}" if pre else name
-            if name in _LEAVES and owner is not None:
+            if (name in _LEAVES or name in getattr(node, "_state_leaves", ())) and owner is not None:
                 yield dotted, owner, name, child, node
             elif name.startswith("_") or child is None or isinstance(child, _OPAQUE):
                 continue
@@ -60,14 +61,18 @@ def update_state(obj, state_dict, prefix=''):
     """Install ``state_dict[name]`` into every weight / bias slot below ``obj`` (storage/state.py:4-23: same names, same
     ``skipped: <name>`` line for a key the checkpoint lacks -- except the bias probes of the bias-free q / k / v projections,
     which the reference prints on every load)."""
-    for name, owner, key, cur, _ in _slots(obj, prefix):
+    from ..vision.conv2d import Conv2d
+    for name, owner, key, cur, module in _slots(obj, prefix):
         if name not in state_dict:
             if cur is not None or not name.endswith((".to_q.bias", ".to_k.bias", ".to_v.bias")):
                 print(f"skipped: {name}")
             continue
         from .. import config
         from .tensor import bfloat16
-        owner[key] = asarray(_to_numpy(state_dict[name]), bfloat16 if config.is_bf16() else np.float16)
+        value = _to_numpy(state_dict[name])
+        if key == "weight" and isinstance(module, Conv2d) and value.ndim == 2 and tuple(module._shape) == tuple(value.shape) + (1, 1):
+            value = value.reshape(module._shape)       # SD-2.x (use_linear_in_transformer): proj_in / proj_out stored as Linear (O, I) -- the 1x1 conv's bytes
+        owner[key] = asarray(value, bfloat16 if config.is_bf16() else np.float16)
 
 
 def _leaf_shape(module, key):
@@ -76,6 +81,8 @@ def _leaf_shape(module, key):
     from ..ff.layer_norm import LayerNorm
     from ..ff.linear import Linear
     from ..vision.conv2d import Conv2d
+    if key in getattr(module, "_state_leaves", ()):
+        return tuple(module._state_leaves[key])
     if isinstance(module, Linear):
         if key == "weight":
             return (module.out_features, module.in_features)

@@ -86,12 +86,15 @@ class ClipTokenizer:
         self.cache[token] = out
         return out
 
-    def encode(self, text):
-        """-> list of 77 ids: start, at most 75 BPE ids, end-of-text padding (tokenizer/clip.py:68-78)."""
+    def encode(self, text, pad_id=None):
+        """-> list of 77 ids: start, at most 75 BPE ids, end-of-text padding (tokenizer/clip.py:68-78).  ``pad_id``: None pads with the
+        end-of-text id as the SD-1.x text encoder was trained; an id (SD-2.x's OpenCLIP tokenizer: 0) is what follows ONE end-of-text token."""
         text = re.sub(r"\s+", " ", text.strip()).strip().lower()
         ids = []
         for word in self.pat.findall(text):
             word = "".join(self.byte_encoder[b] for b in word.encode("utf-8"))
             ids.extend(self.encoder[s] for s in self.bpe(word).split(" "))
         ids = ids[:_CONTEXT - 2]
-        return [_START_ID] + ids + [_END_ID] * (_CONTEXT - 1 - len(ids))
+        if pad_id is None:
+            return [_START_ID] + ids + [_END_ID] * (_CONTEXT - 1 - len(ids))
+        return [_START_ID] + ids + [_END_ID] + [int(pad_id)] * (_CONTEXT - 2 - len(ids))

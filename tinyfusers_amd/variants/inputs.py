@@ -159,13 +159,41 @@ def ip_embeds(x, batch, width):
     return np.ascontiguousarray(np.broadcast_to(e, (batch, width)))
 
 
+def cfg_rescale_phi(phi, who="set_cfg_rescale"):
+    """CFG rescale's phi as a float in [0, 1], or ValueError."""
+    try:
+        v = float(phi)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if not 0.0 <= v <= 1.0:
+        raise ValueError(f"StableDiffusion.{who}: the CFG rescale factor phi is a float in [0, 1], got {phi!r}")
+    return v
+
+
+DUAL_HEAD_SIZES = (40, 80, 160)     # the head sizes tf_sdpa_dual_16 (an IP-Adapter's cross-attention) has instances for
+
+
 def check_compile(cin, has_control_net, config, latent, sampler, inpaint, concat, control, cfg=True, ip_adapter=False, has_ip_adapter=False,
-                  freeu=False, freeu_plan=(), pag=False, pag_table=()):
+                  freeu=False, freeu_plan=(), pag=False, pag_table=(), prediction="eps", cfg_rescale=False, head_sizes=()):
     """compile()'s refusals, before any device work: ``cin`` the UNet's in_channels, ``config`` the package's config module, ``freeu_plan`` the
     UNet's vision/unet.py::freeu_stages rows (stage, block, backbone channels, skip channels, latent size divisor), ``pag_table`` its
-    vision/unet.py::pag_layers paths."""
+    vision/unet.py::pag_layers paths, ``head_sizes`` its vision/unet.py::head_sizes (read for ip_adapter=True)."""
     def refuse(exc, text):
         raise exc(f"StableDiffusion.compile: {text}")
+    if prediction not in ("eps", "v"):
+        refuse(ValueError, f"prediction= takes 'eps' or 'v', got {prediction!r}")
+    if prediction == "v" or cfg_rescale:
+        what = "prediction='v'" if prediction == "v" else "cfg_rescale=True"
+        if sampler is None:
+            refuse(ValueError, f"{what} needs a sampler schedule (sampler=<Schedule>): the reference-shaped step() keeps its eps-prediction DDIM form")
+        if config.cfg_parallel:
+            refuse(UnsupportedSamplerConfig, f"{what} has no two-chain CFG form (TF_CFG_PARALLEL)")
+    if cfg_rescale:
+        if concat == "edit":
+            refuse(ValueError, "cfg_rescale=True and concat='edit' together are not supported (CFG rescale is defined against ONE text group; the InstructPix2Pix "
+                               "combine has two guidance scales)")
+        if not cfg and not pag:
+            refuse(ValueError, "cfg_rescale=True needs a guidance pair or triple to rescale against: cfg=True, or pag=True (cfg=False alone has one group and no guidance)")
     if pag:
         if sampler is None:
             refuse(ValueError, "pag=True needs a sampler schedule (sampler=<Schedule>)")
@@ -200,6 +228,10 @@ def check_compile(cin, has_control_net, config, latent, sampler, inpaint, concat
             refuse(UnsupportedSamplerConfig, "an adapted model has no two-chain CFG form (TF_CFG_PARALLEL)")
         if config.dtype == "fp8":
             refuse(UnsupportedSamplerConfig, "ip_adapter=True runs in the fp16 and the bf16 step, not under the fp8 policy (config.set_dtype('fp8'))")
+        bad = [hs for hs in head_sizes if hs not in DUAL_HEAD_SIZES]
+        if bad:
+            refuse(UnsupportedSamplerConfig, f"ip_adapter=True: this UNet's cross-attentions have head size {bad[0]}, the dual launch (tf_sdpa_dual_16) has "
+                                             f"instances for {', '.join(str(v) for v in DUAL_HEAD_SIZES)} (SD-1.x); an IP-Adapter on SD-2.x is not supported")
     if not cfg:
         if sampler is None:
             refuse(ValueError, "cfg=False needs a sampler schedule (sampler=<Schedule>): the reference-shaped step() keeps its CFG form")

@@ -37,7 +37,7 @@ import numpy as np
 from .. import config
 from ..native import hip
 from ..storage.tensor import Branch, DeviceArray, Stream, _sh, asarray, bfloat16, dtag, pool, use_stream
-from ..vision.unet import SD15, SD15_EDIT, SD15_INPAINT, StepParams, UNetModel, freeu_stages, pag_layers
+from ..vision.unet import SD15, SD15_EDIT, SD15_INPAINT, SD21, SD21_INPAINT, StepParams, UNetModel, freeu_stages, head_sizes, pag_layers
 from . import inputs
 from .samplers import UnsupportedSamplerConfig, get_alphas_cumprod  # noqa: F401  (get_alphas_cumprod: variants/sd.py:61-65, re-exported)
 
@@ -69,12 +69,16 @@ class StableDiffusion:
         self.model = namedtuple("DiffusionModel", ["diffusion_model"])(diffusion_model=UNetModel(cfg, init=init))
         from ..vae.vae import AutoencoderKL
         sd15 = any(cfg is c for c in (SD15, SD15_INPAINT, SD15_EDIT))        # the three SD-1.5 checkpoints share the VAE and the text encoder
-        self.first_stage_model = AutoencoderKL(init=init, init_encoder=False) if sd15 else None   # text-to-image uses the decode side only: the encoder stays an empty tree until update_state fills it (encode_image needs it)
+        sd21 = any(cfg is c for c in (SD21, SD21_INPAINT))                   # SD-2.x: the same VAE (architecture and 0.18215), the OpenCLIP ViT-H text tower
+        self.first_stage_model = AutoencoderKL(init=init, init_encoder=False) if sd15 or sd21 else None   # text-to-image uses the decode side only: the encoder stays an empty tree until update_state fills it (encode_image needs it)
         self.cond_stage_model = None
         if sd15:                         # variants/sd.py:12: cond_stage_model.transformer.text_model
             from ..vae.encoder import CLIPTextTransformer
             self.cond_stage_model = namedtuple("CondStageModel", ["transformer"])(
                 transformer=namedtuple("Transformer", ["text_model"])(text_model=CLIPTextTransformer(init=init)))
+        if sd21:                         # an LDM v2 checkpoint's cond_stage_model.model.* (vae/open_clip_text.py); built empty: update_state fills it
+            from ..vae.open_clip_text import OpenClipText
+            self.cond_stage_model = OpenClipText()
         self.control_model = None        # a ControlNet (vision/controlnet.py), under the LDM checkpoint's name: attach_control sets it
         self._ip_model = None            # an IPAdapter (storage/ip_adapter.py): attach_ip_adapter sets it (private: no checkpoint of the model names it)
         self._clip_vision = None         # a ClipVision (vae/clip_vision.py): attach_clip_vision sets it; start(ip_image=) runs it
@@ -100,6 +104,7 @@ class StableDiffusion:
         self._cond = self._edit = None           # concat=: the conditioning channels; [0] g_I of the three-branch update
         self._hint_emb = self._control_scales = None                 # control=True
         self._freeu, self._freeu_scales = False, None                # freeu=True: the device fp32 words [s1, s2, b1, b2]
+        self._vpred, self._rescale, self._rescale_phi = False, False, None     # prediction="v"; cfg_rescale=True: the device fp32 word phi (in a 4-word block)
         self._ip, self._ip_model_compiled, self._ip_kv, self._ip_scales, self._ip_keep = False, None, None, None, None     # the adapter the step captured, ip_adapter=True: image-token K|V (G B, T, kv_n), the scales
         self._seed, self._image_offset, self._cursor = (0, 0), 0, 0  # what start() sets, step_sampler advances
         self._kv_all = self._kv_key = self._ckv_all = self._emb_cur = self._emb_key = self._keep_row = None     # hoisted K|V and time-embedding row
@@ -249,7 +254,7 @@ class StableDiffusion:
         """first_stage_model with a filled encoder, or the RuntimeError ``who`` raises."""
         fsm = self.first_stage_model
         if fsm is None:
-            raise RuntimeError(f"StableDiffusion.{who}: this model has no first_stage_model (SD-1.5 configurations only)")
+            raise RuntimeError(f"StableDiffusion.{who}: this model has no first_stage_model (SD-1.5 and SD-2.x configurations only)")
         enc = fsm.encoder
         if any(m.weight is None for m in (enc.conv_in, enc.conv_out, fsm.quant_conv)):
             raise RuntimeError(f"StableDiffusion.{who}: the VAE encoder has no weights -- it is built empty; fill it with update_state "
@@ -366,7 +371,7 @@ class StableDiffusion:
 
     # -- whole-step HIP graph ------------------------------------------------------------------------
     def compile(self, unconditional_context, context, latent, stream=None, warmup=2, timesteps=None, sampler=None, inpaint=False, concat=None, control=False,
-                cfg=True, ip_adapter=False, freeu=False, pag=False):
+                cfg=True, ip_adapter=False, freeu=False, pag=False, prediction="eps", cfg_rescale=False):
         """Capture one denoising step for these (static) buffers into a HIP graph.  Afterwards
         ``step(timestep, a_t, a_prev, guidance)`` updates ``latent`` in place with one graph launch.
 
@@ -442,18 +447,29 @@ class StableDiffusion:
         ip_adapter=True, freeu=True, LoRA, bf16; not with concat="edit" (a fourth group), TF_CFG_PARALLEL or the fp8 policy.  The UNet's head sizes
         must be among 40, 64, 80, 128 and 160 (the LDS-DMA attention families; SD-1.5: 40, 80, 160).
 
+        ``prediction="v"`` (with a sampler only): the UNet's output is v (Salimans & Ho 2022) as the SD-2.x 768-v checkpoints predict it; the tail's x0
+        line becomes x0 = sqrt(a_t) x - sqrt(1 - a_t) v and nothing else changes (the coefficient tables are in x0 form).  Combines with everything that
+        has a sampler.  ``cfg_rescale=True`` (with a sampler and a guidance pair or triple: cfg=True or pag=True; not concat="edit"): CFG rescale (Lin et
+        al. 2023; diffusers' ``guidance_rescale``) -- per image the combined output is scaled to the standard deviation of the text group's, e' = phi e
+        std(e_t) / std(e) + (1 - phi) e, inside the step's last launch (tf_sampler_tail_*, csrc/sampler.hip: one block per image, two-pass statistics in
+        a fixed order), so the step keeps its number of graph nodes.  The model owns the device word phi, 0.7 after compile (the paper's suggestion, not
+        tuned here); ``set_cfg_rescale`` and ``start(cfg_rescale=)`` change it without a re-capture, and at 0 the step computes the cfg_rescale=False
+        step's bits.  With the defaults the tail is the entry it always was.  Neither runs under TF_CFG_PARALLEL.
+
         The arguments are remembered: ``set_adapters`` (LoRA) on a compiled model swaps weight handles and calls ``compile`` again with the same ones."""
         inputs.check_compile(self.model.diffusion_model.cfg.in_channels, self.control_model is not None, config, latent, sampler, inpaint, concat, control, cfg,
                              ip_adapter=ip_adapter, has_ip_adapter=self._ip_model is not None, freeu=freeu,
                              freeu_plan=freeu_stages(self.model.diffusion_model.cfg) if freeu else (), pag=pag,
-                             pag_table=pag_layers(self.model.diffusion_model.cfg) if pag else ())
+                             pag_table=pag_layers(self.model.diffusion_model.cfg) if pag else (), prediction=prediction, cfg_rescale=cfg_rescale,
+                             head_sizes=head_sizes(self.model.diffusion_model.cfg) if ip_adapter else ())
         if (ip_adapter or pag) and warmup < 1:
             raise ValueError(f"StableDiffusion.compile: {'ip_adapter' if ip_adapter else 'pag'}=True needs warmup >= 1 (the first launch of an attention instance cannot be captured)")
         if sampler is not None:
             timesteps = sampler.timesteps
         self._reset_state()
         self._compile_args = dict(unconditional_context=unconditional_context, context=context, latent=latent, warmup=warmup, timesteps=timesteps,
-                                  sampler=sampler, inpaint=inpaint, concat=concat, control=control, cfg=cfg, ip_adapter=ip_adapter, freeu=freeu, pag=pag)
+                                  sampler=sampler, inpaint=inpaint, concat=concat, control=control, cfg=cfg, ip_adapter=ip_adapter, freeu=freeu, pag=pag,
+                                  prediction=prediction, cfg_rescale=cfg_rescale)
         self._stream = stream or Stream()
         self._latent, self._unc, self._ctx = latent, unconditional_context, context
         self._sched, self._inpaint, self._concat, self._control = sampler, bool(inpaint), concat, bool(control)
@@ -461,6 +477,7 @@ class StableDiffusion:
         self._groups = 3 if concat == "edit" else (2 if cfg else 1) + (1 if pag else 0)
         self._ip = bool(ip_adapter)
         self._freeu = bool(freeu)
+        self._vpred, self._rescale = prediction == "v", bool(cfg_rescale)
         self._ip_model_compiled = self._ip_model if self._ip else None
         if sampler is not None:
             with use_stream(self._stream):
@@ -491,6 +508,8 @@ class StableDiffusion:
             self._control_scales = DeviceArray.from_numpy(np.ones((16,), np.float32), np.float32, "row")     # one per residual; 16: whole 4-word writes
         if self._freeu:
             self._freeu_scales = DeviceArray.from_numpy(np.ones((4,), np.float32), np.float32, "row")      # [s1, s2, b1, b2]: one 4-word write
+        if self._rescale:
+            self._rescale_phi = DeviceArray.from_numpy(np.asarray([0.7, 0.0, 0.0, 0.0], np.float32), np.float32, "row")       # [0] phi: one 4-word write
         if self._pag:
             self._pag_flags = DeviceArray.from_numpy(inputs.pag_layer_words("mid", pag_layers(self.model.diffusion_model.cfg)), np.float32, "row")
         if self._ip:
@@ -601,6 +620,12 @@ class StableDiffusion:
             return hip.tf_cfg_ddim_step2_f32(lat.ptr, out.ptr, out_c.ptr, sp.dev.ptr, b, c, h, w, _sh())
         if self._sched is None:
             return _entry16("tf_cfg_ddim_step", "f32")(lat.ptr, out.ptr, sp.dev.ptr, b, c, h, w, _sh())
+        if self._vpred or self._rescale:          # the one entry that states every form (csrc/sampler.hip): flags bit 0 v, bit 1 masked, bit 2 rescale
+            ptr = lambda a: a.ptr if a is not None else None
+            flags = (1 if self._vpred else 0) | (2 if self._inpaint else 0) | (4 if self._rescale else 0)
+            return _entry16("tf_sampler_tail", "f32")(lat.ptr, out.ptr, self._x0_hist.ptr, sp.dev.ptr, self._coeffs.ptr, len(self._sched.timesteps),
+                                                      self._edit.ptr if self._groups == 3 else None, ptr(self._x0_init), ptr(self._mask), ptr(self._rescale_phi),
+                                                      b, c, h, w, self._groups, flags, _sh())
         if self._groups == 1:
             extra = (self._x0_init.ptr, self._mask.ptr) if self._inpaint else (None, None)
             return _entry16("tf_sampler_step1", "f32")(lat.ptr, out.ptr, self._x0_hist.ptr, sp.dev.ptr, self._coeffs.ptr, len(self._sched.timesteps), *extra, b, c, h, w, _sh())
@@ -668,7 +693,7 @@ class StableDiffusion:
 
     def start(self, seed=None, noise=None, image_offset=0, init_image=None, init_latent=None, mask=None, cond_image=None, cond_mask=None,
               cond_latent=None, image_guidance=None, control_image=None, control_hint=None, control_scale=None, ip_image_embeds=None, ip_image=None,
-              ip_scale=None, freeu=None, pag=None):
+              ip_scale=None, freeu=None, pag=None, cfg_rescale=None):
         """A new image batch for the compiled sampler: sets the latent in place and rewinds the schedule.  ``seed``: the initial latent is
         drawn on the device (tag 0; image b is global image image_offset + b), and the ancestral noise of every step comes from the same seed
         (tag 1); ``noise``: a host (B,C,H,W) array for the initial latent instead (the ancestral noise then uses ``seed``, default 0).
@@ -703,8 +728,12 @@ class StableDiffusion:
         their values.
 
         A PAG model (compile(..., pag=True)): ``pag=(scale, layers)`` or ``(scale, layers, adaptive)`` sets what ``set_pag`` sets; without it they
-        keep their values."""
+        keep their values.
+
+        A rescaled model (compile(..., cfg_rescale=True)): ``cfg_rescale=phi`` writes the word ``set_cfg_rescale`` writes; without it phi keeps its
+        value."""
         self._require_sampler("start")
+        phi = self._check_cfg_rescale(cfg_rescale, "start")
         pg = self._check_pag(pag, "start")
         fu = self._check_freeu(freeu, "start")
         ipa = self._check_ip(ip_image_embeds, ip_image, ip_scale)
@@ -722,7 +751,27 @@ class StableDiffusion:
             self._write_freeu(fu)
         if pg is not None:
             self._write_pag(*pg)
+        if phi is not None:
+            self._write_cfg_rescale(phi)
         return self._latent
+
+    def _check_cfg_rescale(self, phi, who):
+        """phi checked against the compiled model before anything changes: None when not given, else the float in [0, 1]."""
+        if phi is None:
+            return None
+        if not self._rescale:
+            raise ValueError(f"StableDiffusion.{who}: " + ("cfg_rescale= needs" if who == "start" else "needs") + " a model compiled with cfg_rescale=True")
+        return inputs.cfg_rescale_phi(phi, who)
+
+    def _write_cfg_rescale(self, phi):
+        with use_stream(self._stream, ordered=False):                    # stream-ordered: the value travels as a kernel argument
+            hip.tf_set_step_params(self._rescale_phi.ptr, float(phi), 0.0, 0.0, 0.0, _sh())
+
+    def set_cfg_rescale(self, phi=0.7):
+        """CFG rescale's phi from the next step on: 0 <= phi <= 1, checked before anything is written; 0 is the un-rescaled step, 0.7 the paper's
+        suggestion.  The captured step reads the word from the device: nothing is captured again."""
+        self._require_sampler("set_cfg_rescale")
+        self._write_cfg_rescale(self._check_cfg_rescale(phi, "set_cfg_rescale"))
 
     def _check_pag(self, pag, who):
         """(scale, layers[, adaptive]) checked against the compiled model before anything changes: None when not given, else (the 16 fp32 layer
@@ -1163,7 +1212,7 @@ class StableDiffusion:
             raise ValueError(f"StableDiffusion.load_lora: an adapter named {name!r} is loaded already (unload_lora it first, or pass name=)")
         mods, other = L.parse_lora(src)
         shapes = {k: L.weight_shape(m) for k, m in L.lora_targets(self).items()}
-        weights = L.check_lora(mods, other, shapes, strict=strict, bf16=config.is_bf16(), has_text_encoder=self.cond_stage_model is not None)
+        weights = L.check_lora(mods, other, shapes, strict=strict, bf16=config.is_bf16(), has_text_encoder=hasattr(self.cond_stage_model, "transformer"))
         reg.loaded[name] = L.upload(weights, config.is_bf16())
         self._lora = reg
         return name

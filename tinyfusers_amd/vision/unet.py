@@ -20,7 +20,7 @@ self-attention takes the identity (``pag_layers``; attention/sdpa.py::sdpa_pag_s
 """
 import ctypes
 from dataclasses import dataclass, replace
-from typing import Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 
@@ -44,12 +44,32 @@ class UNetConfig:
     attention_levels: Tuple[int, ...] = (0, 1, 2)
     n_heads: int = 8
     context_dim: int = 768
+    d_head: Optional[int] = None      # SD-2.x: a fixed head size, the head count follows the channels (``heads_at``); n_heads is then unused
 
 
 SD15 = UNetConfig()
 SD15_INPAINT = replace(SD15, in_channels=9)   # sd-v1-5-inpainting: [latent(4) | mask(1) | latent of the masked image(4)]
 SD15_EDIT = replace(SD15, in_channels=8)      # InstructPix2Pix: [latent(4) | latent of the image to edit(4)]
 TINY = UNetConfig(model_channels=64, channel_mult=(1, 2, 2), attention_levels=(0, 1), n_heads=2, context_dim=64)
+SD21 = replace(SD15, d_head=64, context_dim=1024)     # Stable Diffusion 2.0 / 2.1 (512-base, 768-v): 5 / 10 / 20 / 20 heads of 64, OpenCLIP ViT-H context
+SD21_INPAINT = replace(SD21, in_channels=9)           # 512-inpainting-ema: SD15_INPAINT's channels
+TINY_V2 = UNetConfig(model_channels=64, channel_mult=(1, 2, 2), attention_levels=(0, 1), d_head=64, context_dim=128)     # 1 / 2 / 2 heads of 64
+
+
+def heads_at(cfg, ch):
+    """(head count, head size) of a SpatialTransformer at ``ch`` channels: cfg.n_heads heads of ch // n_heads (SD-1.x), or -- cfg.d_head set --
+    ch // d_head heads of d_head (SD-2.x).  The one place the encoder plan, the decoder half and the compile checks take them from."""
+    if cfg.d_head is None:
+        return cfg.n_heads, ch // cfg.n_heads
+    if cfg.d_head <= 0 or ch % cfg.d_head:
+        raise ValueError(f"UNetConfig: d_head={cfg.d_head} does not divide the {ch} channels of a SpatialTransformer")
+    return ch // cfg.d_head, cfg.d_head
+
+
+def head_sizes(cfg):
+    """The head sizes of the UNet's SpatialTransformers, one per attention level, from the channel plan alone."""
+    return sorted({heads_at(cfg, cfg.model_channels * cfg.channel_mult[lev])[1] for lev in cfg.attention_levels}
+                  | {heads_at(cfg, cfg.model_channels * cfg.channel_mult[-1])[1]})
 
 
 class Upsample:
@@ -112,9 +132,9 @@ def encoder_plan(cfg, in_channels, init=False):
     """The encoder half of vision/unet.py:12-37 from the channel plan: (time_embed, input_blocks, middle_block, chans) -- chans[i] = the channel
     count input block i saves for the skip concat.  Built once for the UNet and for a ControlNet (vision/controlnet.py), whose trunk is this."""
     mc, emb = cfg.model_channels, cfg.model_channels * 4
-    nh, cd = cfg.n_heads, cfg.context_dim
+    cd = cfg.context_dim
     R = lambda i, o: ResBlock(i, emb, o, init=init)
-    S = lambda c: SpatialTransformer(c, cd, nh, c // nh, init=init)
+    S = lambda c: SpatialTransformer(c, cd, *heads_at(cfg, c), init=init)
     time_embed = [Linear(mc, emb, init=init), Tensor.silu, Linear(emb, emb, init=init)]
     input_blocks = [[Conv2d(in_channels, mc, kernel_size=[3, 3], padding=[1, 1], init=init)]]
     chans, ch, nlev = [mc], mc, len(cfg.channel_mult)
@@ -367,9 +387,9 @@ class UNetModel(StepModel):
     def __init__(self, cfg: UNetConfig = SD15, init=False):
         self.cfg = cfg
         mc, emb = cfg.model_channels, cfg.model_channels * 4
-        nh, cd = cfg.n_heads, cfg.context_dim
+        cd = cfg.context_dim
         R = lambda i, o: ResBlock(i, emb, o, init=init)
-        S = lambda c: SpatialTransformer(c, cd, nh, c // nh, init=init)
+        S = lambda c: SpatialTransformer(c, cd, *heads_at(cfg, c), init=init)
         self.time_embed, self.input_blocks, self.middle_block, chans = encoder_plan(cfg, cfg.in_channels, init)
         ch, nlev = chans[-1], len(cfg.channel_mult)
         self.output_blocks = []

@@ -34,6 +34,9 @@ tf_freeu_backbone_16 on its two backbone shapes; written to profiles/sampler_ben
 UNet batch 3 instead of 2) to the alternation at scale 3 on the middle block and on every transformer, next to the plain CFG step of the same rounds
 with the rounds' spread, and the library entries one eager step of each calls (the launch count per step); written to
 profiles/sampler_bench_pag.json as well.
+--sd2 is a run of its own (nothing above is timed): the SD21 step (heads of 64, 1024-wide context) against the SD15 step at 64x64 in the same
+rounds, the SD21 step at 96x96 for 1 and 4 images, the v-prediction step with and without CFG rescale at both sizes and batches, tf_sampler_tail_*
+alone with bit 2 against without, and the OpenCLIP text tower for two prompts; written to profiles/sampler_bench_sd2.json.
 Prints one JSON line."""
 import argparse
 import contextlib
@@ -343,6 +346,124 @@ def clip_vision_bench(T, hip, model, ip_emb, args):
             "start_ip_image_ms": round(med["start_ip_image"], 3), "start_ip_image_embeds_interleaved_ms": round(med["start_ip_image_embeds"], 3)}
 
 
+def sd2_bench(args):
+    """--sd2: medians of --rounds rounds of --replays graph replays (or launches), every comparison's sides alternating inside the same rounds,
+    the spread between the rounds stated.  Synthetic weights."""
+    import tinyfusers_amd.storage.tensor as T
+    from tinyfusers_amd.native import hip
+    from tinyfusers_amd.storage.state import param_shapes, update_state
+    from tinyfusers_amd.storage.synth import synth_normal, synth_state_dict
+    from tinyfusers_amd.vae import open_clip_text as O
+    from tinyfusers_amd.variants.samplers import DPMSolverPP2M
+    from tinyfusers_amd.variants.sd import StableDiffusion
+    from tinyfusers_amd.vision.unet import SD15, SD21
+
+    T.ensure_init(0)
+    sched = DPMSolverPP2M().schedule(args.dpm_steps)
+    states = {}
+
+    def model(cfg, side, images, **modes):
+        if cfg not in states:
+            states[cfg] = synth_state_dict(param_shapes(StableDiffusion(cfg).model.diffusion_model), 0)
+        m = StableDiffusion(cfg)
+        update_state(m.model.diffusion_model, states[cfg], "")
+        ctx = T.DeviceArray.from_numpy(synth_normal(5, "c", (images, 77, cfg.context_dim)).astype(np.float16))
+        unc = T.DeviceArray.from_numpy(synth_normal(5, "u", (images, 77, cfg.context_dim)).astype(np.float16))
+        lat = m.latent_from_numpy(np.zeros((images, 4, side, side), np.float32))
+        m.compile(unc, ctx, lat, sampler=sched, **modes)
+        m.start(seed=1234)
+        return m, lat
+
+    def timed(stream, fn, n):
+        ev0, ev1, ms = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_float()
+        hip.tf_event_create(ctypes.byref(ev0)); hip.tf_event_create(ctypes.byref(ev1))
+        stream.synchronize()
+        hip.tf_event_record(ev0, stream.handle)
+        fn(n)
+        hip.tf_event_record(ev1, stream.handle)
+        stream.synchronize()
+        hip.tf_event_elapsed_ms(ctypes.byref(ms), ev0, ev1)
+        hip.tf_event_destroy(ev0); hip.tf_event_destroy(ev1)
+        return ms.value / n
+
+    def replays(m, lat):
+        m.synchronize()
+        lat0 = T.DeviceArray.from_numpy(lat.numpy(), np.float32, "row")      # the start latent, put back at the head of every pass over the schedule
+
+        def run(n):
+            for s in range(n):
+                i = s % len(sched.timesteps)
+                if i == 0:
+                    hip.tf_memcpy_async(lat.ptr, lat0.ptr, lat.nbytes, 3, m._stream.handle)
+                m.step_sampler(i, 7.5)
+        return run
+
+    def alternate(arms):
+        """arms: {key: (stream, fn(n))} -> {key: (median ms, spread ms)} of --rounds rounds, the arms alternating inside every round."""
+        for st, fn in arms.values():
+            timed(st, fn, 20)
+        ms = {k: [] for k in arms}
+        for _ in range(args.rounds):
+            for k, (st, fn) in arms.items():
+                ms[k].append(timed(st, fn, args.replays))
+        return {k: (round(float(np.median(v)), 4), round(max(v) - min(v), 4)) for k, v in ms.items()}
+
+    out = {"protocol": f"median of {args.rounds} rounds of {args.replays} replays, (median ms, max - min over the rounds); DPM++2M, CFG pair, synthetic weights"}
+    # 1. SD21 against SD15 at 64 x 64, one image (UNet batch 2); the v step and the rescaled v step in the same rounds
+    for side, images in ((64, 1), (96, 1), (96, 4)):
+        arms = {}
+        for key, cfg, modes in (("sd15", SD15, {}), ("sd21", SD21, {}), ("sd21_v", SD21, dict(prediction="v")), ("sd21_v_rescale", SD21, dict(prediction="v", cfg_rescale=True))):
+            if key == "sd15" and side != 64:
+                continue
+            m, lat = model(cfg, side, images, **modes)
+            arms[key] = (m._stream, replays(m, lat), m, lat)
+        res = alternate({k: v[:2] for k, v in arms.items()})
+        for k, (_, _, m, lat) in arms.items():
+            m.synchronize()
+            assert np.isfinite(lat.numpy()).all(), k
+        out[f"step_ms_{side}x{side}_images{images}"] = res
+        if side == 64:
+            ent = {k: step_entries(T, v[2]) for k, v in arms.items()}
+            out["step_entries"] = {k: sum(v.values()) for k, v in ent.items()}
+        del arms
+    # 2. the tail alone: tf_sampler_tail_f32 with bit 2 against without (flags 1: v), the CFG pair
+    st = T.Stream()
+    with T.use_stream(st):
+        for side in (64, 96):
+            for images in (1, 4):
+                lat, hist = (T.DeviceArray.zeros((images, 4, side, side), np.float32, "row") for _ in range(2))
+                eps = T.DeviceArray.from_numpy(synth_normal(3, "eps", (2 * images, 4, side, side)), np.float16, "nhwc")
+                tab = T.DeviceArray.from_numpy(np.asarray(sched.coeffs, np.float32), np.float32, "row")
+                sp, phi = T.DeviceArray.zeros((8,), np.float32, "row"), T.DeviceArray.from_numpy(np.float32([0.7, 0, 0, 0]), np.float32, "row")
+                hip.tf_set_sampler_params(sp.ptr, 500.0, 0.3, 0.4, 7.5, 3, 1, 2, 0, None, None, 0, T._sh())
+
+                def launches(flags):
+                    def run(n):
+                        for _ in range(n):
+                            hip.tf_sampler_tail_f32(lat.ptr, eps.ptr, hist.ptr, sp.ptr, tab.ptr, len(sched.timesteps), None, None, None, phi.ptr if flags & 4 else None,
+                                                    images, 4, side, side, 2, flags, T._sh())
+                    return run
+                res = alternate({"v": (st, launches(1)), "v_rescale": (st, launches(5))})
+                out[f"tail_us_{side}x{side}_images{images}"] = {k: (round(1e3 * a, 2), round(1e3 * b, 2)) for k, (a, b) in res.items()}
+    # 3. the OpenCLIP tower for two prompts (eager launches, as example/sd1.py runs it)
+    tower = O.OpenClipText.load(O.synthetic_state(O.VIT_H_TEXT, 0))
+    ids = np.zeros((2, 77), np.int64); ids[:, 0] = 49406; ids[0, 1:10] = np.random.default_rng(0).integers(1, 49406, 9); ids[0, 10] = 49407; ids[1, 1] = 49407
+    keep = []
+
+    def towers(n):
+        for _ in range(n):
+            keep.append(tower(ids)); del keep[:-2]
+    with T.use_stream(st):
+        towers(3)
+        a, b = alternate({"open_clip_two_prompts": (st, towers)})["open_clip_two_prompts"]
+    out["open_clip_text_two_prompts_ms"] = (a, b)
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sampler_bench_sd2.json")
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--replays", type=int, default=100)
@@ -357,7 +478,10 @@ def main():
     ap.add_argument("--freeu", action="store_true", help="also time the FreeU step (compile(..., freeu=True)) at the quoted values and at all ones against the plain one, and count the entries of both steps")
     ap.add_argument("--pag", action="store_true", help="also time the perturbed-attention-guidance step (compile(..., pag=True), three guidance groups) against the plain CFG one, and count the entries of both steps")
     ap.add_argument("--lcm", action="store_true", help="also time the guidance-free step (cfg=False) against the CFG step for DPM++2M and LCM, and LCM-4 cfg=False end to end")
+    ap.add_argument("--sd2", action="store_true", help="a run of its own: the SD-2.x step (SD21, v-prediction, CFG rescale), the rescaled tail alone and the OpenCLIP text tower; writes profiles/sampler_bench_sd2.json")
     args = ap.parse_args()
+    if args.sd2:
+        return sd2_bench(args)
 
     import torch  # noqa: F401  (the weight arena is a torch allocation)
     import tinyfusers_amd.storage.tensor as T
