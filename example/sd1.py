@@ -21,6 +21,7 @@ BASELINE config 3: full 50-step sampler, batch 1, end-to-end img/s.
     python -m example.sd1 --steps 20 --sampler dpmpp2m --ip-adapter ip-adapter_sd15.safetensors --ip-image x.npy [--clip-vision image_encoder.safetensors]   # ... or as the picture itself, uint8 (224, 224, 3): the CLIP ViT-H tower runs on the device
     python -m example.sd1 --sd2 --steps 20 --sampler dpmpp2m --prediction v --cfg-rescale 0.7   # Stable Diffusion 2.x: OpenCLIP context, heads of 64, v-prediction, CFG rescale
     python -m example.sd1 --ckpt v2-1_768-ema-pruned.safetensors --steps 20 --sampler dpmpp2m --prediction v --cfg-rescale 0.7   # ... from a checkpoint (768-v: --prediction v)
+    python -m example.sd1 --sdxl --steps 20 --sampler dpmpp2m [--ckpt sd_xl_base_1.0.safetensors] [--size 1024]   # SDXL base: two text towers, pooled / size conditioning
 With --ckpt the configuration is read off the checkpoint: its conv_in (4, 9 or 8 input channels), and SD-2.x when the cross-attention keys read a
 1024-wide context; --concat / --sd2 pick it on synthetic weights.  The parameterisation is NOT in the file: --prediction defaults to eps.
 """
@@ -32,6 +33,88 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+def run_sdxl(ap, args):
+    """--sdxl: text to image on the SDXL base model -- both towers, start(pooled=, original_size=, crop_top_left=, target_size=), the sampler, the VAE
+    at latent_scale 0.13025.  Token ids stand in for the two tokenizers' output when there is no --vocab (both towers read CLIP's BPE; bigG pads with 0)."""
+    import contextlib
+    import io
+    if not args.sampler:
+        ap.error("--sdxl needs --sampler (the time-embedding rows of an SDXL model are built in start())")
+    for flag, name in ((args.concat, "--concat"), (args.control_image, "--control-image"), (args.lora, "--lora"), (args.ip_adapter is not None, "--ip-adapter"),
+                       (args.freeu is not None, "--freeu"), (args.pag is not None, "--pag"), (args.init_image, "--init-image"), (args.sd2, "--sd2")):
+        if flag:
+            ap.error(f"{name} with --sdxl is not supported by this example")
+    if args.size < 64 or args.size % 64:
+        ap.error(f"--size {args.size}: expected a positive multiple of 64")
+    import tinyfusers_amd.storage.tensor as T
+    from tinyfusers_amd.storage.state import param_shapes, update_state
+    from tinyfusers_amd.storage.synth import synth_state_dict
+    from tinyfusers_amd.variants.samplers import make
+    from tinyfusers_amd.variants.sd import StableDiffusion
+    from tinyfusers_amd.vae.open_clip_text import synthetic_state
+    from tinyfusers_amd.vision.unet import SDXL
+    t0 = time.time()
+    T.ensure_init(0)
+    model = StableDiffusion(SDXL)
+    big_g = "conditioner.embedders.1.model."
+    if args.ckpt:
+        from tinyfusers_amd.storage.unpicker import load_checkpoint
+        state = load_checkpoint(args.ckpt)
+        if "model.diffusion_model.label_emb.0.0.weight" not in state:
+            sys.exit("--ckpt: the file holds no model.diffusion_model.label_emb.* tensors -- not an SDXL base checkpoint")
+    else:
+        state = synth_state_dict({k: v for k, v in param_shapes(model).items() if not k.startswith(big_g)}, 0)
+        state.update(synthetic_state(model.conditioner.embedders[1].cfg, 0, big_g, pooled=True))
+    with contextlib.redirect_stdout(io.StringIO()):
+        update_state(model, state, "")
+    del state
+    print(f"weights installed in {time.time() - t0:.1f}s")
+    if args.vocab:
+        from tinyfusers_amd.tokenizer.clip import ClipTokenizer
+        tok = ClipTokenizer(args.vocab)
+        ids = [np.array([tok.encode(p, pad_id=pad)]) for p in (args.prompt, "") for pad in (None, 0)]
+    else:
+        rng = np.random.default_rng(args.seed)
+        prompt = np.full((1, 77), 49407, dtype=np.int64); prompt[0, 0] = 49406; prompt[0, 1:10] = rng.integers(0, 49406, 9)
+        empty = np.full((1, 77), 49407, dtype=np.int64); empty[0, 0] = 49406
+        pg, eg = prompt.copy(), empty.copy()
+        pg[0, 11:] = 0; eg[0, 2:] = 0
+        ids = [prompt, pg, empty, eg]
+    model.encode_prompt(ids[0], ids[1])                          # first call folds the LayerNorms / fuses q|k|v once
+    T.hip.tf_stream_sync(None)
+    t0 = time.perf_counter()
+    context, pooled = model.encode_prompt(ids[0], ids[1])
+    unc, unc_pooled = (None, None) if args.no_cfg else model.encode_prompt(ids[2], ids[3])
+    T.hip.tf_stream_sync(None)
+    print(f"context {context.shape}, pooled {pooled.shape}  ({1e3 * (time.perf_counter() - t0):.2f} ms for both towers" + ("" if args.no_cfg else ", two prompts") + ")")
+    side = args.size // 8
+    latent = model.latent_from_numpy(np.zeros((1, 4, side, side), np.float32))
+    schedule = make(args.sampler, args.eta).schedule(args.steps)
+    model.compile(unc, context, latent, sampler=schedule, cfg=not args.no_cfg, prediction=args.prediction, cfg_rescale=args.cfg_rescale is not None)
+    if args.cfg_rescale is not None:
+        model.set_cfg_rescale(args.cfg_rescale)
+    times = []
+    for n in range(args.images + 1):
+        t0 = time.perf_counter()
+        model.start(seed=args.seed, image_offset=n, pooled=pooled.numpy(), uncond_pooled=None if unc_pooled is None else unc_pooled.numpy(),
+                    original_size=(args.size, args.size), crop_top_left=(0, 0), target_size=(args.size, args.size))
+        model.synchronize()
+        t1 = time.perf_counter()
+        model.run(None if args.no_cfg else args.guidance)
+        model.synchronize()
+        t2 = time.perf_counter()
+        assert np.isfinite(latent.numpy()).all(), f"image {n}: the sampler produced a non-finite latent"
+        with T.use_stream(model._stream):
+            x = model.decode(latent)
+        t3 = time.perf_counter()
+        times.append((t1 - t0, t2 - t1, t3 - t2))
+        print(f"image {n}: start {1e3 * (t1 - t0):.1f} ms, {args.steps} steps {1e3 * (t2 - t1):.1f} ms, decode {1e3 * (t3 - t2):.1f} ms, image {x.shape} mean {x.mean():.1f}")
+    st, s, d = (np.median([t[i] for t in times[1:]]) for i in range(3))
+    print(f"end-to-end (start + sampler + VAE decode, batch 1): {1.0 / (st + s + d):.3f} img/s")
+    if args.out:
+        np.save(args.out, x)
+
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(description="Run the SD-1.x sampler on MI355X (synthetic weights)")
@@ -87,7 +170,13 @@ if __name__ == "__main__":
                     help="what the UNet predicts (needs --sampler for v): the SD-2.x 768-v checkpoints predict v; a checkpoint file does not say, so the default is eps")
     ap.add_argument("--cfg-rescale", type=float, default=None, metavar="PHI",
                     help="CFG rescale inside the captured step (needs --sampler and a guidance pair): the factor phi in [0, 1]; 0.7 is the value usually quoted with v-prediction")
+    ap.add_argument("--sdxl", action="store_true", help="the SDXL base configuration (needs --sampler): two text towers, pooled / size conditioning through start(); "
+                                                         "--ckpt FILE: an SGM checkpoint (sd_xl_base_1.0), synthetic weights without one")
+    ap.add_argument("--size", type=int, default=1024, help="with --sdxl: the image's side in pixels, a multiple of 64 (default 1024)")
     args = ap.parse_args()
+    if args.sdxl:
+        run_sdxl(ap, args)
+        sys.exit(0)
     if (args.prediction == "v" or args.cfg_rescale is not None) and not args.sampler:
         ap.error("--prediction v and --cfg-rescale need --sampler")
     if args.cfg_rescale is not None and not 0.0 <= args.cfg_rescale <= 1.0:

@@ -489,6 +489,10 @@ int tf_ln_fold_weights_16(int dtype, void* w_out, void* bias_out, void* colsum_o
 int tf_linear_ln_16(int dtype, void* y, const void* x, const void* w_folded, const void* bias_folded, const void* colsum_f32, const void* residual,
                     int M, int N, int K, int act, float eps, tfStream_t s);
 int tf_gemv_16(int dtype, void* y, const void* x, const void* w, const void* bias, int M, int N, int K, int silu_input, tfStream_t s);
+/* tf_gemv_16 for 1 <= M <= 65536 rows in ONE launch: the same kernel with one block row per group of 8 input rows, so every output row holds the
+ * bits tf_gemv_16 gives it in a launch of its own group (a whole schedule's time-embedding rows, M = steps x images: the weight is read from HBM
+ * once and from the cache by the other groups).  K a positive multiple of 8; x and w 16-byte aligned */
+int tf_gemv_rows_16(int dtype, void* y, const void* x, const void* w, const void* bias, int M, int N, int K, int silu_input, tfStream_t s);
 int tf_sdpa_16(int dtype, void* o, const void* q, const void* k, const void* v, int B, int NH, int Tq, int Tk, int HS,
                long long q_sb, long long q_sh, long long q_st, long long k_sb, long long k_sh, long long k_st,
                long long v_sb, long long v_sh, long long v_st, long long o_sb, long long o_sh, long long o_st, int causal, tfStream_t s);
@@ -637,6 +641,20 @@ int tf_sampler_tail_f32(void* latent, const void* eps, void* x0_hist, const void
                         const void* x0_init, const void* mask, const void* rescale, int B, int C, int H, int W, int groups, unsigned flags, tfStream_t s);
 int tf_sampler_tail_bf16(void* latent, const void* eps, void* x0_hist, const void* step_params, const void* coeffs, int rows, const void* edit_params,
                          const void* x0_init, const void* mask, const void* rescale, int B, int C, int H, int W, int groups, unsigned flags, tfStream_t s);
+
+/* ---- SDXL vector conditioning (csrc/adm.hip; vision/unet.py, variants/sd.py::start(pooled=)): emb = time_embed(t) + label_emb(y) with
+ * y = [pooled text | Fourier(original h, w, crop top, left, target h, w)].  Everything y-dependent runs in start(), outside the captured step.
+ * dtype tags the 16-bit tensors; arguments are checked before the device is touched (TF_E_ARG, nothing written); plain stores, no atomics. */
+/* out (R, P + 6 D), row r = [pooled[r, :P] | emb(ids[r, 0]) | .. | emb(ids[r, 5])]; emb(t) = [cos(t f_i) | sin(t f_i)], f_i = exp(-ln(max_period) i /
+ * (D / 2)), i < D / 2: tf_timestep_embedding_*'s arithmetic for the scalar t at dim = D -- the same fp32 expression, one rounding -- so the D values
+ * are the bits that entry writes for the timestep t.  pooled (R, P) 16-bit: its bits are copied.  ids (R, 6) fp32 on the device.  D even, >= 2 */
+int tf_adm_vector_16(int dtype, void* out, const void* pooled, const void* ids_f32, int R, int P, int D, float max_period, tfStream_t s);
+/* out (S R, E): out[s R + r, :] = round16(t_emb[s, :] + y_emb[r, :]) -- fp32 add, one rounding; t_emb (S, E), y_emb (R, E).  16-byte loads and
+ * stores: E a positive multiple of 8, every tensor 16-byte aligned */
+int tf_adm_emb_rows_16(int dtype, void* out, const void* t_emb, const void* y_emb, int S, int R, int E, tfStream_t s);
+/* out (B, W) 16-bit: out[b, :] = src[idx[b], :], src (rows, W), idx B int32 ON THE DEVICE (the EOS positions of the pooled text vector:
+ * vae/open_clip_text.py).  Bits are copied.  An index outside [0, rows) gives a row of zeros.  W a positive multiple of 8; out, src 16-byte aligned */
+int tf_gather_rows_16(void* out, const void* src, const void* idx_i32, int B, int W, int rows, tfStream_t s);
 
 /* ---- LoRA adapters (csrc/lora.hip; storage/lora.py, variants/sd.py:set_adapters): the reference has no adapters -- its weights come from
  * update_state alone (storage/checkpoint.py).  Every weight is a row matrix (N, Kd) of 16-bit elements: a Linear (out, in), a conv in KRSC

@@ -200,11 +200,12 @@ class BasicTransformerBlock:
 
 
 class SpatialTransformer:
-    def __init__(self, channels, context_dim, n_heads, d_head, init=True):
+    def __init__(self, channels, context_dim, n_heads, d_head, init=True, depth=1):
+        """depth: the number of BasicTransformerBlocks between proj_in and proj_out (SDXL: 2 and 10); each reads its own K|V of the context."""
         self.norm = GroupNorm(32, channels, init=init)
-        assert channels == n_heads * d_head
+        assert channels == n_heads * d_head and depth >= 1, (channels, n_heads, d_head, depth)
         self.proj_in = Conv2d(channels, n_heads * d_head, kernel_size=[1, 1], init=init)
-        self.transformer_blocks = [BasicTransformerBlock(channels, context_dim, n_heads, d_head, init=init)]
+        self.transformer_blocks = [BasicTransformerBlock(channels, context_dim, n_heads, d_head, init=init) for _ in range(depth)]
         self.proj_out = Conv2d(n_heads * d_head, channels, kernel_size=[1, 1], init=init)
         self._fold = None
 
@@ -225,21 +226,24 @@ class SpatialTransformer:
         return self._fold[1], self._fold[2]
 
     def __call__(self, x, context=None, kv=None, out_gn=0, out_norm=None, ip=None, pag=None):
-        """ip: CrossAttention's (KVSlice, scale_ptr), handed to every block's cross-attention; pag: CrossAttention's (flag_ptr, batch range), handed to
+        """kv: the block's K|V of the context, or one per block (a list; the UNet's step-level projection holds every block's columns).  ip:
+        CrossAttention's (KVSlice, scale_ptr), handed to every block's cross-attention; pag: CrossAttention's (flag_ptr, batch range), handed to
         every block's self-attention."""
         b, c, h, w = x.shape
+        kvs = kv if isinstance(kv, (list, tuple)) else [kv] * len(self.transformer_blocks)
+        assert len(kvs) == len(self.transformer_blocks), (len(kvs), len(self.transformer_blocks))
         x_in = x
         x = self.proj_in(x, gn_in=(self.norm, False))    # GroupNorm -> 1x1 conv (attention.py:66-68) as one launch where the statistics came with x
         x = x.tokens()                                   # (b, hw, c): free re-view of NHWC (attention.py:71)
         if config.fold_proj_out and config.dtype != "fp8" and c % 8 == 0 and self.proj_out.weight.shape[0] == c:   # (fp8: the FeedForward runs in e4m3, proj_out stays fp16)
-            for block in self.transformer_blocks[:-1]:
-                x = block(x, context=context, kv=kv, ip=ip, pag=pag)
-            hid, x2 = self.transformer_blocks[-1](x, context=context, kv=kv, defer_ff2=True, ip=ip, pag=pag)
+            for block, bkv in zip(self.transformer_blocks[:-1], kvs):
+                x = block(x, context=context, kv=bkv, ip=ip, pag=pag)
+            hid, x2 = self.transformer_blocks[-1](x, context=context, kv=kvs[-1], defer_ff2=True, ip=ip, pag=pag)
             wf, bf = self._ff2_proj_out()
             pair = (hid.image(b, hid.shape[-1], h, w), x2.image(b, c, h, w))
             return _conv(pair, wf, bf, [0, 0], [1, 1], [1, 1], residual=x_in, gn=out_gn, out_norm=out_norm)
-        for block in self.transformer_blocks:
-            x = block(x, context=context, kv=kv, ip=ip, pag=pag)
+        for block, bkv in zip(self.transformer_blocks, kvs):
+            x = block(x, context=context, kv=bkv, ip=ip, pag=pag)
         x = x.image(b, c, h, w)                          # attention.py:74
         return self.proj_out(x, residual=x_in, gn=out_gn, out_norm=out_norm)   # + x_in fused (attention.py:75)
 

@@ -57,13 +57,16 @@ __global__ void __launch_bounds__(256) k_pack_weight_fp8(unsigned char* __restri
   }
 }
 
-// ---- weight-streaming GEMV for M <= 8 (time-embedding MLP, ResBlock emb_layers): one wave per output row
+// ---- weight-streaming GEMV for M <= 8 (time-embedding MLP, ResBlock emb_layers): one wave per output row; blockIdx.y: the group of 8 input
+// rows a block serves (tf_gemv_rows_16 -- tf_gemv_16 launches the one group, y = 0)
 template <bool BF = false>
 __global__ void __launch_bounds__(256) k_gemv(half_t* __restrict__ y, const half_t* __restrict__ x, const half_t* __restrict__ w,
                                               const half_t* __restrict__ bias, int M, int N, int K, int silu_in) {
   int wv = threadIdx.x >> 6, l = threadIdx.x & 63;
   int n = blockIdx.x * 4 + wv;
   if (n >= N) return;
+  const int m0 = blockIdx.y * 8;
+  x += (long long)m0 * K; y += (long long)m0 * N; M = min(M - m0, 8);
   const half_t* wr = w + (long long)n * K;
   float acc[8];
 #pragma unroll
@@ -727,6 +730,16 @@ int tf_gemv_16(int dtype, void* y, const void* x, const void* w, const void* bia
 }
 int tf_gemv_f16(void* y, const void* x, const void* w, const void* bias, int M, int N, int K, int silu_input, tfStream_t s) {
   return tf_gemv_16(TF_DTYPE_F16, y, x, w, bias, M, N, K, silu_input, s);
+}
+int tf_gemv_rows_16(int dtype, void* y, const void* x, const void* w, const void* bias, int M, int N, int K, int silu_input, tfStream_t s) {
+  TF_REQUIRE_DTYPE("tf_gemv_rows_16");
+  TF_REQUIRE(y && x && w && M >= 1 && M <= (1 << 16) && N >= 1 && K >= 8 && K % 8 == 0, "tf_gemv_rows_16: needs 1 <= M <= 65536 (M=%d), N >= 1 (N=%d) and K a positive multiple of 8 (K=%d)", M, N, K);
+  TF_REQUIRE((((uintptr_t)x | (uintptr_t)w) & 15) == 0 && ((uintptr_t)y & 1) == 0, "tf_gemv_rows_16: x and w must be 16-byte aligned");
+  const dim3 grid(ceil_div(N, 4), ceil_div(M, 8));
+  if (dtype == TF_DTYPE_BF16) hipLaunchKernelGGL(k_gemv<true>, grid, dim3(256), 0, tf_hs(s), (half_t*)y, (const half_t*)x, (const half_t*)w, (const half_t*)bias, M, N, K, silu_input);
+  else hipLaunchKernelGGL(k_gemv<false>, grid, dim3(256), 0, tf_hs(s), (half_t*)y, (const half_t*)x, (const half_t*)w, (const half_t*)bias, M, N, K, silu_input);
+  TF_LAUNCH_CHECK();
+  return TF_OK;
 }
 
 }  // extern "C"

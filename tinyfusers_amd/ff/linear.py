@@ -13,8 +13,21 @@ def workspace(nbytes):
     return DeviceArray.empty((nbytes,), np.uint8, "row") if nbytes else None
 
 
+class RowSlice:
+    """Columns [off, off + k) of every row of a (rows, ld) array as a conv's per-image bias: image i reads ptr + i * stride elements (the
+    hoisted time-embedding rows of a vector-conditioned UNet, one per image: vision/unet.py::StepModel.time_embedding_all)."""
+    __slots__ = ("ptr", "size", "stride", "_base")
+
+    def __init__(self, arr, off, k):
+        rows, ld = arr.shape
+        assert 0 <= off and off + k <= ld, (arr.shape, off, k)
+        self.ptr, self.size, self.stride, self._base = arr.ptr + off * arr.dtype.itemsize, rows * k, ld, arr
+
+
 def bias_nc_stride(bias_nc, k):
     """Elements between the rows of a per-image bias (n, k) of a conv with k outputs; 0: one row for every image (or no such bias)."""
+    if isinstance(bias_nc, RowSlice):
+        return bias_nc.stride
     return k if bias_nc is not None and bias_nc.size // k > 1 else 0
 
 
@@ -83,6 +96,16 @@ def gemv_f16(x, w, b=None, silu_input=False):
     rows = x.size // K
     y = DeviceArray.empty(x.shape[:-1] + (w.shape[0],), x.dtype, "row")
     hip.tf_gemv_16(dtag(x.dtype), y.ptr, x.ptr, w.ptr, b.ptr if b is not None else None, rows, w.shape[0], K, 1 if silu_input else 0, _sh())
+    return y
+
+
+def gemv_rows(x, w, b=None, silu_input=False):
+    """gemv_f16 for any number of rows in ONE launch (tf_gemv_rows_16: the same kernel over groups of 8 rows, every row's arithmetic the one
+    tf_gemv_16 does): a whole schedule's time-embedding rows through the batched ResBlock projection."""
+    K = x.shape[-1]
+    rows = x.size // K
+    y = DeviceArray.empty(x.shape[:-1] + (w.shape[0],), x.dtype, "row")
+    hip.tf_gemv_rows_16(dtag(x.dtype), y.ptr, x.ptr, w.ptr, b.ptr if b is not None else None, rows, w.shape[0], K, 1 if silu_input else 0, _sh())
     return y
 
 

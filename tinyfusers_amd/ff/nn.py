@@ -112,4 +112,10 @@ class CLIPMLP:
         if self.act == "gelu":
             hip.tf_gelu_erf_16(dtag(h.dtype), h.ptr, h.ptr, h.size, _sh())
             return self.fc2(h, residual=residual)
+        from ..storage.tensor import is_bfloat16
+        if is_bfloat16(h.dtype):
+            # bfloat16 weights (SDXL's CLIP-L under config.set_dtype("bf16")): the quick-GELU kernel is float16's, so the activation hops through
+            # float16 -- two conversions around the one launch; float16 holds bfloat16's mantissa, and fc1's outputs stay far inside its range
+            from .linear import to_bf16, to_f16
+            return self.fc2(to_bf16(Tensor.quick_gelu(to_f16(h))), residual=residual)
         return self.fc2(Tensor.quick_gelu(h), residual=residual)

@@ -10,6 +10,8 @@ from ..attention.attention import CLIPAttention
 from ..ff.embedding import Embedding, embedding
 from ..ff.layer_norm import LayerNorm
 from ..ff.nn import CLIPMLP
+from ..native import hip
+from ..storage.tensor import DeviceArray, _sh, bfloat16, dtag, is_bfloat16
 
 
 ENCODER_WIDTHS = ((128, 128), (128, 256), (256, 512), (512, 512))     # (in, out) channels of encoder level 0 (image resolution) .. 3
@@ -51,11 +53,11 @@ class Encoder:
 
 
 class CLIPEncoderLayer:
-    def __init__(self, init=True):
-        self.self_attn = CLIPAttention(init=init)
-        self.layer_norm1 = LayerNorm(768, init=init)
-        self.mlp = CLIPMLP(init=init)
-        self.layer_norm2 = LayerNorm(768, init=init)
+    def __init__(self, init=True, width=768, heads=12, mlp=3072):
+        self.self_attn = CLIPAttention(init=init, embed_dim=width, num_heads=heads)
+        self.layer_norm1 = LayerNorm(width, init=init)
+        self.mlp = CLIPMLP(init=init, dim=width, hidden=mlp)
+        self.layer_norm2 = LayerNorm(width, init=init)
 
     def __call__(self, hidden_states, causal_attention_mask):
         hidden_states = self.self_attn(hidden_states, causal_attention_mask, residual=hidden_states, ln=self.layer_norm1)
@@ -63,38 +65,58 @@ class CLIPEncoderLayer:
 
 
 class CLIPEncoder:
-    def __init__(self, init=True):
-        self.layers = [CLIPEncoderLayer(init=init) for i in range(12)]
+    def __init__(self, init=True, layers=12, width=768, heads=12, mlp=3072):
+        self.layers = [CLIPEncoderLayer(init=init, width=width, heads=heads, mlp=mlp) for i in range(layers)]
 
-    def __call__(self, hidden_states, causal_attention_mask):
-        for l in self.layers:
+    def __call__(self, hidden_states, causal_attention_mask, layers=None):
+        """layers: run the first ``layers`` layers only (None: all of them)."""
+        for l in self.layers[:layers]:
             hidden_states = l(hidden_states, causal_attention_mask)
         return hidden_states
 
 
 class CLIPTextEmbeddings:
-    def __init__(self, init=True):
-        self.token_embedding = Embedding(49408, 768, init=init)
-        self.position_embedding = Embedding(77, 768, init=init)
+    def __init__(self, init=True, vocab=49408, width=768, positions=77):
+        self.token_embedding = Embedding(vocab, width, init=init)
+        self.position_embedding = Embedding(positions, width, init=init)
 
     def __call__(self, input_ids, position_ids=None):
         """position_ids: None or arange(T) (all the reference passes, vae/encoder.py:78): row i is added to token i."""
         if position_ids is not None:
             p = np.asarray(position_ids).reshape(-1)
             assert (p == np.arange(p.size)).all(), "position_ids must be arange(T)"
-        return embedding(self.token_embedding.weight, input_ids, self.position_embedding.weight)
+        w, pos = self.token_embedding.weight, self.position_embedding.weight
+        if not is_bfloat16(w.dtype):
+            return embedding(w, input_ids, pos)
+        # bfloat16 weights (the SDXL towers under config.set_dtype("bf16")): the gather copies the rows' bits, one tf_add_16 per sequence adds the
+        # positions -- vae/open_clip_text.py::OpenClipText.embeddings' form
+        rows = embedding(w, input_ids)
+        b, t, d = rows.shape
+        x = DeviceArray.empty((b, t, d), bfloat16, "row")
+        for k in range(b):
+            hip.tf_add_16(dtag(bfloat16), x.ptr + k * t * d * 2, rows.ptr + k * t * d * 2, pos.ptr, t * d, _sh())
+        x._base = rows                                                       # (referenced until the adds have run)
+        return x
 
 
 class CLIPTextTransformer:
-    def __init__(self, init=True):
-        self.embeddings = CLIPTextEmbeddings(init=init)
-        self.encoder = CLIPEncoder(init=init)
-        self.final_layer_norm = LayerNorm(768, init=init)
+    """tap = k: the output of encoder layer k (the first k layers run) WITHOUT final_layer_norm -- SDXL reads CLIP-L at k = 11 of 12, transformers'
+    ``hidden_states[-2]``; None: every layer and the final LayerNorm, the SD-1.x context.  The shape arguments default to CLIP ViT-L/14's."""
+
+    def __init__(self, init=True, tap=None, width=768, layers=12, heads=12, mlp=3072, vocab=49408, positions=77):
+        if tap is not None and not 1 <= int(tap) <= layers:
+            raise ValueError(f"CLIPTextTransformer: tap={tap!r} names no encoder layer (1 .. {layers}, or None)")
+        self._tap = None if tap is None else int(tap)
+        self.embeddings = CLIPTextEmbeddings(init=init, vocab=vocab, width=width, positions=positions)
+        self.encoder = CLIPEncoder(init=init, layers=layers, width=width, heads=heads, mlp=mlp)
+        self.final_layer_norm = LayerNorm(width, init=init)
 
     def __call__(self, input_ids):
         """input_ids: (B, T <= 77) integer token ids (host array or int32 DeviceArray) -> (B, T, 768) f16 context."""
         t = input_ids.shape[1]
         x = self.embeddings(input_ids)
         mask = np.triu(np.full((1, 1, t, t), float("-inf"), dtype=np.float32), k=1)       # vae/encoder.py:79
+        if self._tap is not None:
+            return self.encoder(x, mask, layers=self._tap)
         x = self.encoder(x, mask)
         return self.final_layer_norm(x)

@@ -12,7 +12,12 @@ StableDiffusion walks them:
     transformer.resblocks.N.attn.in_proj_weight (3W, W) / in_proj_bias (3W,): q | k | v rows in that order, installed as the fused operand
     transformer.resblocks.N.attn.out_proj, .mlp.c_fc, .mlp.c_proj .weight / .bias           ln_final.weight / .bias
 
-The last resblock, ``text_projection``, ``logit_scale`` and ``attn_mask`` of a checkpoint have no slot here: they are read past and never run."""
+The last resblock, ``text_projection``, ``logit_scale`` and ``attn_mask`` of a checkpoint have no slot here: they are read past and never run.
+
+SDXL's second embedder (LDM's ``FrozenOpenCLIPEmbedder2(layer="penultimate", legacy=False)``, ViT-bigG/14: ``BIG_G_TEXT``) is
+``OpenClipText(cfg, tap="penultimate_raw", pooled=True)``: every resblock runs, the context is the penultimate resblock's output WITHOUT ``ln_final``,
+and the pooled vector is ``ln_final(last)[b, argmax(ids[b])] @ text_projection`` -- the row of the highest token id, OpenCLIP's rule for the
+end-of-text token; ``text_projection`` is a bare (W, W) parameter used un-transposed.  Then the last resblock and ``text_projection`` do have slots."""
 import os
 from dataclasses import dataclass
 
@@ -43,6 +48,17 @@ class OpenClipTextConfig:
 
 
 VIT_H_TEXT = OpenClipTextConfig()
+BIG_G_TEXT = OpenClipTextConfig(width=1280, layers=32, heads=20, mlp=5120)       # OpenCLIP ViT-bigG/14: SDXL's second text tower
+
+
+def pooled_rows(input_ids):
+    """The row of the (B T, W) token matrix the pooled vector is read from, per prompt: b T + argmax(ids[b]) -- the FIRST position of the highest
+    id (numpy's and torch's argmax), which is the end-of-text token wherever it stands, padding behind it or not."""
+    ids = np.asarray(input_ids)
+    if ids.ndim != 2 or ids.dtype.kind not in "iu":
+        raise ValueError(f"OpenClipText: the pooled vector needs (B, T) integer token ids on the host, got {ids.dtype} {ids.shape}")
+    b, t = ids.shape
+    return (np.arange(b) * t + ids.argmax(axis=1)).astype(np.int32)
 
 
 class _Attention(CLIPAttention):
@@ -90,17 +106,20 @@ class _ResBlock:
 
 
 class _Transformer:
-    def __init__(self, cfg):
-        self.resblocks = [_ResBlock(cfg) for _ in range(cfg.layers - 1)]      # penultimate: the last resblock never runs
+    def __init__(self, cfg, every=False):
+        self.resblocks = [_ResBlock(cfg) for _ in range(cfg.layers if every else cfg.layers - 1)]      # penultimate: the last resblock never runs (every: the pooled vector reads it)
 
 
 class _Model:
-    def __init__(self, cfg):
+    def __init__(self, cfg, pooled=False):
         self.token_embedding = Embedding(cfg.vocab, cfg.width, init=False)
         self.positional_embedding = None
         self._state_leaves = {"positional_embedding": (cfg.positions, cfg.width)}
-        self.transformer = _Transformer(cfg)
+        self.transformer = _Transformer(cfg, every=pooled)
         self.ln_final = LayerNorm(cfg.width, eps=cfg.eps, init=False)
+        if pooled:
+            self.text_projection = None
+            self._state_leaves["text_projection"] = (cfg.width, cfg.width)
 
 
 def config_from_state(state, heads=None):
@@ -140,11 +159,16 @@ class OpenClipText:
     """``tower = OpenClipText.load(file | dict)`` (or built empty and filled by update_state under ``cond_stage_model``); ``tower(ids)``: (B, T <= 77)
     token ids, host or int32 device array -> the device (B, T, width) context in the 16-bit type the weights were installed in."""
 
-    def __init__(self, cfg=VIT_H_TEXT):
+    def __init__(self, cfg=VIT_H_TEXT, tap="penultimate", pooled=False):
+        """tap: "penultimate" -- ln_final of the penultimate resblock's output, the SD-2.x context -- or "penultimate_raw", that output itself
+        (SDXL).  pooled=True: ``tower(ids)`` returns (context, pooled (B, W)); the last resblock and text_projection are then part of the tree."""
         if cfg.layers < 2 or cfg.width % cfg.heads or cfg.width % 64 or cfg.width > 2560 or cfg.mlp % 8:
             raise ValueError(f"OpenClipText: unsupported configuration {cfg} (at least 2 layers, width a multiple of 64 and of heads, <= 2560)")
+        if tap not in ("penultimate", "penultimate_raw"):
+            raise ValueError(f"OpenClipText: tap= takes 'penultimate' or 'penultimate_raw', got {tap!r}")
         self.cfg = cfg
-        self.model = _Model(cfg)
+        self._tap, self._pooled, self._proj_t = tap, bool(pooled), None
+        self.model = _Model(cfg, pooled=self._pooled)
 
     @classmethod
     def load(cls, src, heads=None):
@@ -184,23 +208,45 @@ class OpenClipText:
 
     def __call__(self, input_ids):
         t = int(input_ids.shape[1])
+        rows = pooled_rows(input_ids) if self._pooled else None                            # (checked before anything is launched)
         x = self.embeddings(input_ids)
         mask = np.triu(np.full((1, 1, t, t), float("-inf"), dtype=np.float32), k=1)       # the causal mask of vae/encoder.py:79
-        for block in self.model.transformer.resblocks:
+        blocks = self.model.transformer.resblocks
+        for block in blocks[:self.cfg.layers - 1]:
             x = block(x, mask)
-        return self.model.ln_final(x)
+        ctx = self.model.ln_final(x) if self._tap == "penultimate" else x
+        if not self._pooled:
+            return ctx
+        return ctx, self._pool(self.model.ln_final(blocks[-1](x, mask)), rows)
+
+    def _pool(self, last, rows):
+        """ln_final(last)[b, argmax(ids[b])] @ text_projection: one row gather (tf_gather_rows_16; the indices travel as a device int32 array) and one
+        GEMV over the projection transposed once per weight (our Linear computes x W^T)."""
+        b, t, w = last.shape
+        proj = self.model.text_projection
+        if self._proj_t is None or self._proj_t[0] != proj.wkey:
+            pt = DeviceArray.empty((w, w), proj.dtype, "row")
+            hip.tf_nhwc_to_nchw_f16(pt.ptr, proj.ptr, 1, w, 1, w, _sh())                  # (K, N) -> (N, K): a 2-byte transpose, either element type
+            self._proj_t = (proj.wkey, pt)
+        idx = DeviceArray.from_numpy(rows, np.int32, "row")
+        picked = DeviceArray.empty((b, w), last.dtype, "row")
+        hip.tf_gather_rows_16(picked.ptr, last.ptr, idx.ptr, b, w, b * t, _sh())
+        from ..ff.linear import gemv_rows
+        out = gemv_rows(picked, self._proj_t[1])
+        out._base = (out._base, idx, picked, last)                                        # (referenced until the kernels have run)
+        return out
 
 
-def param_shapes(cfg):
+def param_shapes(cfg, pooled=False):
     """name (below ``cond_stage_model.model.``) -> shape of every tensor the tower reads."""
-    return _param_shapes(OpenClipText(cfg).model)
+    return _param_shapes(OpenClipText(cfg, pooled=pooled).model)
 
 
-def synthetic_state(cfg, seed=0, prefix=""):
+def synthetic_state(cfg, seed=0, prefix="", pooled=False):
     """Seeded weights in the checkpoint's names (fp16 values as fp32 arrays), the LAST resblock included as a file has it: what example/sd1.py and
     tools/sampler_bench.py run without a file.  Scaled so that activations stay of order one through the layers."""
     rng = np.random.default_rng(seed)
-    shapes = dict(param_shapes(cfg))
+    shapes = dict(param_shapes(cfg, pooled))
     last = f"transformer.resblocks.{cfg.layers - 1}."
     shapes.update({k.replace("transformer.resblocks.0.", last): s for k, s in list(shapes.items()) if k.startswith("transformer.resblocks.0.")})
     out = {}
@@ -209,6 +255,8 @@ def synthetic_state(cfg, seed=0, prefix=""):
             a = 1.0 + 0.05 * rng.standard_normal(s)
         elif k.endswith(("bias", "positional_embedding", "token_embedding.weight")):
             a = 0.05 * rng.standard_normal(s)
+        elif k == "text_projection":
+            a = rng.standard_normal(s) * (0.7 / np.sqrt(s[0]))
         else:
             a = rng.standard_normal(s) * (0.7 / np.sqrt(s[-1]))
         out[prefix + k] = a.astype(np.float16).astype(np.float32)

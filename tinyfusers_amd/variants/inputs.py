@@ -170,16 +170,66 @@ def cfg_rescale_phi(phi, who="set_cfg_rescale"):
     return v
 
 
+def adm_pooled(x, batch, width, name):
+    """start(pooled= / uncond_pooled=): a host float (B, P) array (or one row for every image) -> fp32 (B, P)."""
+    if isinstance(x, DeviceArray):
+        raise TypeError(f"StableDiffusion.start: {name}= takes a host array")
+    e = np.ascontiguousarray(x, dtype=np.float32)
+    if e.ndim != 2 or e.shape[0] not in (1, batch) or e.shape[1] != width:
+        raise ValueError(f"StableDiffusion.start: {name} must be float {(batch, width)} (or one row for all) for the compiled latent and this UNet, got {e.shape}")
+    if not np.isfinite(e).all():
+        raise ValueError(f"StableDiffusion.start: {name} holds non-finite values")
+    return np.ascontiguousarray(np.broadcast_to(e, (batch, width)))
+
+
+def adm_ids(x, batch, name="uncond_size_ids"):
+    """The six size ids [original h, w, crop top, left, target h, w] per image: a host (B, 6) array (or one row for all) -> fp32 (B, 6), finite and >= 0."""
+    e = np.ascontiguousarray(x, dtype=np.float32)
+    if e.ndim == 1:
+        e = e[None]
+    if e.ndim != 2 or e.shape[0] not in (1, batch) or e.shape[1] != 6:
+        raise ValueError(f"StableDiffusion.start: {name} must be {(batch, 6)} (or one row for all): original h, w, crop top, left, target h, w; got {e.shape}")
+    if not (np.isfinite(e).all() and (e >= 0).all()):
+        raise ValueError(f"StableDiffusion.start: {name} holds negative or non-finite values")
+    return np.ascontiguousarray(np.broadcast_to(e, (batch, 6)))
+
+
+def adm_size_ids(original_size, crop_top_left, target_size, batch, height, width):
+    """start(original_size=, crop_top_left=, target_size=) -> fp32 (B, 6) [original h, w, crop top, left, target h, w]: each an (h, w) pair or a
+    (B, 2) array with a pair per image; None: the image size (height, width), (0, 0) and the image size."""
+    cols = []
+    for name, v, default in (("original_size", original_size, (height, width)), ("crop_top_left", crop_top_left, (0, 0)), ("target_size", target_size, (height, width))):
+        e = np.asarray(default if v is None else v, dtype=np.float32)
+        if e.ndim == 1:
+            e = e[None]
+        if e.ndim != 2 or e.shape[0] not in (1, batch) or e.shape[1] != 2:
+            raise ValueError(f"StableDiffusion.start: {name} takes an (h, w) pair or a {(batch, 2)} array, got shape {np.shape(v)}")
+        cols.append(np.broadcast_to(e, (batch, 2)))
+    return adm_ids(np.concatenate(cols, axis=1), batch, "original_size / crop_top_left / target_size")
+
+
 DUAL_HEAD_SIZES = (40, 80, 160)     # the head sizes tf_sdpa_dual_16 (an IP-Adapter's cross-attention) has instances for
 
 
 def check_compile(cin, has_control_net, config, latent, sampler, inpaint, concat, control, cfg=True, ip_adapter=False, has_ip_adapter=False,
-                  freeu=False, freeu_plan=(), pag=False, pag_table=(), prediction="eps", cfg_rescale=False, head_sizes=()):
+                  freeu=False, freeu_plan=(), pag=False, pag_table=(), prediction="eps", cfg_rescale=False, head_sizes=(), adm=False):
     """compile()'s refusals, before any device work: ``cin`` the UNet's in_channels, ``config`` the package's config module, ``freeu_plan`` the
     UNet's vision/unet.py::freeu_stages rows (stage, block, backbone channels, skip channels, latent size divisor), ``pag_table`` its
-    vision/unet.py::pag_layers paths, ``head_sizes`` its vision/unet.py::head_sizes (read for ip_adapter=True)."""
+    vision/unet.py::pag_layers paths, ``head_sizes`` its vision/unet.py::head_sizes (read for ip_adapter=True), ``adm`` whether the UNet is
+    vector-conditioned (UNetConfig.adm_in_channels: SDXL)."""
     def refuse(exc, text):
         raise exc(f"StableDiffusion.compile: {text}")
+    if adm:      # SDXL runs cfg=True / False, every sampler, img2img, inpaint=True, prediction="v", cfg_rescale=True, bf16; the rest is refused by name
+        if sampler is None:
+            refuse(UnsupportedSamplerConfig, "an SDXL model needs a sampler schedule (sampler=<Schedule>): its time-embedding rows depend on start(pooled=) and are built there")
+        for flag, name in ((control, "control=True (an SDXL ControlNet)"), (ip_adapter, "ip_adapter=True (an SDXL IP-Adapter)"), (concat is not None, f"concat={concat!r}"),
+                           (pag, "pag=True"), (freeu, "freeu=True")):
+            if flag:
+                refuse(UnsupportedSamplerConfig, f"{name} on an SDXL model is not supported")
+        if config.dtype == "fp8":
+            refuse(UnsupportedSamplerConfig, "an SDXL model runs in the fp16 and the bf16 step, not under the fp8 policy (config.set_dtype('fp8'))")
+        if config.cfg_parallel:
+            refuse(UnsupportedSamplerConfig, "an SDXL model has no two-chain CFG form (TF_CFG_PARALLEL)")
     if prediction not in ("eps", "v"):
         refuse(ValueError, f"prediction= takes 'eps' or 'v', got {prediction!r}")
     if prediction == "v" or cfg_rescale:

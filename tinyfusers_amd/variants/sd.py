@@ -22,6 +22,9 @@ on B images against the context alone, between tf_latent_stack1_* and tf_sampler
 scaled backbone in front of the concats of the first two decoder stages, four device scalars that change without a re-capture.
 ``compile(..., pag=True)`` is perturbed-attention guidance inside the captured step (csrc/sdpa_pag.hip; ``set_pag``, ``start(pag=)``): one more
 guidance group whose self-attentions are the identity in the selected transformers, combined by the tails that exist.
+``StableDiffusion(SDXL)`` is the SDXL base model: a UNet with vector conditioning (``start(pooled=, original_size=, crop_top_left=, target_size=)``
+-- everything that depends on it is computed in ``start``, the captured step gains no launch), two text towers under ``conditioner.embedders``
+(``encode_prompt``), the SD-1.5 VAE tree at ``latent_scale`` 0.13025.
 
 How the object is laid out.  Everything ``compile`` / ``start`` / ``set_context`` / ``set_adapters`` keep on the model is declared, with its
 "not compiled" value, in ``_reset_state``: ``__init__`` runs all of it, ``compile`` the per-compile part, so a re-compile with other flags drops the
@@ -37,7 +40,7 @@ import numpy as np
 from .. import config
 from ..native import hip
 from ..storage.tensor import Branch, DeviceArray, Stream, _sh, asarray, bfloat16, dtag, pool, use_stream
-from ..vision.unet import SD15, SD15_EDIT, SD15_INPAINT, SD21, SD21_INPAINT, StepParams, UNetModel, freeu_stages, head_sizes, pag_layers
+from ..vision.unet import SD15, SD15_EDIT, SD15_INPAINT, SD21, SD21_INPAINT, SDXL, StepParams, UNetModel, freeu_stages, head_sizes, pag_layers
 from . import inputs
 from .samplers import UnsupportedSamplerConfig, get_alphas_cumprod  # noqa: F401  (get_alphas_cumprod: variants/sd.py:61-65, re-exported)
 
@@ -70,7 +73,9 @@ class StableDiffusion:
         from ..vae.vae import AutoencoderKL
         sd15 = any(cfg is c for c in (SD15, SD15_INPAINT, SD15_EDIT))        # the three SD-1.5 checkpoints share the VAE and the text encoder
         sd21 = any(cfg is c for c in (SD21, SD21_INPAINT))                   # SD-2.x: the same VAE (architecture and 0.18215), the OpenCLIP ViT-H text tower
-        self.first_stage_model = AutoencoderKL(init=init, init_encoder=False) if sd15 or sd21 else None   # text-to-image uses the decode side only: the encoder stays an empty tree until update_state fills it (encode_image needs it)
+        sdxl = cfg is SDXL                                                   # SDXL base: the same VAE architecture at another latent scale, two text towers
+        self.latent_scale = 0.13025 if sdxl else 0.18215                     # decode divides by it, encode_image and the inpainting conditioning multiply
+        self.first_stage_model = AutoencoderKL(init=init, init_encoder=False) if sd15 or sd21 or sdxl else None   # text-to-image uses the decode side only: the encoder stays an empty tree until update_state fills it (encode_image needs it)
         self.cond_stage_model = None
         if sd15:                         # variants/sd.py:12: cond_stage_model.transformer.text_model
             from ..vae.encoder import CLIPTextTransformer
@@ -79,6 +84,12 @@ class StableDiffusion:
         if sd21:                         # an LDM v2 checkpoint's cond_stage_model.model.* (vae/open_clip_text.py); built empty: update_state fills it
             from ..vae.open_clip_text import OpenClipText
             self.cond_stage_model = OpenClipText()
+        self.conditioner = None
+        if sdxl:                         # an SGM checkpoint's conditioner.embedders.0.transformer.text_model.* (CLIP-L, tapped behind layer 11 of 12) and
+            from ..vae.encoder import CLIPTextTransformer          # conditioner.embedders.1.model.* (OpenCLIP bigG: penultimate output, pooled vector)
+            from ..vae.open_clip_text import BIG_G_TEXT, OpenClipText
+            clip_l = namedtuple("Embedder0", ["transformer"])(transformer=namedtuple("Transformer", ["text_model"])(text_model=CLIPTextTransformer(init=init, tap=11)))
+            self.conditioner = namedtuple("Conditioner", ["embedders"])(embedders=[clip_l, OpenClipText(BIG_G_TEXT, tap="penultimate_raw", pooled=True)])
         self.control_model = None        # a ControlNet (vision/controlnet.py), under the LDM checkpoint's name: attach_control sets it
         self._ip_model = None            # an IPAdapter (storage/ip_adapter.py): attach_ip_adapter sets it (private: no checkpoint of the model names it)
         self._clip_vision = None         # a ClipVision (vae/clip_vision.py): attach_clip_vision sets it; start(ip_image=) runs it
@@ -107,6 +118,9 @@ class StableDiffusion:
         self._vpred, self._rescale, self._rescale_phi = False, False, None     # prediction="v"; cfg_rescale=True: the device fp32 word phi (in a 4-word block)
         self._ip, self._ip_model_compiled, self._ip_kv, self._ip_scales, self._ip_keep = False, None, None, None, None     # the adapter the step captured, ip_adapter=True: image-token K|V (G B, T, kv_n), the scales
         self._seed, self._image_offset, self._cursor = (0, 0), 0, 0  # what start() sets, step_sampler advances
+        # a UNet with label_emb (SDXL): y (G B, adm) and label_emb(y) (G B, E), private buffers start(pooled=) fills; the schedule's table of
+        # time-embedding rows (S G B, N) built there, and the serial that keys it (a new start invalidates the rows of the previous one)
+        self._adm, self._adm_y, self._y_emb, self._adm_table, self._adm_serial, self._adm_keep = False, None, None, None, 0, None
         self._kv_all = self._kv_key = self._ckv_all = self._emb_cur = self._emb_key = self._keep_row = None     # hoisted K|V and time-embedding row
         self._emb_rows = {}
         self._ctx_tmp = self._kv_tmp = self._start_keep = self._cond_keep = self._control_keep = self._ip_tower_keep = None   # referenced until their kernels have run
@@ -196,7 +210,7 @@ class StableDiffusion:
         b, c, h, w = x.shape
         assert b == 1, "decode: batch 1 (the reference reshapes to (3,512,512), variants/sd.py:52)"
         z16 = DeviceArray.empty((b, c, h, w), np.float16, "row")
-        hip.tf_scale_cast_f32_to_f16(z16.ptr, x.ptr, 1.0 / 0.18215, x.size, _sh())
+        hip.tf_scale_cast_f32_to_f16(z16.ptr, x.ptr, 1.0 / self.latent_scale, x.size, _sh())
         z = DeviceArray.empty((b, c, h, w), np.float16, "nhwc")
         hip.tf_nchw_to_nhwc_f16(z.ptr, z16.ptr, b, c, h, w, _sh())
         y = self.first_stage_model.decoder(self.first_stage_model.post_quant_conv(z))      # (1,3,8h,8w) NHWC
@@ -218,6 +232,22 @@ class StableDiffusion:
             return f"the width {w} must be a multiple of 64 up to 1280 (the encoder's reference-exact AttnBlock runs a head size of width / 8)"
         return None
 
+    def encode_prompt(self, ids_l, ids_g):
+        """SDXL: (B, T) token ids of the two tokenizers (host arrays) -> (context (B, T, 2048), pooled (B, 1280)) on the device: CLIP-L's layer-11 output
+        and OpenCLIP bigG's penultimate output, neither through its final LayerNorm, side by side; the pooled vector from bigG's last layer."""
+        if self.conditioner is None:
+            raise RuntimeError("StableDiffusion.encode_prompt: this model has no conditioner (the SDXL configuration only)")
+        if tuple(np.shape(ids_l)) != tuple(np.shape(ids_g)) or np.ndim(ids_l) != 2:
+            raise ValueError(f"StableDiffusion.encode_prompt: both towers take (B, T) token ids of one shape, got {np.shape(ids_l)} and {np.shape(ids_g)}")
+        a = self.conditioner.embedders[0].transformer.text_model(ids_l)
+        g, pooled = self.conditioner.embedders[1](ids_g)
+        (b, t, wa), wg = a.shape, g.shape[2]
+        ctx = DeviceArray.empty((b, t, wa + wg), a.dtype, "row")
+        hip.tf_memcpy_2d_async(ctx.ptr, (wa + wg) * 2, a.ptr, wa * 2, wa * 2, b * t, _sh())
+        hip.tf_memcpy_2d_async(ctx.ptr + wa * 2, (wa + wg) * 2, g.ptr, wg * 2, wg * 2, b * t, _sh())
+        ctx._base = (a, g)                                               # (referenced until the copies have run)
+        return ctx, pooled
+
     def encode_image(self, images):
         """vae/vae.py:12-15 for image-to-image: uint8 (B,H,W,3) images (host or device) -> x0 = 0.18215 x means, a device fp32 NCHW latent
         (B,4,H/8,W/8) -- the inverse of decode's 1/0.18215 (variants/sd.py:49).  uint8 -> x/127.5 - 1 (tf_image_from_u8_f16) -> Encoder +
@@ -229,7 +259,10 @@ class StableDiffusion:
             raise ValueError(f"StableDiffusion.encode_image: {why or 'an empty batch'}")
         means, keep = self._encode_u8(fsm, images)                       # (B,4,H/8,W/8) fp16 NHWC
         x0 = DeviceArray.empty(means.shape, np.float32, "row")
-        hip.tf_means_to_latent_f32(x0.ptr, means.ptr, b, means.shape[2], means.shape[3], _sh())
+        if self.latent_scale == 0.18215:
+            hip.tf_means_to_latent_f32(x0.ptr, means.ptr, b, means.shape[2], means.shape[3], _sh())
+        else:                            # the same kernel and product at the model's scale (SDXL: 0.13025)
+            hip.tf_means_to_cond_f32(x0.ptr, means.ptr, b, means.shape[2], means.shape[3], self.latent_scale, 0, 4, _sh())
         x0._base = keep                                                  # (referenced until the kernels have run)
         return x0
 
@@ -254,7 +287,7 @@ class StableDiffusion:
         """first_stage_model with a filled encoder, or the RuntimeError ``who`` raises."""
         fsm = self.first_stage_model
         if fsm is None:
-            raise RuntimeError(f"StableDiffusion.{who}: this model has no first_stage_model (SD-1.5 and SD-2.x configurations only)")
+            raise RuntimeError(f"StableDiffusion.{who}: this model has no first_stage_model (SD-1.5, SD-2.x and SDXL configurations only)")
         enc = fsm.encoder
         if any(m.weight is None for m in (enc.conv_in, enc.conv_out, fsm.quant_conv)):
             raise RuntimeError(f"StableDiffusion.{who}: the VAE encoder has no weights -- it is built empty; fill it with update_state "
@@ -461,7 +494,8 @@ class StableDiffusion:
                              ip_adapter=ip_adapter, has_ip_adapter=self._ip_model is not None, freeu=freeu,
                              freeu_plan=freeu_stages(self.model.diffusion_model.cfg) if freeu else (), pag=pag,
                              pag_table=pag_layers(self.model.diffusion_model.cfg) if pag else (), prediction=prediction, cfg_rescale=cfg_rescale,
-                             head_sizes=head_sizes(self.model.diffusion_model.cfg) if ip_adapter else ())
+                             head_sizes=head_sizes(self.model.diffusion_model.cfg) if ip_adapter else (),
+                             adm=bool(self.model.diffusion_model.cfg.adm_in_channels))
         if (ip_adapter or pag) and warmup < 1:
             raise ValueError(f"StableDiffusion.compile: {'ip_adapter' if ip_adapter else 'pag'}=True needs warmup >= 1 (the first launch of an attention instance cannot be captured)")
         if sampler is not None:
@@ -478,6 +512,7 @@ class StableDiffusion:
         self._ip = bool(ip_adapter)
         self._freeu = bool(freeu)
         self._vpred, self._rescale = prediction == "v", bool(cfg_rescale)
+        self._adm = bool(self.model.diffusion_model.cfg.adm_in_channels)
         self._ip_model_compiled = self._ip_model if self._ip else None
         if sampler is not None:
             with use_stream(self._stream):
@@ -512,6 +547,10 @@ class StableDiffusion:
             self._rescale_phi = DeviceArray.from_numpy(np.asarray([0.7, 0.0, 0.0, 0.0], np.float32), np.float32, "row")       # [0] phi: one 4-word write
         if self._pag:
             self._pag_flags = DeviceArray.from_numpy(inputs.pag_layer_words("mid", pag_layers(self.model.diffusion_model.cfg)), np.float32, "row")
+        if self._adm:                        # y = 0 until start(pooled=) writes it: the warm-up steps and the capture read these buffers
+            ucfg = self.model.diffusion_model.cfg
+            self._adm_y = DeviceArray.zeros((self._groups * b, ucfg.adm_in_channels), _step_dtype(), "row")
+            self._y_emb = DeviceArray.empty((self._groups * b, 4 * ucfg.model_channels), _step_dtype(), "row")
         if self._ip:
             ad = self._ip_model_compiled
             self._ip_kv = DeviceArray.zeros((self._groups * b, ad.num_tokens, ad.kv_layout()[1]), _step_dtype(), "row")
@@ -521,6 +560,8 @@ class StableDiffusion:
         """The private stacked context and -- config.hoist_step_invariants -- what depends on it or on the timestep alone: the K|V projections and
         the buffer ``_emb_cur`` the captured step reads its time-embedding row from, with the rows of ``timesteps`` computed up front."""
         self._ctx2 = self._stack_context(self._unc, self._ctx, self._groups, self._cond_groups())
+        if self._adm:
+            self._refresh_y_emb()
         if not config.hoist_step_invariants or config.cfg_parallel:
             return
         self._kv_all, self._kv_key = self.model.diffusion_model.context_kv(self._ctx2), self._weights_key()
@@ -531,6 +572,8 @@ class StableDiffusion:
         assert self._emb_cur.nbytes % 16 == 0
         hip.tf_memcpy_async(self._emb_cur.ptr, row.ptr, row.nbytes, 3, _sh())   # (the warm-up steps run at t = 981)
         self._keep_row = row
+        if self._adm:
+            return                           # the schedule's rows depend on y: start() builds them all in one pass (_build_adm_table)
         for t in (timesteps if timesteps is not None else ()):
             self._emb_row(float(t))
 
@@ -586,7 +629,8 @@ class StableDiffusion:
         b = self._latent.shape[0]
         pag = (self._pag_flags, ((self._groups - 2) * b, (self._groups - 1) * b)) if self._pag else None      # the group in front of the conditional one
         if not self._control:
-            return unet(x2, sp, ctx, shared=None if row is None else (None, row, self._kv_all), ip=ip, freeu=self._freeu_scales, pag=pag)     # (step() has put this timestep's row into _emb_cur)
+            return unet(x2, sp, ctx, shared=None if row is None else (None, row, self._kv_all), ip=ip, freeu=self._freeu_scales, pag=pag,
+                        y_emb=self._y_emb if row is None else None)     # (step() has put this timestep's row -- SDXL: one per image -- into _emb_cur)
         # the UNet's encoder, then the ControlNet on the same stacked latent, then the seam (UNetModel.__call__ calls `residuals` behind its
         # middle block); each model reads its own view of the hoisted row [UNet's | ControlNet's]
         shared_u = shared_c = None
@@ -693,7 +737,8 @@ class StableDiffusion:
 
     def start(self, seed=None, noise=None, image_offset=0, init_image=None, init_latent=None, mask=None, cond_image=None, cond_mask=None,
               cond_latent=None, image_guidance=None, control_image=None, control_hint=None, control_scale=None, ip_image_embeds=None, ip_image=None,
-              ip_scale=None, freeu=None, pag=None, cfg_rescale=None):
+              ip_scale=None, freeu=None, pag=None, cfg_rescale=None, pooled=None, uncond_pooled=None, original_size=None, crop_top_left=None,
+              target_size=None, uncond_size_ids=None):
         """A new image batch for the compiled sampler: sets the latent in place and rewinds the schedule.  ``seed``: the initial latent is
         drawn on the device (tag 0; image b is global image image_offset + b), and the ancestral noise of every step comes from the same seed
         (tag 1); ``noise``: a host (B,C,H,W) array for the initial latent instead (the ancestral noise then uses ``seed``, default 0).
@@ -731,8 +776,17 @@ class StableDiffusion:
         keep their values.
 
         A rescaled model (compile(..., cfg_rescale=True)): ``cfg_rescale=phi`` writes the word ``set_cfg_rescale`` writes; without it phi keeps its
-        value."""
+        value.
+
+        A vector-conditioned model (UNetConfig.adm_in_channels: SDXL) needs ``pooled`` at every start: the pooled text vector, a host float (B | 1, P)
+        array (``encode_prompt``'s second result).  ``uncond_pooled``: the unconditional group's (zeros when not given).  ``original_size``,
+        ``crop_top_left``, ``target_size``: (h, w) pairs in pixels, or (B, 2) arrays with a pair per image; when not given the latent's size x 8,
+        (0, 0) and the latent's size x 8.  ``uncond_size_ids``: the unconditional group's six ids (B | 1, 6) [original h, w, crop top, left, target
+        h, w]; the conditional ones when not given.  y = [pooled | Fourier(ids)] (tf_adm_vector_16), label_emb(y) and the time-embedding rows of
+        the whole schedule -- one per step and image -- are computed here: the replay's parameter launch copies G B rows where it copied one.
+        On any other model these arguments raise."""
         self._require_sampler("start")
+        adm = self._check_adm(pooled, uncond_pooled, original_size, crop_top_left, target_size, uncond_size_ids)
         phi = self._check_cfg_rescale(cfg_rescale, "start")
         pg = self._check_pag(pag, "start")
         fu = self._check_freeu(freeu, "start")
@@ -753,7 +807,61 @@ class StableDiffusion:
             self._write_pag(*pg)
         if phi is not None:
             self._write_cfg_rescale(phi)
+        if adm is not None:
+            self._write_adm(*adm)
         return self._latent
+
+    def _check_adm(self, pooled, uncond_pooled, original_size, crop_top_left, target_size, uncond_size_ids):
+        """start()'s vector-conditioning arguments, checked against the compiled model before anything changes: None for a model without label_emb,
+        else (pooled (R, P) fp32, size ids (R, 6) fp32) for the R = G B rows of the stacked batch, unconditional group first."""
+        given = [n for n, v in (("pooled", pooled), ("uncond_pooled", uncond_pooled), ("original_size", original_size), ("crop_top_left", crop_top_left),
+                                ("target_size", target_size), ("uncond_size_ids", uncond_size_ids)) if v is not None]
+        if not self._adm:
+            if given:
+                raise UnsupportedSamplerConfig(f"StableDiffusion.start: {given[0]}= needs a vector-conditioned UNet (UNetConfig.adm_in_channels: SDXL); this model has none")
+            return None
+        if pooled is None:
+            raise UnsupportedSamplerConfig("StableDiffusion.start: a vector-conditioned model (SDXL) reads its pooled text vector at every start -- pass pooled= "
+                                           "(encode_prompt's second result)")
+        ucfg = self.model.diffusion_model.cfg
+        (b, _, h, w), p = self._latent.shape, ucfg.adm_in_channels - 6 * ucfg.adm_time_dim
+        pc = inputs.adm_pooled(pooled, b, p, "pooled")
+        pu = inputs.adm_pooled(uncond_pooled, b, p, "uncond_pooled") if uncond_pooled is not None else np.zeros_like(pc)
+        ic = inputs.adm_size_ids(original_size, crop_top_left, target_size, b, 8 * h, 8 * w)
+        iu = inputs.adm_ids(uncond_size_ids, b) if uncond_size_ids is not None else ic
+        lead = self._groups - 1              # [uncond ; cond], or cond alone (cfg=False)
+        return np.concatenate([pu] * lead + [pc]), np.concatenate([iu] * lead + [ic])
+
+    def _write_adm(self, pooled, ids):
+        """y = [pooled | Fourier(ids)] into the model's buffer, then everything that depends on it, on the sampler stream behind every step already
+        queued.  The serial makes the rows of the previous start stale."""
+        self.synchronize()
+        ucfg = self.model.diffusion_model.cfg
+        with use_stream(self._stream):
+            dp, di = DeviceArray.from_numpy(pooled, _step_dtype(), "row"), DeviceArray.from_numpy(ids, np.float32, "row")
+            hip.tf_adm_vector_16(dtag(self._adm_y.dtype), self._adm_y.ptr, dp.ptr, di.ptr, pooled.shape[0], pooled.shape[1], ucfg.adm_time_dim, 10000.0, _sh())
+            self._adm_keep = (dp, di)                                    # (referenced until the kernel has run)
+            self._adm_serial += 1
+            self._refresh_y_emb()
+            self._build_adm_table()
+
+    def _refresh_y_emb(self):
+        """label_emb(y) into the buffer an un-hoisted step reads (and the rows are built from), on the current stream."""
+        y_emb = self.model.diffusion_model.label_embedding(self._adm_y)
+        hip.tf_memcpy_async(self._y_emb.ptr, y_emb.ptr, y_emb.nbytes, 3, _sh())
+        self._adm_keep = (self._adm_keep, y_emb)
+
+    def _build_adm_table(self):
+        """The whole schedule's time-embedding rows in one pass (UNetModel.time_embedding_table), keyed by the weights and this start's serial:
+        row block s is what the parameter launch of step s copies into ``_emb_cur``."""
+        if self._emb_cur is None:
+            return                                                       # (not hoisted: the step computes its rows from _y_emb)
+        ts = [float(t) for t in self._sched.timesteps]
+        table = self.model.diffusion_model.time_embedding_table(ts, self._y_emb)
+        r, n = self._emb_cur.shape
+        assert table.shape == (len(ts) * r, n), (table.shape, len(ts), r, n)
+        self._adm_table, self._emb_key = table, self._weights_key()
+        self._emb_rows = {t: table.view((r, n), "row", i * r * n) for i, t in enumerate(ts)}
 
     def _check_cfg_rescale(self, phi, who):
         """phi checked against the compiled model before anything changes: None when not given, else the float in [0, 1]."""
@@ -1090,7 +1198,7 @@ class StableDiffusion:
             dlm = DeviceArray.from_numpy(lat_mask, np.float32, "row")
             means, keep = self._encode_u8(self.first_stage_model, image, m8)
             hip.tf_memcpy_2d_async(self._cond.ptr, cc * h * w * 4, dlm.ptr, h * w * 4, h * w * 4, b, _sh())     # channel 0: the latent mask
-            hip.tf_means_to_cond_f32(self._cond.ptr, means.ptr, b, h, w, 0.18215, 1, cc, _sh())
+            hip.tf_means_to_cond_f32(self._cond.ptr, means.ptr, b, h, w, self.latent_scale, 1, cc, _sh())
             self._cond_keep = keep + (dlm,)                                  # (referenced until the kernels have run)
 
     def _guidance(self, guidance, what):
@@ -1140,6 +1248,9 @@ class StableDiffusion:
         key = self._weights_key() if key is None else key
         if self._emb_key != key:
             self._emb_rows, self._emb_key = {}, key
+            if self._adm:                    # a weight was replaced since start(): label_emb(y) and the schedule's rows again, from the kept y
+                self._refresh_y_emb()
+                self._build_adm_table()
         row = self._emb_rows.get(t)
         if row is None:
             if len(self._emb_rows) >= 1024:
@@ -1152,12 +1263,14 @@ class StableDiffusion:
     def _weights_key(self):
         """weights_key() of everything the hoisted tables were computed from: the UNet and, in a controlled model, the ControlNet."""
         key = self.model.diffusion_model.weights_key()
+        if self._adm:
+            key = key + (("adm", self._adm_serial),)     # the conditioning serial: start(pooled=) makes every cached row stale
         return key + self.control_model.weights_key() if self._control else key
 
     def _time_row(self, params):
         """The hoisted time-embedding row of one timestep: the UNet's, and behind it in the same buffer a controlled model's ControlNet's -- one
         copy in the parameter launch hands both to the replay."""
-        row = self.model.diffusion_model.time_embedding_all(params)[1]
+        row = self.model.diffusion_model.time_embedding_all(params, self._y_emb if self._adm else None)[1]
         if not self._control:
             return row
         crow = self.control_model.time_embedding_all(params)[1]
@@ -1205,6 +1318,9 @@ class StableDiffusion:
         ``skipped: <key>``; a model without a text encoder has no ``lora_te_*`` targets.  Returns the name."""
         import os
         from ..storage import lora as L
+        if self.model.diffusion_model.cfg.adm_in_channels:
+            raise UnsupportedSamplerConfig("StableDiffusion.load_lora: LoRA adapters on an SDXL model are not supported (their targets name two text towers and "
+                                           "transformers of depth 2 and 10; nothing is loaded)")
         reg = self._lora if self._lora is not None else L.LoraRegistry()
         if name is None:
             name = os.path.splitext(os.path.basename(str(src)))[0] if not isinstance(src, dict) else f"lora{len(reg.loaded)}"

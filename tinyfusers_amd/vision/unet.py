@@ -26,7 +26,7 @@ import numpy as np
 
 from ..attention.attention import SpatialTransformer, _concat_rows
 from ..ff.group_norm import GroupNorm
-from ..ff.linear import Linear, gemv_f16, linear_f16
+from ..ff.linear import Linear, RowSlice, gemv_f16, gemv_rows, linear_f16
 from ..native import ControlEntry, FreeuEntry, hip
 from .. import config
 from ..storage.tensor import Branch, DeviceArray, Tensor, _sh, asarray, bfloat16, dtag, is_bfloat16
@@ -45,6 +45,9 @@ class UNetConfig:
     n_heads: int = 8
     context_dim: int = 768
     d_head: Optional[int] = None      # SD-2.x: a fixed head size, the head count follows the channels (``heads_at``); n_heads is then unused
+    transformer_depth: Optional[Tuple[int, ...]] = None      # SDXL: BasicTransformerBlocks per SpatialTransformer, one entry per level (0: none there); None: 1 on attention_levels (``depth_at``)
+    adm_in_channels: Optional[int] = None                    # SDXL: the width of the vector conditioning y; emb = time_embed(t) + label_emb(y)
+    adm_time_dim: int = 256                                  # SDXL: the Fourier width of each of the six size ids inside y
 
 
 SD15 = UNetConfig()
@@ -54,6 +57,10 @@ TINY = UNetConfig(model_channels=64, channel_mult=(1, 2, 2), attention_levels=(0
 SD21 = replace(SD15, d_head=64, context_dim=1024)     # Stable Diffusion 2.0 / 2.1 (512-base, 768-v): 5 / 10 / 20 / 20 heads of 64, OpenCLIP ViT-H context
 SD21_INPAINT = replace(SD21, in_channels=9)           # 512-inpainting-ema: SD15_INPAINT's channels
 TINY_V2 = UNetConfig(model_channels=64, channel_mult=(1, 2, 2), attention_levels=(0, 1), d_head=64, context_dim=128)     # 1 / 2 / 2 heads of 64
+# SDXL base: three levels with 0 / 2 / 10 transformer blocks (10 in the middle block), 5 / 10 / 20 heads of 64, the 2048-wide context of two text
+# towers, y = [pooled (1280) | Fourier(original h, w, crop top, left, target h, w) (6 x 256)]
+SDXL = UNetConfig(channel_mult=(1, 2, 4), transformer_depth=(0, 2, 10), d_head=64, context_dim=2048, adm_in_channels=2816)
+TINY_XL = UNetConfig(model_channels=64, channel_mult=(1, 2, 2), transformer_depth=(0, 1, 2), d_head=64, context_dim=128, adm_in_channels=64 + 6 * 32, adm_time_dim=32)
 
 
 def heads_at(cfg, ch):
@@ -66,9 +73,21 @@ def heads_at(cfg, ch):
     return ch // cfg.d_head, cfg.d_head
 
 
+def depth_at(cfg, lev):
+    """BasicTransformerBlocks of a SpatialTransformer at level ``lev`` (0: the level has none); lev = "mid": of the middle block's.  The one place
+    the plan is read from: cfg.transformer_depth where set (the middle block takes the last level's), else 1 on cfg.attention_levels and in the
+    middle block -- the SD-1.x / SD-2.x plan."""
+    td = cfg.transformer_depth
+    if td is None:
+        return 1 if lev == "mid" or lev in cfg.attention_levels else 0
+    if len(td) != len(cfg.channel_mult) or min(td) < 0 or td[-1] < 1:
+        raise ValueError(f"UNetConfig: transformer_depth={td} needs one entry >= 0 per level of channel_mult={cfg.channel_mult}, the last >= 1 (the middle block's)")
+    return td[-1] if lev == "mid" else td[lev]
+
+
 def head_sizes(cfg):
     """The head sizes of the UNet's SpatialTransformers, one per attention level, from the channel plan alone."""
-    return sorted({heads_at(cfg, cfg.model_channels * cfg.channel_mult[lev])[1] for lev in cfg.attention_levels}
+    return sorted({heads_at(cfg, cfg.model_channels * cfg.channel_mult[lev])[1] for lev in range(len(cfg.channel_mult)) if depth_at(cfg, lev)}
                   | {heads_at(cfg, cfg.model_channels * cfg.channel_mult[-1])[1]})
 
 
@@ -134,7 +153,7 @@ def encoder_plan(cfg, in_channels, init=False):
     mc, emb = cfg.model_channels, cfg.model_channels * 4
     cd = cfg.context_dim
     R = lambda i, o: ResBlock(i, emb, o, init=init)
-    S = lambda c: SpatialTransformer(c, cd, *heads_at(cfg, c), init=init)
+    S = lambda c, d: SpatialTransformer(c, cd, *heads_at(cfg, c), init=init, depth=d)
     time_embed = [Linear(mc, emb, init=init), Tensor.silu, Linear(emb, emb, init=init)]
     input_blocks = [[Conv2d(in_channels, mc, kernel_size=[3, 3], padding=[1, 1], init=init)]]
     chans, ch, nlev = [mc], mc, len(cfg.channel_mult)
@@ -142,14 +161,14 @@ def encoder_plan(cfg, in_channels, init=False):
         for _ in range(cfg.num_res_blocks):
             blk = [R(ch, mc * mult)]
             ch = mc * mult
-            if lev in cfg.attention_levels:
-                blk.append(S(ch))
+            if depth_at(cfg, lev):
+                blk.append(S(ch, depth_at(cfg, lev)))
             input_blocks.append(blk)
             chans.append(ch)
         if lev != nlev - 1:
             input_blocks.append([Downsample(ch, init=init)])
             chans.append(ch)
-    middle_block = [R(ch, ch), S(ch), R(ch, ch)]
+    middle_block = [R(ch, ch), S(ch, depth_at(cfg, "mid")), R(ch, ch)]
     return time_embed, input_blocks, middle_block, chans
 
 
@@ -165,8 +184,9 @@ class StepModel:
 
     def _prepare(self):
         res, sts = self._all(ResBlock), self._all(SpatialTransformer)
+        blocks = [blk for s in sts for blk in s.transformer_blocks]          # every block of every transformer, in execution order
         key = tuple(r.emb_layers[1].weight.wkey for r in res) + tuple(r.emb_layers[1].bias.wkey for r in res) \
-            + tuple(w.wkey for s in sts for w in (s.transformer_blocks[0].attn2.to_k.weight, s.transformer_blocks[0].attn2.to_v.weight))
+            + tuple(w.wkey for blk in blocks for w in (blk.attn2.to_k.weight, blk.attn2.to_v.weight))
         if self._batched is not None and self._batched["key"] == key:
             return self._batched
         emb_w = _concat_rows([r.emb_layers[1].weight for r in res])
@@ -175,24 +195,73 @@ class StepModel:
         for r in res:
             emb_off[id(r)] = (off, r.emb_layers[1].weight.shape[0]); off += r.emb_layers[1].weight.shape[0]
         kv_w, kv_off, off = None, {}, 0
-        if sts:
+        if blocks:
             ws = []
-            for s in sts:
-                a = s.transformer_blocks[0].attn2
+            for blk in blocks:                      # kv_off: per block (a transformer of depth d owns d consecutive column slices)
+                a = blk.attn2
                 ws += [a.to_k.weight, a.to_v.weight]
-                kv_off[id(s)] = off; off += 2 * a.to_k.weight.shape[0]
+                kv_off[id(blk)] = off; off += 2 * a.to_k.weight.shape[0]
             kv_w = _concat_rows(ws)
         self._batched = dict(key=key, emb_w=emb_w, emb_b=emb_b, emb_off=emb_off, kv_w=kv_w, kv_off=kv_off, kv_n=off)
         return self._batched
 
-    def time_embedding_all(self, timesteps):
+    def time_embedding_all(self, timesteps, y_emb=None):
         """(emb, emb_all): the time-embedding chain of unet.py:54-56 and every ResBlock's Linear(SiLU(emb)) (resnet.py:28) as one row.  Both
         depend on the timestep alone -- not on the latent, the context or the batch -- so a sampler may compute the row of a timestep once
-        and keep it (variants/sd.py here: StableDiffusion.compile(timesteps=...))."""
+        and keep it (variants/sd.py here: StableDiffusion.compile(timesteps=...)).
+
+        The rule of the row's shape, stated once.  A model WITHOUT ``label_emb`` (SD-1.x, SD-2.x, every ControlNet) has the (1, N) row above; its
+        ResBlocks read it through a stride-0 per-image bias (one row for every image), and ``y_emb`` must be None.  A model WITH ``label_emb``
+        (cfg.adm_in_channels: SDXL) computes emb = time_embed(t) + label_emb(y), and SiLU sits between that sum and the ResBlock projections, so
+        the rows of two images (or of the unconditional and the conditional group) differ: ``y_emb`` = ``label_embedding(y)``, (R, E) with R the
+        batch the UNet runs on, is required, emb is (R, E) and emb_all (R, N); ResBlock i reads columns [off_i, off_i + n_i) of image b's row
+        through a per-image bias of stride N (ff/linear.py::RowSlice).  Both still depend on nothing but the timestep and y."""
         bt = self._prepare()
         t_emb = timestep_embedding(timesteps, self.cfg.model_channels)
         emb = self.time_embed[2](self.time_embed[0](t_emb), silu_input=True)          # Linear -> SiLU -> Linear
-        return emb, gemv_f16(emb, bt["emb_w"], bt["emb_b"], silu_input=True)          # every ResBlock's Linear(SiLU(emb))
+        if getattr(self, "label_emb", None) is None:
+            if y_emb is not None:
+                raise ValueError("time_embedding_all: y_emb= is for a model with label_emb (UNetConfig.adm_in_channels)")
+            return emb, gemv_f16(emb, bt["emb_w"], bt["emb_b"], silu_input=True)      # every ResBlock's Linear(SiLU(emb))
+        if y_emb is None:
+            raise ValueError("time_embedding_all: a model with label_emb (UNetConfig.adm_in_channels) needs y_emb = label_embedding(y)")
+        emb = self.emb_rows(emb, y_emb)                                               # (R, E): row r = emb + y_emb[r]
+        return emb, gemv_rows(emb, bt["emb_w"], bt["emb_b"], silu_input=True)
+
+    def label_embedding(self, y):
+        """label_emb(y): y (R, adm_in_channels) in the step's 16-bit type -> (R, E), Linear -> SiLU -> Linear."""
+        le = getattr(self, "label_emb", None)
+        if le is None:
+            raise ValueError("label_embedding: this model has no label_emb (UNetConfig.adm_in_channels is None)")
+        if y.ndim != 2 or y.shape[1] != le[0][0].in_features:
+            raise ValueError(f"label_embedding: y must be (R, {le[0][0].in_features}), got {y.shape}")
+        return gemv_rows(gemv_rows(y, le[0][0].weight, le[0][0].bias), le[0][2].weight, le[0][2].bias, silu_input=True)
+
+    @staticmethod
+    def emb_rows(t_emb, y_emb):
+        """(S R, E): row s R + r = t_emb[s] + y_emb[r] (tf_adm_emb_rows_16: fp32 add, one rounding)."""
+        (s, e), r = t_emb.shape, y_emb.shape[0]
+        assert y_emb.shape == (r, e) and dtag(y_emb.dtype) == dtag(t_emb.dtype), (t_emb.shape, y_emb.shape)
+        out = DeviceArray.empty((s * r, e), t_emb.dtype, "row")
+        hip.tf_adm_emb_rows_16(dtag(t_emb.dtype), out.ptr, t_emb.ptr, y_emb.ptr, s, r, e, _sh())
+        return out
+
+    def time_embedding_table(self, timesteps, y_emb):
+        """(S R, N): ``time_embedding_all``'s emb_all for every timestep of a schedule, rows [s R, (s + 1) R) those of timesteps[s] -- the time MLP
+        at M = S, ONE row build and ONE pass of the batched ResBlock projection at M = S R (the projection weight, 35 MB at SDXL, is read once
+        per table, not once per timestep).  Every row holds the bits ``time_embedding_all`` gives it (the GEMV computes each row on its own)."""
+        bt = self._prepare()
+        mc, ts = self.cfg.model_channels, [float(t) for t in timesteps]
+        t_sin = DeviceArray.empty((len(ts), mc), bfloat16 if config.is_bf16() else np.float16, "row")
+        keep = []
+        for i, t in enumerate(ts):
+            row = timestep_embedding(t, mc)
+            hip.tf_memcpy_async(t_sin.ptr + i * row.nbytes, row.ptr, row.nbytes, 3, _sh())
+            keep.append(row)
+        t_emb = gemv_rows(gemv_rows(t_sin, self.time_embed[0].weight, self.time_embed[0].bias), self.time_embed[2].weight, self.time_embed[2].bias, silu_input=True)
+        out = gemv_rows(self.emb_rows(t_emb, y_emb), bt["emb_w"], bt["emb_b"], silu_input=True)
+        out._base = (out._base, keep, t_sin, t_emb)
+        return out
 
     def context_kv(self, context):
         """Every cross-attention's K|V projection of the (stacked) context as ONE GEMM (attention/attention.py:35-36 for all 16 blocks):
@@ -202,15 +271,16 @@ class StepModel:
 
     def weights_key(self):
         """Identity of everything time_embedding_all / context_kv depend on: a cached row is stale once any of these weights is replaced."""
-        return self._prepare()["key"] + tuple(m.weight.wkey for m in (self.time_embed[0], self.time_embed[2])) + tuple(m.bias.wkey for m in (self.time_embed[0], self.time_embed[2]))
+        mlps = (self.time_embed[0], self.time_embed[2]) + ((self.label_emb[0][0], self.label_emb[0][2]) if getattr(self, "label_emb", None) is not None else ())
+        return self._prepare()["key"] + tuple(m.weight.wkey for m in mlps) + tuple(m.bias.wkey for m in mlps)
 
-    def step_shared(self, timesteps, context):
+    def step_shared(self, timesteps, context, y_emb=None):
         """What one denoising step computes ONCE for every sample: the time-embedding chain (the same timestep for the whole batch) and
         the cross-attention K|V projection of all contexts.  __call__ computes them itself unless handed the result (``shared``)."""
-        emb, emb_all = self.time_embedding_all(timesteps)
+        emb, emb_all = self.time_embedding_all(timesteps, y_emb)
         return emb, emb_all, self.context_kv(context)
 
-    def _shared(self, timesteps, context, shared):
+    def _shared(self, timesteps, context, shared, y_emb=None):
         """(emb, emb_all, kv_all, br) of one call: handed in (``shared``) or computed here; br is the open side branch the K|V projection runs
         on (config.parallel_branches), joined by the first SpatialTransformer."""
         bt = self._prepare()
@@ -221,7 +291,7 @@ class StepModel:
             br = Branch()                              # the context projection is independent of the time-embedding chain
             with br:
                 kv_all = linear_f16(context, bt["kv_w"])      # (either element type since round 5)
-        emb, emb_all = self.time_embedding_all(timesteps)                            # Linear -> SiLU -> Linear, then every ResBlock's Linear(SiLU(emb))
+        emb, emb_all = self.time_embedding_all(timesteps, y_emb)                     # Linear -> SiLU -> Linear, then every ResBlock's Linear(SiLU(emb))
         if br is None:
             kv_all = self.context_kv(context)                                         # every attn2's K|V of the context
         return emb, emb_all, kv_all, br
@@ -243,7 +313,12 @@ class StepModel:
                 else (nxt.norm, False) if isinstance(nxt, SpatialTransformer) else None
             if isinstance(bb, ResBlock):
                 off, n = bt["emb_off"][id(bb)]
-                return bb(x, emb, emb_out=emb_all.view((emb_all.shape[0], n), "row", off), out_gn=gn, out_norm=on)
+                if emb_all.shape[0] == 1:                      # one row for every image (time_embedding_all's rule)
+                    return bb(x, emb, emb_out=emb_all.view((1, n), "row", off), out_gn=gn, out_norm=on)
+                nb = (x[0] if isinstance(x, (tuple, list)) else x).shape[0]
+                if emb_all.shape[0] != nb:
+                    raise ValueError(f"UNet: {emb_all.shape[0]} time-embedding rows for a batch of {nb} (label_embedding(y) has one row per image)")
+                return bb(x, emb, emb_out=RowSlice(emb_all, off, n), out_gn=gn, out_norm=on)
             if isinstance(bb, SpatialTransformer):
                 c = bb.proj_in.weight.shape[0]
                 bip = None
@@ -251,7 +326,8 @@ class StepModel:
                     off, idx = ip[1][id(bb)]
                     bip = (KVSlice(ip[0], off, c, ip[2]), ip[3].ptr + 4 * idx)
                 bpag = (pag[0].ptr + 4 * pag_idx[id(bb)], pag[1]) if pag is not None else None
-                return bb(x, context, kv=KVSlice(kv_all, bt["kv_off"][id(bb)], c, bt["kv_n"]), out_gn=gn, out_norm=on, ip=bip, pag=bpag)
+                kvs = [KVSlice(kv_all, bt["kv_off"][id(blk)], c, bt["kv_n"]) for blk in bb.transformer_blocks]      # each block its own K|V columns
+                return bb(x, context, kv=kvs, out_gn=gn, out_norm=on, ip=bip, pag=bpag)
             if isinstance(bb, (Downsample, Upsample)):
                 return bb(x, out_gn=gn, out_norm=on)
             if isinstance(bb, Conv2d):
@@ -320,7 +396,7 @@ def pag_layers(cfg):
     nlev, paths, i = len(cfg.channel_mult), [], 1
     for lev in range(nlev):
         for _ in range(cfg.num_res_blocks):
-            if lev in cfg.attention_levels:
+            if depth_at(cfg, lev):
                 paths.append(f"input_blocks.{i}")
             i += 1
         i += lev != nlev - 1                          # the Downsample block
@@ -328,7 +404,7 @@ def pag_layers(cfg):
     i = 0
     for lev in reversed(range(nlev)):
         for _ in range(cfg.num_res_blocks + 1):
-            if lev in cfg.attention_levels:
+            if depth_at(cfg, lev):
                 paths.append(f"output_blocks.{i}")
             i += 1
     return paths
@@ -389,8 +465,10 @@ class UNetModel(StepModel):
         mc, emb = cfg.model_channels, cfg.model_channels * 4
         cd = cfg.context_dim
         R = lambda i, o: ResBlock(i, emb, o, init=init)
-        S = lambda c: SpatialTransformer(c, cd, *heads_at(cfg, c), init=init)
+        S = lambda c, d: SpatialTransformer(c, cd, *heads_at(cfg, c), init=init, depth=d)
         self.time_embed, self.input_blocks, self.middle_block, chans = encoder_plan(cfg, cfg.in_channels, init)
+        # SDXL: emb = time_embed(t) + label_emb(y); the tree spells the checkpoint's label_emb.0.0.* / label_emb.0.2.* (None: no such leaves)
+        self.label_emb = [[Linear(cfg.adm_in_channels, emb, init=init), Tensor.silu, Linear(emb, emb, init=init)]] if cfg.adm_in_channels else None
         ch, nlev = chans[-1], len(cfg.channel_mult)
         self.output_blocks = []
         for lev in reversed(range(nlev)):
@@ -398,8 +476,8 @@ class UNetModel(StepModel):
             for i in range(cfg.num_res_blocks + 1):
                 blk = [R(ch + chans.pop(), mc * mult)]
                 ch = mc * mult
-                if lev in cfg.attention_levels:
-                    blk.append(S(ch))
+                if depth_at(cfg, lev):
+                    blk.append(S(ch, depth_at(cfg, lev)))
                 if lev > 0 and i == cfg.num_res_blocks:
                     blk.append(Upsample(ch, init=init))
                 self.output_blocks.append(blk)
@@ -415,8 +493,9 @@ class UNetModel(StepModel):
             raise ValueError("UNetModel.ip_slots: the adapter was built for another UNet")
         return {id(st): (offs[k], k) for k, (_, _, st) in enumerate(paths)}
 
-    def __call__(self, x, timesteps=None, context=None, shared=None, control=None, ip=None, freeu=None, pag=None):
-        """control = (residuals, scales): a ControlNet's len(input_blocks) + 1 residual tensors (or a callable that returns them, called behind
+    def __call__(self, x, timesteps=None, context=None, shared=None, control=None, ip=None, freeu=None, pag=None, y_emb=None):
+        """y_emb: ``label_embedding(y)``, (batch, E), on a model with label_emb (SDXL) where ``shared`` does not hand the rows in.
+        control = (residuals, scales): a ControlNet's len(input_blocks) + 1 residual tensors (or a callable that returns them, called behind
         the middle block) and the device fp32 array of their strengths.  Behind the middle block one launch (control_add) makes new skip tensors
         and a new middle output, skip_i + s_i residual_i, which carry no statistics: the output path's concat GroupNorms then compute theirs
         (ff/group_norm.py::_gn, the explicit path), and no producer is asked for concat statistics.  None: the step as it always was.
@@ -431,7 +510,7 @@ class UNetModel(StepModel):
         ``pag_layers`` order; the rows [b0, b1) of x are the perturbed guidance group: in every SpatialTransformer whose word is not zero their
         self-attention is the identity, attn1(x) = to_out(to_v(norm1(x))), inside the one attention launch (tf_sdpa_pag_16 in place of tf_sdpa_16).
         The words are read when the kernels run.  None: the plain launches."""
-        emb, emb_all, kv_all, br = self._shared(timesteps, context, shared)
+        emb, emb_all, kv_all, br = self._shared(timesteps, context, shared, y_emb)
         fu = freeu_stages(self.cfg) if freeu is not None else []
         if ip is not None:
             adapter, kv_ip, scales = ip

@@ -464,6 +464,136 @@ def sd2_bench(args):
     print(json.dumps(out))
 
 
+def sdxl_bench(args):
+    """--sdxl: the SDXL base step (synthetic weights) -- 128 x 128 latent, CFG pair, --dpm-steps DPM++2M steps; medians of --rounds rounds of --replays
+    replays with the spread between the rounds.  start() with the schedule's rows built in one pass (time_embedding_table: the batched ResBlock
+    projection once at M = S R) against S passes at M = R, alternating in the same rounds; both text towers for the prompt pair; the library entries of
+    one step; the GEMM shapes that had no row in the tuning table.  Writes profiles/sampler_bench_sdxl.json."""
+    import tinyfusers_amd.storage.tensor as T
+    from tinyfusers_amd.native import hip
+    from tinyfusers_amd.storage.state import param_shapes, update_state
+    from tinyfusers_amd.storage.synth import synth_normal, synth_state_dict
+    from tinyfusers_amd.vae.open_clip_text import synthetic_state
+    from tinyfusers_amd.variants.samplers import DPMSolverPP2M
+    from tinyfusers_amd.variants.sd import StableDiffusion
+    from tinyfusers_amd.vision.unet import SDXL
+
+    T.ensure_init(0)
+
+    def table_keys():
+        n, key, cfg_ = ctypes.c_int(0), (ctypes.c_int * 10)(), (ctypes.c_int * 5)()
+        hip.tf_gemm_tune_count(ctypes.byref(n))
+        keys = set()
+        for i in range(n.value):
+            hip.tf_gemm_tune_entry(i, key, cfg_)
+            keys.add(tuple(key))
+        return keys
+    shipped = table_keys()
+    sched = DPMSolverPP2M().schedule(args.dpm_steps)
+    side, images = args.sdxl_side, 1
+    m = StableDiffusion(SDXL)
+    big_g = "conditioner.embedders.1.model."
+    with contextlib.redirect_stdout(io.StringIO()):
+        update_state(m.model.diffusion_model, synth_state_dict(param_shapes(m.model.diffusion_model), 0), "")
+        update_state(m.conditioner, synth_state_dict({k: v for k, v in param_shapes(m.conditioner, "conditioner").items() if not k.startswith(big_g)}, 0), "conditioner")
+        update_state(m.conditioner, synthetic_state(m.conditioner.embedders[1].cfg, 0, big_g, pooled=True), "conditioner")
+    rng = np.random.default_rng(0)
+    prompt = np.full((1, 77), 49407, dtype=np.int64); prompt[0, 0] = 49406; prompt[0, 1:10] = rng.integers(0, 49406, 9)
+    empty = np.full((1, 77), 49407, dtype=np.int64); empty[0, 0] = 49406
+    pg, eg = prompt.copy(), empty.copy()
+    pg[0, 11:] = 0; eg[0, 2:] = 0
+    out = {"protocol": f"median of {args.rounds} rounds of {args.replays} replays, (median ms, max - min over the rounds); SDXL base, {side} x {side} latent, "
+                       f"CFG pair, {args.dpm_steps}-step DPM++2M, synthetic weights"}
+    # 1. both towers, the prompt pair (eager launches, wall time from the call to the drained stream)
+    m.encode_prompt(prompt, pg); m.encode_prompt(empty, eg)
+    hip.tf_stream_sync(None)
+    tw = []
+    for _ in range(args.rounds):
+        t0 = time.perf_counter()
+        ctx, pooled = m.encode_prompt(prompt, pg)
+        unc, unc_pooled = m.encode_prompt(empty, eg)
+        hip.tf_stream_sync(None)
+        tw.append(1e3 * (time.perf_counter() - t0))
+    out["both_towers_two_prompts_ms"] = (round(float(np.median(tw)), 3), round(max(tw) - min(tw), 3))
+    pooled_h, unc_pooled_h = pooled.numpy(), unc_pooled.numpy()
+    # 2. the step
+    lat = m.latent_from_numpy(np.zeros((images, 4, side, side), np.float32))
+    m.compile(unc, ctx, lat, sampler=sched)
+    kw = dict(pooled=pooled_h, uncond_pooled=unc_pooled_h, original_size=(8 * side, 8 * side), target_size=(8 * side, 8 * side))
+    m.start(seed=1234, **kw)
+    m.synchronize()
+    lat0 = T.DeviceArray.from_numpy(lat.numpy(), np.float32, "row")
+    ev0, ev1, ms = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_float()
+    hip.tf_event_create(ctypes.byref(ev0)); hip.tf_event_create(ctypes.byref(ev1))
+
+    def replays(n):
+        m.synchronize()
+        hip.tf_event_record(ev0, m._stream.handle)
+        for s_ in range(n):
+            i = s_ % len(sched.timesteps)
+            if i == 0:
+                hip.tf_memcpy_async(lat.ptr, lat0.ptr, lat.nbytes, 3, m._stream.handle)
+            m.step_sampler(i, 7.5)
+        hip.tf_event_record(ev1, m._stream.handle)
+        m.synchronize()
+        hip.tf_event_elapsed_ms(ctypes.byref(ms), ev0, ev1)
+        return ms.value / n
+    replays(len(sched.timesteps))
+    per = [replays(args.replays) for _ in range(args.rounds)]
+    assert np.isfinite(lat.numpy()).all()
+    out["step_ms"] = (round(float(np.median(per)), 4), round(max(per) - min(per), 4))
+    ent = step_entries(T, m)
+    out["step_entries"] = sum(ent.values())
+    out["step_entries_by_name"] = dict(sorted(ent.items()))
+    # 3. start(): the rows in one pass against one pass per timestep, alternating
+    unet = m.model.diffusion_model
+
+    def start_wall(per_timestep):
+        if per_timestep:
+            def rows_one_by_one():
+                ts = [float(t) for t in sched.timesteps]
+                keep = [unet.time_embedding_all(t, m._y_emb)[1] for t in ts]                  # S passes of the projection at M = R
+                m._adm_table, m._emb_key = keep, m._weights_key()
+                m._emb_rows = dict(zip(ts, keep))
+            m._build_adm_table = rows_one_by_one
+        t0 = time.perf_counter()
+        m.start(seed=1234, **kw)
+        m.synchronize()
+        dt = 1e3 * (time.perf_counter() - t0)
+        if per_timestep:
+            del m._build_adm_table                       # (the instance attribute: the method is back)
+        return dt
+    start_wall(False); start_wall(True)
+    st = {"single_pass": [], "per_timestep": []}
+    for _ in range(args.rounds):
+        st["single_pass"].append(start_wall(False)); st["per_timestep"].append(start_wall(True))
+    out["start_ms"] = {k: (round(float(np.median(v)), 3), round(max(v) - min(v), 3)) for k, v in st.items()}
+    with T.use_stream(m._stream):
+        tb = []
+        for _ in range(args.rounds + 1):
+            m.synchronize()
+            t0 = time.perf_counter()
+            keep = unet.time_embedding_table(sched.timesteps, m._y_emb)
+            m.synchronize()
+            t1 = time.perf_counter()
+            keep = [unet.time_embedding_all(float(t), m._y_emb)[1] for t in sched.timesteps]
+            m.synchronize()
+            tb.append((1e3 * (t1 - t0), 1e3 * (time.perf_counter() - t1)))
+    out["rows_alone_ms"] = {"single_pass": round(float(np.median([a for a, _ in tb[1:]])), 3), "per_timestep": round(float(np.median([b for _, b in tb[1:]])), 3)}
+    m.start(seed=1234, **kw); m.synchronize()
+    bt = unet._prepare()
+    out["plan"] = {"transformer_blocks": len(bt["kv_off"]), "kv_n": bt["kv_n"], "resblock_projection_columns": int(bt["emb_w"].shape[0]),
+                   "rows_per_step": int(m._emb_cur.shape[0]), "table_rows": int(m._adm_table.shape[0])}
+    out["gemm_shapes_autotuned_MNK"] = sorted({tuple(k[:3]) for k in table_keys() - shipped})
+    hip.tf_event_destroy(ev0); hip.tf_event_destroy(ev1)
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sampler_bench_sdxl.json")
+    if not args.sdxl_no_write:
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--replays", type=int, default=100)
@@ -479,9 +609,14 @@ def main():
     ap.add_argument("--pag", action="store_true", help="also time the perturbed-attention-guidance step (compile(..., pag=True), three guidance groups) against the plain CFG one, and count the entries of both steps")
     ap.add_argument("--lcm", action="store_true", help="also time the guidance-free step (cfg=False) against the CFG step for DPM++2M and LCM, and LCM-4 cfg=False end to end")
     ap.add_argument("--sd2", action="store_true", help="a run of its own: the SD-2.x step (SD21, v-prediction, CFG rescale), the rescaled tail alone and the OpenCLIP text tower; writes profiles/sampler_bench_sd2.json")
+    ap.add_argument("--sdxl", action="store_true", help="a run of its own: the SDXL base step, start() with the time-embedding rows in one pass against one pass per timestep, both text towers; writes profiles/sampler_bench_sdxl.json")
+    ap.add_argument("--sdxl-side", type=int, default=128, help="with --sdxl: the latent's side (default 128: a 1024 x 1024 image)")
+    ap.add_argument("--sdxl-no-write", action="store_true", help="with --sdxl: print the result only")
     args = ap.parse_args()
     if args.sd2:
         return sd2_bench(args)
+    if args.sdxl:
+        return sdxl_bench(args)
 
     import torch  # noqa: F401  (the weight arena is a torch allocation)
     import tinyfusers_amd.storage.tensor as T
