@@ -372,6 +372,19 @@ int tf_sdpa_pag_16(int dtype, void* o, const void* q, const void* k, const void*
                    long long q_st, long long k_sb, long long k_sh, long long k_st, long long v_sb, long long v_sh, long long v_st, long long o_sb, long long o_sh,
                    long long o_st, int pag_b0, int pag_b1, const float* pag_flag_dev, tfStream_t s);
 int tf_sdpa_pag_instance(int dtype, int B, int NH, int Tq, int Tk, int HS, long long k_st, long long v_st, int pag_b0, int pag_b1);
+/* ---- temporal attention of a video latent (the attention of an AnimateDiff motion module; attention/sdpa.py:53-77 with the F frames of ONE pixel as
+ * the tokens): for every video g < G, pixel p < P and head h < NH, o[g, f, p, h, :] = softmax_f'(q'[f] . k'[f'] / sqrt HS) v'[f'] over the F frames.
+ * Element (g, f, p, h, c) of a tensor x lies at x + (g F + f) x_sf + p x_sp + h x_sh + c: a frame, a pixel and a head stride (elements) per tensor, the
+ * videos F frame strides apart -- q, k, v are read where a fused q|k|v projection left them (column views of a (G F, P, 3 C) buffer: x_sf = 3 C P,
+ * x_sp = 3 C, x_sh = HS) and o is written as the (G F, P, C) token matrix the output projection reads; nothing is transposed or copied.  pe_q, pe_k,
+ * pe_v: optional fp32 tables of shape (F, NH HS) ON THE DEVICE, added in fp32 as the operand is loaded, q' = q + pe_q[f] (NULL: zero) -- the motion
+ * module's (LN(x) + pe) W = LN(x) W + pe W with pe W precomputed.  Scores, softmax and P V are fp32 (fixed summation order, no atomics: deterministic);
+ * the output is rounded once.  1 <= F <= 32 (more: TF_E_UNSUPPORTED), HS % 8 == 0 in [8, 160], NH >= 1, any G, P >= 0 (0: nothing to do); every stride
+ * a multiple of 8 elements, every pointer 16-byte aligned; what is not returns TF_E_ARG with a message before the device is touched.  Profiled in
+ * family 4 with 4 G P NH F^2 HS FLOPs. */
+int tf_sdpa_temporal_16(int dtype, void* o, const void* q, const void* k, const void* v, const float* pe_q, const float* pe_k, const float* pe_v, int G, int F,
+                        int P, int NH, int HS, long long q_sf, long long q_sp, long long q_sh, long long k_sf, long long k_sp, long long k_sh, long long v_sf,
+                        long long v_sp, long long v_sh, long long o_sf, long long o_sp, long long o_sh, tfStream_t s);
 /* row softmax over (N, C) fp32 -- Device.softmax (storage/device.py:129-157; softmax_func.cu:22-113) */
 int tf_softmax_rows_f32(void* out, const void* inp, int N, int C, tfStream_t s);
 /* softmax step of the UNFUSED attention (attention/sdpa.py:63-75 as the reference runs it: scale * matmul, + mask (:67-68: bool ->

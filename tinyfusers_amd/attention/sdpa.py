@@ -65,6 +65,18 @@ def sdpa_pag_instance(dtype, B, NH, Tq, Tk, HS, k_st=None, v_st=None, batch_rang
     return SDPA_INSTANCES[rc]
 
 
+def sdpa_temporal_strided(o, q, k, v, G, F, P, NH, HS, qs, ks, vs, os_, pe_q=None, pe_k=None, pe_v=None):
+    """Raw launch of the temporal attention (tf_sdpa_temporal_16): for every video g, pixel p and head h the F <= 32 frames of the pixel attend to each
+    other.  q / k / v / o are DeviceArrays (or views) whose element (g, f, p, h, c) lies at (g F + f) sf + p sp + h sh + c; *s = (frame, pixel, head)
+    element strides.  pe_*: optional fp32 DeviceArrays of shape (F, NH HS) added to the operand in fp32 as it is loaded (None: zero)."""
+    assert dtag(q.dtype) == dtag(k.dtype) == dtag(v.dtype) == dtag(o.dtype), "sdpa_temporal: q / k / v / o must hold the same 16-bit type"
+    for t in (pe_q, pe_k, pe_v):
+        assert t is None or (t.dtype == np.float32 and tuple(t.shape) == (F, NH * HS)), "sdpa_temporal: a positional table is fp32 of shape (F, NH HS)"
+    pe = [None if t is None else t.ptr for t in (pe_q, pe_k, pe_v)]
+    hip.tf_sdpa_temporal_16(dtag(q.dtype), o.ptr, q.ptr, k.ptr, v.ptr, *pe, G, F, P, NH, HS, *qs, *ks, *vs, *os_, _sh())
+    return o
+
+
 def _is_causal_mask(m, tq, tk):
     m = np.asarray(m)
     if m.shape[-2:] != (tq, tk):

@@ -145,6 +145,14 @@ def get_alphas_cumprod(beta_start=0.00085, beta_end=0.0120, n_training_steps=N_T
     return np.cumprod(alphas, axis=0)
 
 
+def linear_alphas_cumprod(beta_start=0.00085, beta_end=0.0120, n_training_steps=N_TRAIN):
+    """The LINEAR-beta training table (betas evenly spaced from beta_start to beta_end, where get_alphas_cumprod spaces their square roots): what the
+    AnimateDiff motion modules were trained with.  To be handed to ``schedule(alphas_cumprod=)``; the default table stays get_alphas_cumprod's.  Host
+    float64 products, returned as fp32 like the default table."""
+    betas = np.linspace(beta_start, beta_end, n_training_steps, dtype=np.float64)
+    return np.cumprod(1.0 - betas, axis=0).astype(np.float32)
+
+
 def default_timesteps(steps):
     """example/sd1.py:54: range(1, 1000, 1000 // steps), walked high to low."""
     steps = int(steps)
