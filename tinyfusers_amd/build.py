@@ -26,9 +26,9 @@ SOURCES = ["gemm_k_pp16.hip", "gemm_k_pp16_bf16.hip", "gemm_k_pp8.hip", "gemm_k_
            "sdpa_dual.hip", "sdpa_dual_bf16.hip", "sdpa_pag.hip", "sdpa_pag_bf16.hip", "sdpa_temporal.hip", "sdpa_temporal_bf16.hip", "gemm_k_igemm8.hip", "gemm_k_c4.hip", "gemm_k_c4_bf16.hip", "gemm_k_c8.hip", "gemm_k_c8_bf16.hip", "gemm_k_ar.hip", "gemm_k_ar_bf16.hip", "gemm_k_pp3.hip", "gemm_k_pp3_bf16.hip", "gemm.hip", "gemm_reduce.hip", "norm.hip", "elementwise.hip", "runtime.hip", "sgemm.hip",
            "comm.hip", "rtc.hip", "sampler.hip", "img2img.hip", "control.hip", "lora.hip", "vit.hip", "freeu.hip", "adm.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function", "-ffp-contract=fast"]
-# sdpa.hip: keep the MFMA accumulators in VGPRs (the softmax reads every score: no v_accvgpr_read traffic) and drop
-# the NaN-canonicalising v_max in front of every fmaxf on MFMA outputs (scores are never NaN; -inf masks still work)
-SDPA_UNITS = ["sdpa.hip", "sdpa_bf16.hip", "sdpa_split.hip", "sdpa_split_bf16.hip", "sdpa_dual.hip", "sdpa_dual_bf16.hip", "sdpa_pag.hip", "sdpa_pag_bf16.hip"]     # sdpa.hip itself and the units that #include it
+# the key-tile attention kernels (k_sdpa, and k_sdpa_dma / _split / _dual / _pag around sdpa_dma_body.inc): keep the MFMA accumulators in VGPRs (the softmax
+# reads every score: no v_accvgpr_read traffic) and drop the NaN-canonicalising v_max in front of every fmaxf on MFMA outputs (scores are never NaN; -inf masks still work)
+SDPA_UNITS = ["sdpa.hip", "sdpa_bf16.hip", "sdpa_split.hip", "sdpa_split_bf16.hip", "sdpa_dual.hip", "sdpa_dual_bf16.hip", "sdpa_pag.hip", "sdpa_pag_bf16.hip"]
 EXTRA = {s: ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans"] for s in SDPA_UNITS}
 
 
@@ -70,7 +70,7 @@ def build(force=False, verbose=False, ablation=False, tag=None, defs=(), asan_ho
         src = os.path.join(CSRC, s)
         obj = os.path.join(objdir, s.replace(".hip", ".o"))
         objs.append(obj)
-        twin = [os.path.join(CSRC, "sdpa.hip"), os.path.join(CSRC, s.replace("_bf16.hip", ".hip"))] if s in SDPA_UNITS else [os.path.join(CSRC, s.replace("_bf16.hip", ".hip"))] if s.endswith("_bf16.hip") else []
+        twin = [os.path.join(CSRC, s.replace("_bf16.hip", ".hip"))] if s.endswith("_bf16.hip") else []
         if force or _stale(obj, [src] + twin + headers):
             jobs.append([hipcc] + FLAGS + (["-DTF_ABLATION"] if ablation else []) + (ASAN_FLAGS if asan_host else []) + list(defs) + EXTRA.get(s, []) + ["-c", src, "-o", obj])
 

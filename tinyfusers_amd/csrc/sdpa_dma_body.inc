@@ -1,5 +1,7 @@
-// Body of the LDS-DMA attention kernels, #included into k_sdpa_dma (KS = 1, SR = 0 as local constants), k_sdpa_split and k_sdpa_dual (sdpa.hip): one
-// text, three __global__ functions -- a shared __device__ function, even force-inlined, changed the code of the shipped k_sdpa_dma instances.
+// Body of the LDS-DMA attention kernels, #included into k_sdpa_dma (sdpa_dma.h; KS = 1, SR = 0 as local constants), k_sdpa_split (sdpa_split.hip), k_sdpa_dual
+// (sdpa_dual.hip) and k_sdpa_pag (sdpa_pag.hip): one text, four __global__ functions -- a shared __device__ function, even force-inlined, changed the code of the
+// shipped k_sdpa_dma instances.  So did, later, a __device__ function for the piece-offset arithmetic alone, which voff[] and the dual form's image tile both spell
+// out below (profiles/sdpa_refactor_code_identity.txt): the two copies stay.
 // In scope: template parameters HS, QT, DBG, NW, BF; constants KS (key slices), SR (stages per ring when KS > 1); the kernel argument `p`.
 //
 // TF_SDPA_BODY_DUAL (a compile-time flag, #defined to 1 around the #include in k_sdpa_dual only; KS = 1, DBG = 0, no causal mask; also in scope: `pd`,

@@ -2,8 +2,7 @@
 // launch (tf_sdpa_pag_16; attention/attention.py:35-41 with the softmax replaced by the identity matrix for the perturbed guidance group).  k_sdpa_pag
 // is k_sdpa_dma's body (sdpa_dma_body.inc, untouched) behind a block-uniform early-out, in a translation unit of its own: the code objects of sdpa.hip,
 // sdpa_split.hip and sdpa_dual.hip stay what they were without it.
-#define TF_TU_PAG 1
-#include "sdpa.hip"
+#include "sdpa_common.h"
 
 struct SdpaPagP {
   SdpaP p;                 // the launch as tf_sdpa_16 would fill it (causal = 0)
@@ -49,7 +48,9 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(sd
     constexpr int QB0 = 16 * NW * QT;
     const int nqb0 = (p.Tq + QB0 - 1) / QB0, per_b = nqb0 * p.NH, nblk0 = per_b * p.B;
     const int q0 = nblk0 >> 3, r0 = nblk0 & 7, xcd0 = blockIdx.x & 7;
-    const int bid0 = (xcd0 < r0 ? xcd0 * (q0 + 1) : r0 * (q0 + 1) + (xcd0 - r0) * q0) + (blockIdx.x >> 3);      // sdpa_block's remap
+    // sdpa_block's remap, restated: the shift here is the unsigned blockIdx's, sdpa_block's an int's, and a helper serving both merges the two computations,
+    // which takes two instructions out of every k_sdpa_pag instance (profiles/sdpa_refactor_code_identity.txt) -- the code objects are to stay what they were
+    const int bid0 = (xcd0 < r0 ? xcd0 * (q0 + 1) : r0 * (q0 + 1) + (xcd0 - r0) * q0) + (blockIdx.x >> 3);
     if (bid0 >= pp.b0 * per_b && bid0 < pp.b1 * per_b && *pp.flag != 0.f) {
       const SdpaBlk blk0 = sdpa_block(p, QB0);
       const int t0 = blk0.qb * QB0;
@@ -63,43 +64,20 @@ __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(sd
 
 template <int HS, int QT, int NW = 4>
 static int launch_sdpa_pag(const SdpaPagP& pp, hipStream_t st) {
-  constexpr int smem = sdpa_ring(SdpaDma<HS>::STAGE_B, NW, SdpaDma<HS>::S) * SdpaDma<HS>::STAGE_B;      // k_sdpa_dma<HS, QT, 0, NW>'s ring
-  constexpr int QB = 16 * NW * QT;
-  static bool attr_set = false;
-  if (!attr_set) {
-    TF_HIP(hipFuncSetAttribute((const void*)k_sdpa_pag<HS, QT, NW, kBF>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((k_sdpa_pag<HS, QT, NW, kBF>), dim3((unsigned)((pp.p.Tq + QB - 1) / QB * pp.p.NH * pp.p.B)), dim3(NW * 64), smem, st, pp);
-  TF_LAUNCH_CHECK();
-  return TF_OK;
-}
-
-template <int QT, int NW = 4>
-static int launch_sdpa_pag_hs(const SdpaPagP& pp, hipStream_t st) {
-  switch (pp.p.HS) {
-    case 40: return launch_sdpa_pag<40, QT, NW>(pp, st);
-    case 64: return launch_sdpa_pag<64, QT, NW>(pp, st);
-    case 80: return launch_sdpa_pag<80, QT, NW>(pp, st);
-    case 128: return launch_sdpa_pag<128, QT, NW>(pp, st);
-    default: return launch_sdpa_pag<160, QT, NW>(pp, st);
-  }
+  return launch_sdpa_kernel<k_sdpa_pag<HS, QT, NW, kBF>>(pp, pp.p, sdpa_ring_bytes<HS, NW>(), 16 * NW * QT, NW, st);      // k_sdpa_dma<HS, QT, 0, NW>'s ring
 }
 
 int tfk_sdpa_pag_bf16(const SdpaPagP& pp, int inst, hipStream_t st);
 int TFK(tfk_sdpa_pag)(const SdpaPagP& pp, int inst, hipStream_t st) {
-  if (inst == TF_SDPA_INST_DMA16) return launch_sdpa_pag_hs<1>(pp, st);
-  if (inst == TF_SDPA_INST_DMA32_W8) return pp.p.HS == 40 ? launch_sdpa_pag<40, 2, 8>(pp, st) : launch_sdpa_pag<80, 2, 8>(pp, st);     // (the rule names it for 40 and 80 only)
-  return launch_sdpa_pag_hs<2>(pp, st);
+  if (inst == TF_SDPA_INST_DMA16) return sdpa_by_head_size<40, 64, 80, 128, 160>(pp.p.HS, [&](auto hs) { return launch_sdpa_pag<hs, 1>(pp, st); });
+  if (inst == TF_SDPA_INST_DMA32_W8) return sdpa_by_head_size<40, 80>(pp.p.HS, [&](auto hs) { return launch_sdpa_pag<hs, 2, 8>(pp, st); });     // (the rule names it for 40 and 80 only)
+  return sdpa_by_head_size<40, 64, 80, 128, 160>(pp.p.HS, [&](auto hs) { return launch_sdpa_pag<hs, 2>(pp, st); });
 }
 
 #if !TF_TU_BF
-// Which family a perturbed launch runs: the one sdpa_instance names with the split forms left out (tf_sdpa_dual_16's rule), among the LDS-DMA
-// families.  0: a key set no kernel can address; < 0: the rule names the generic kernel, which has no perturbed instance.
+// Which family a perturbed launch runs: sdpa_unsplit_dma_rule (tf_sdpa_dual_16's rule too); the generic kernel has no perturbed instance
 static int sdpa_pag_rule(int B, int NH, int Tq, int Tk, int HS, long long k_st, long long v_st) {
-  if (!(((long long)Tk * k_st + HS) * 2 < (1ll << 31) && ((long long)Tk * v_st + HS) * 2 < (1ll << 31))) return 0;
-  const int inst = tfk_sdpa_instance_unsplit(B, NH, Tq, HS);
-  return inst == TF_SDPA_INST_DMA16 || inst == TF_SDPA_INST_DMA32 || inst == TF_SDPA_INST_DMA32_W8 ? inst : -1;
+  return sdpa_unsplit_dma_rule(B, NH, Tq, HS, sdpa_addressable(Tk, HS, k_st, v_st));
 }
 static int sdpa_pag_refuse(const char* who, int rule, int Tk, int HS, long long k_st, long long v_st) {
   if (rule == 0) return sdpa_refuse(who, Tk, HS, k_st, v_st);
@@ -108,10 +86,9 @@ static int sdpa_pag_refuse(const char* who, int rule, int Tk, int HS, long long 
 }
 // the checks on sizes, strides and the batch range shared by the launch and the query; 0 or a status with the message set
 static int sdpa_pag_args(const char* who, int dtype, int B, int NH, int Tq, int Tk, int HS, long long k_st, long long v_st, int b0, int b1) {
-  TF_REQUIRE(dtype == TF_DTYPE_F16 || dtype == TF_DTYPE_BF16, "%s: dtype=%d (0 = float16, 1 = bfloat16)", who, dtype);
-  TF_REQUIRE(B >= 0 && NH >= 1 && Tq >= 0 && Tk >= 1, "%s: bad sizes B=%d NH=%d Tq=%d Tk=%d", who, B, NH, Tq, Tk);
-  TF_REQUIRE(HS >= 8 && HS % 8 == 0 && HS <= 160, "%s: head size %d must be a multiple of 8 in [8, 160]", who, HS);
-  TF_REQUIRE(k_st % 8 == 0 && v_st % 8 == 0, "%s: k / v strides must be multiples of 8 elements (16-B rows)", who);
+  if (int rc = sdpa_check_shape(who, &dtype, B, NH, Tq, Tk, nullptr, HS, 0)) return rc;
+  const long long str[] = {k_st, v_st};
+  if (int rc = sdpa_check_strides(who, "k / v", str, 2)) return rc;
   TF_REQUIRE(0 <= b0 && b0 <= b1 && b1 <= B, "%s: the perturbed batch range [%d, %d) must lie in [0, B = %d] (an empty range is plain attention)", who, b0, b1, B);
   return TF_OK;
 }
@@ -126,27 +103,18 @@ extern "C" int tf_sdpa_pag_instance(int dtype, int B, int NH, int Tq, int Tk, in
 extern "C" int tf_sdpa_pag_16(int dtype, void* o, const void* q, const void* k, const void* v, int B, int NH, int Tq, int Tk, int HS, long long q_sb, long long q_sh,
                               long long q_st, long long k_sb, long long k_sh, long long k_st, long long v_sb, long long v_sh, long long v_st, long long o_sb, long long o_sh,
                               long long o_st, int pag_b0, int pag_b1, const float* pag_flag_dev, tfStream_t s) {
-  TF_REQUIRE(o && q && k && v, "tf_sdpa_pag_16: null tensor");
-  TF_REQUIRE(pag_flag_dev, "tf_sdpa_pag_16: null flag (the device address of one fp32 word)");
-  if (int rc = sdpa_pag_args("tf_sdpa_pag_16", dtype, B, NH, Tq, Tk, HS, k_st, v_st, pag_b0, pag_b1)) return rc;
-  TF_REQUIRE((long long)((Tq + 63) / 64) * NH * B < (1ll << 31), "tf_sdpa_pag_16: too many (query block, head, batch) work items");
-  const long long str[] = {q_sb, q_sh, q_st, k_sb, k_sh, v_sb, v_sh};
-  for (int i = 0; i < 7; ++i) TF_REQUIRE(str[i] % 8 == 0, "tf_sdpa_pag_16: q / k / v strides must be multiples of 8 elements (16-B rows)");
-  TF_REQUIRE(o_sb % 4 == 0 && o_sh % 4 == 0 && o_st % 4 == 0, "tf_sdpa_pag_16: output strides must be multiples of 4 elements");
-  if (B == 0 || Tq == 0) return TF_OK;
+  const char* who = "tf_sdpa_pag_16";
+  TF_REQUIRE(o && q && k && v, "%s: null tensor", who);
+  TF_REQUIRE(pag_flag_dev, "%s: null flag (the device address of one fp32 word)", who);
+  if (int rc = sdpa_pag_args(who, dtype, B, NH, Tq, Tk, HS, k_st, v_st, pag_b0, pag_b1)) return rc;
   SdpaPagP pp;
-  SdpaP& p = pp.p;
-  p.q = (const half_t*)q; p.k = (const half_t*)k; p.v = (const half_t*)v; p.o = (half_t*)o;
-  p.B = B; p.NH = NH; p.Tq = Tq; p.Tk = Tk; p.HS = HS;
-  p.q_sb = q_sb; p.q_sh = q_sh; p.q_st = q_st; p.k_sb = k_sb; p.k_sh = k_sh; p.k_st = k_st;
-  p.v_sb = v_sb; p.v_sh = v_sh; p.v_st = v_st; p.o_sb = o_sb; p.o_sh = o_sh; p.o_st = o_st;
-  p.scale_log2e = (1.0f / sqrtf((float)HS)) * 1.4426950408889634f;
-  p.causal = 0;
-  p.dbg = 0;
+  pp.p = sdpa_params(o, q, k, v, B, NH, Tq, Tk, HS, q_sb, q_sh, q_st, k_sb, k_sh, k_st, v_sb, v_sh, v_st, o_sb, o_sh, o_st, 0);
   pp.flag = pag_flag_dev; pp.b0 = pag_b0; pp.b1 = pag_b1;
+  if (int rc = sdpa_check_launch(who, "q / k / v", pp.p)) return rc;
+  if (B == 0 || Tq == 0) return TF_OK;
   // the instance is decided (and a shape without one refused) before anything touches the device
   const int rule = sdpa_pag_rule(B, NH, Tq, Tk, HS, k_st, v_st);
-  if (rule <= 0) return sdpa_pag_refuse("tf_sdpa_pag_16", rule, Tk, HS, k_st, v_st);
+  if (rule <= 0) return sdpa_pag_refuse(who, rule, Tk, HS, k_st, v_st);
   hipStream_t st = tf_hs(s);
   TfProfScope prof_(TF_PROF_FAM_SDPA, 4.0 * B * NH * (double)Tq * Tk * HS, st);      // (booked as the plain launch: what runs depends on a device word)
   return dtype == TF_DTYPE_BF16 ? tfk_sdpa_pag_bf16(pp, rule, st) : tfk_sdpa_pag(pp, rule, st);

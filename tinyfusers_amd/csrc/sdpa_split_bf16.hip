@@ -1,4 +1,3 @@
 // bfloat16 twins of the key-slice attention instances the launcher routes to (sdpa_split.hip)
 #define TF_TU_BF 1
-#define TF_TU_SPLIT 1
-#include "sdpa.hip"
+#include "sdpa_split.hip"
