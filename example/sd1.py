@@ -22,6 +22,7 @@ BASELINE config 3: full 50-step sampler, batch 1, end-to-end img/s.
     python -m example.sd1 --sd2 --steps 20 --sampler dpmpp2m --prediction v --cfg-rescale 0.7   # Stable Diffusion 2.x: OpenCLIP context, heads of 64, v-prediction, CFG rescale
     python -m example.sd1 --ckpt v2-1_768-ema-pruned.safetensors --steps 20 --sampler dpmpp2m --prediction v --cfg-rescale 0.7   # ... from a checkpoint (768-v: --prediction v)
     python -m example.sd1 --sdxl --steps 20 --sampler dpmpp2m [--ckpt sd_xl_base_1.0.safetensors] [--size 1024]   # SDXL base: two text towers, pooled / size conditioning
+    python -m example.sd1 --steps 20 --sampler dpmpp2m --motion [mm_sd_v15_v2.ckpt] --frames 16 [--motion-scale 1.0] [--size 512] --out frames.npy   # AnimateDiff: one 16-frame video, (F, H, W, 3) uint8
 With --ckpt the configuration is read off the checkpoint: its conv_in (4, 9 or 8 input channels), and SD-2.x when the cross-attention keys read a
 1024-wide context; --concat / --sd2 pick it on synthetic weights.  The parameterisation is NOT in the file: --prediction defaults to eps.
 """
@@ -116,6 +117,88 @@ def run_sdxl(ap, args):
         np.save(args.out, x)
 
 
+def run_motion(ap, args):
+    """--motion [FILE]: text to video with AnimateDiff motion modules on SD-1.5 -- one video of --frames frames under one prompt, the linear-beta
+    schedule the motion modules were trained with, every frame decoded by the VAE; --out gets the (F, H, W, 3) uint8 frames."""
+    import contextlib
+    import io
+    if not args.sampler:
+        ap.error("--motion needs --sampler")
+    for flag, name in ((args.concat, "--concat"), (args.control_image, "--control-image"), (args.ip_adapter is not None, "--ip-adapter"), (args.freeu is not None, "--freeu"),
+                       (args.pag is not None, "--pag"), (args.init_image, "--init-image"), (args.sd2, "--sd2")):
+        if flag:
+            ap.error(f"{name} with --motion is not supported")
+    if args.size < 64 or args.size % 64 or args.size > 1024:
+        ap.error(f"--size {args.size}: expected a multiple of 64 up to 1024")
+    import tinyfusers_amd.storage.tensor as T
+    from tinyfusers_amd.storage.state import param_shapes, update_state
+    from tinyfusers_amd.storage.synth import synth_motion_state_dict, synth_state_dict
+    from tinyfusers_amd.variants.samplers import linear_alphas_cumprod, make
+    from tinyfusers_amd.variants.sd import StableDiffusion
+    from tinyfusers_amd.vision.motion import MotionAdapter
+    from tinyfusers_amd.vision.unet import SD15
+    t0 = time.time()
+    T.ensure_init(0)
+    model = StableDiffusion(SD15)
+    if args.ckpt:
+        from tinyfusers_amd.storage.unpicker import load_checkpoint
+        state = load_checkpoint(args.ckpt)
+    else:
+        state = synth_state_dict(param_shapes(model), 0)
+    with contextlib.redirect_stdout(io.StringIO()):
+        update_state(model, state, "")
+    del state
+    adapter = MotionAdapter.load(SD15, args.motion or synth_motion_state_dict(SD15, 1, max_len=24))
+    if not 1 <= args.frames <= min(32, adapter.max_len):
+        ap.error(f"--frames {args.frames}: this motion module takes 1 .. {min(32, adapter.max_len)} frames")
+    model.attach_motion(adapter)
+    print(f"weights installed in {time.time() - t0:.1f}s: {len(adapter.modules)} motion modules, max_len {adapter.max_len}" + (", mid_block" if adapter.mid else ""))
+    if args.lora:
+        names = [model.load_lora(spec.split(":")[0], name=f"{i}") for i, spec in enumerate(args.lora)]
+        model.set_adapters(names, [float(spec.split(":")[1]) if ":" in spec else 1.0 for spec in args.lora])
+    if args.vocab:
+        from tinyfusers_amd.tokenizer.clip import ClipTokenizer
+        tok = ClipTokenizer(args.vocab)
+        prompt, empty = np.array([tok.encode(args.prompt)]), np.array([tok.encode("")])
+    else:
+        rng = np.random.default_rng(args.seed)
+        prompt = np.full((1, 77), 49407, dtype=np.int64); prompt[0, 0] = 49406; prompt[0, 1:10] = rng.integers(0, 49406, 9)
+        empty = np.full((1, 77), 49407, dtype=np.int64); empty[0, 0] = 49406
+    text_model = model.cond_stage_model.transformer.text_model
+    context = text_model(prompt)                                 # ONE prompt for the video: compile broadcasts it to the frames
+    unc = None if args.no_cfg else text_model(empty)
+    side, f = args.size // 8, args.frames
+    latent = model.latent_from_numpy(np.zeros((f, 4, side, side), np.float32))
+    schedule = make(args.sampler, args.eta).schedule(args.steps, alphas_cumprod=linear_alphas_cumprod())
+    model.compile(unc, context, latent, sampler=schedule, cfg=not args.no_cfg, prediction=args.prediction, cfg_rescale=args.cfg_rescale is not None,
+                  motion=True, frames=f)
+    if args.cfg_rescale is not None:
+        model.set_cfg_rescale(args.cfg_rescale)
+    if args.motion_scale is not None:
+        model.set_motion_scale(args.motion_scale)
+    times = []
+    for n in range(args.images + 1):
+        model.start(seed=args.seed, image_offset=n * f)
+        model.synchronize()
+        t0 = time.perf_counter()
+        model.run(None if args.no_cfg else args.guidance)
+        model.synchronize()
+        t1 = time.perf_counter()
+        assert np.isfinite(latent.numpy()).all(), f"video {n}: the sampler produced a non-finite latent"
+        per = latent.size // f
+        with T.use_stream(model._stream):
+            frames = np.stack([model.decode(latent.view((1, 4, side, side), "row", k * per)) for k in range(f)])
+        t2 = time.perf_counter()
+        times.append((t1 - t0, t2 - t1))
+        print(f"video {n}: {args.steps} steps {1e3 * (t1 - t0):.1f} ms ({args.steps / (t1 - t0):.1f} steps/s), decode of {f} frames {1e3 * (t2 - t1):.1f} ms, "
+              f"frames {frames.shape} {frames.dtype} mean {frames.mean():.1f}")
+    s, d = (np.median([t[i] for t in times[1:]]) for i in range(2)) if len(times) > 1 else times[0]
+    print(f"end-to-end (sampler + VAE decode, one video of {f} frames): {f / (s + d):.3f} frames/s")
+    if args.out:
+        np.save(args.out, frames)
+        print(f"wrote {frames.shape} {frames.dtype} to {args.out}")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(description="Run the SD-1.x sampler on MI355X (synthetic weights)")
     ap.add_argument("--steps", type=int, default=50)
@@ -172,11 +255,25 @@ if __name__ == "__main__":
                     help="CFG rescale inside the captured step (needs --sampler and a guidance pair): the factor phi in [0, 1]; 0.7 is the value usually quoted with v-prediction")
     ap.add_argument("--sdxl", action="store_true", help="the SDXL base configuration (needs --sampler): two text towers, pooled / size conditioning through start(); "
                                                          "--ckpt FILE: an SGM checkpoint (sd_xl_base_1.0), synthetic weights without one")
-    ap.add_argument("--size", type=int, default=1024, help="with --sdxl: the image's side in pixels, a multiple of 64 (default 1024)")
+    ap.add_argument("--size", type=int, default=None, help="with --sdxl or --motion: the image's side in pixels, a multiple of 64 (default 1024 / 512)")
+    ap.add_argument("--motion", nargs="?", const="", default=None, metavar="FILE",
+                    help="text to video with AnimateDiff motion modules (needs --sampler): a motion-module file (mm_sd_v15*.ckpt / .safetensors, AnimateDiff or "
+                         "diffusers names); without FILE: synthetic module weights.  --out then holds the (F, H, W, 3) uint8 frames")
+    ap.add_argument("--frames", type=int, default=16, help="with --motion: the frames of the video, 1 .. min(32, the file's max_len) (default 16)")
+    ap.add_argument("--motion-scale", type=float, default=None, help="with --motion: the strength of the modules' residual branch (default 1.0)")
     args = ap.parse_args()
+    if args.size is None:
+        args.size = 512 if args.motion is not None else 1024
     if args.sdxl:
+        if args.motion is not None:
+            ap.error("--motion with --sdxl is not supported")
         run_sdxl(ap, args)
         sys.exit(0)
+    if args.motion is not None:
+        run_motion(ap, args)
+        sys.exit(0)
+    if args.motion_scale is not None:
+        ap.error("--motion-scale needs --motion")
     if (args.prediction == "v" or args.cfg_rescale is not None) and not args.sampler:
         ap.error("--prediction v and --cfg-rescale need --sampler")
     if args.cfg_rescale is not None and not 0.0 <= args.cfg_rescale <= 1.0:

@@ -10,7 +10,7 @@ import zlib
 
 import numpy as np
 
-__all__ = ["synth_tensor", "synth_state_dict", "synth_normal"]
+__all__ = ["synth_tensor", "synth_state_dict", "synth_normal", "synth_motion_state_dict"]
 
 
 def _rng(seed, name):
@@ -48,3 +48,26 @@ def synth_tensor(seed, name, shape):
 def synth_state_dict(shapes, seed=0, prefix=""):
     """name -> fp16 array for every entry of ``shapes`` (name -> shape)."""
     return {prefix + k: synth_tensor(seed, k, s) for k, s in shapes.items()}
+
+
+def synth_motion_state_dict(cfg, seed=0, max_len=32, mid=False, pe=True):
+    """A synthetic AnimateDiff motion-module file for the UNet configuration ``cfg`` (vision/motion.py: names in the AnimateDiff repository's
+    spelling), name -> fp16 array: projection weights ~ N(0, 1 / fan_in), their bias ~ N(0, 0.02^2), every norm's gamma ~ 1 + 0.1 N and beta ~ 0.1 N,
+    the positional tables the sinusoid + 0.1 N (``pe=False``: a file without them).  ``proj_out`` is NOT zero: the published files' zero-initialised
+    proj_out has been trained away from zero, and a zero one would hide the whole module from a test."""
+    from ..vision.motion import module_shapes, motion_slots, sinusoid_pe
+    out = {}
+    for prefix, _, c in motion_slots(cfg, mid):
+        for rel, shape in module_shapes(c, max_len, pe).items():
+            name = f"{prefix}.temporal_transformer.{rel}"
+            x = _rng(seed, name).standard_normal(size=shape, dtype=np.float32)
+            if rel.endswith(".pe"):
+                x = sinusoid_pe(max_len, c) + np.float32(0.1) * x
+            elif len(shape) == 2:
+                x *= np.float32(1.0 / np.sqrt(shape[1]))
+            elif rel.startswith("norm.") or ".norms." in rel or ".ff_norm." in rel:
+                x = (np.float32(1.0) + np.float32(0.1) * x) if rel.endswith(".weight") else np.float32(0.1) * x
+            else:
+                x *= np.float32(0.02)
+            out[name] = x.astype(np.float16)
+    return out

@@ -208,17 +208,43 @@ def adm_size_ids(original_size, crop_top_left, target_size, batch, height, width
     return adm_ids(np.concatenate(cols, axis=1), batch, "original_size / crop_top_left / target_size")
 
 
+MOTION_MAX_FRAMES = 32            # tf_sdpa_temporal_16's F (vision/motion.py::MAX_FRAMES)
 DUAL_HEAD_SIZES = (40, 80, 160)     # the head sizes tf_sdpa_dual_16 (an IP-Adapter's cross-attention) has instances for
 
 
 def check_compile(cin, has_control_net, config, latent, sampler, inpaint, concat, control, cfg=True, ip_adapter=False, has_ip_adapter=False,
-                  freeu=False, freeu_plan=(), pag=False, pag_table=(), prediction="eps", cfg_rescale=False, head_sizes=(), adm=False):
+                  freeu=False, freeu_plan=(), pag=False, pag_table=(), prediction="eps", cfg_rescale=False, head_sizes=(), adm=False, motion=False,
+                  has_motion=False, frames=None, motion_max_len=0):
     """compile()'s refusals, before any device work: ``cin`` the UNet's in_channels, ``config`` the package's config module, ``freeu_plan`` the
     UNet's vision/unet.py::freeu_stages rows (stage, block, backbone channels, skip channels, latent size divisor), ``pag_table`` its
     vision/unet.py::pag_layers paths, ``head_sizes`` its vision/unet.py::head_sizes (read for ip_adapter=True), ``adm`` whether the UNet is
-    vector-conditioned (UNetConfig.adm_in_channels: SDXL)."""
+    vector-conditioned (UNetConfig.adm_in_channels: SDXL), ``has_motion`` whether a MotionAdapter is attached and ``motion_max_len`` the frames its
+    positional tables hold (read for motion=True)."""
     def refuse(exc, text):
         raise exc(f"StableDiffusion.compile: {text}")
+    if motion:   # the video step runs cfg=True / False, every sampler, prediction="v", cfg_rescale=True, img2img starts, bf16, LoRA; the rest is refused by name
+        if adm:
+            refuse(UnsupportedSamplerConfig, "motion=True on an SDXL model is not supported (the motion modules of AnimateDiff-SDXL have another block plan)")
+        if not has_motion:
+            refuse(ValueError, "motion=True needs an adapter: attach_motion(MotionAdapter.load(cfg, FILE)) first")
+        if sampler is None:
+            refuse(ValueError, "motion=True needs a sampler schedule (sampler=<Schedule>)")
+        for flag, name in ((control, "control=True (a ControlNet under the motion modules)"), (ip_adapter, "ip_adapter=True"), (concat is not None, f"concat={concat!r}"),
+                           (pag, "pag=True"), (freeu, "freeu=True"), (inpaint, "inpaint=True")):
+            if flag:
+                refuse(UnsupportedSamplerConfig, f"motion=True and {name} together are not supported")
+        if config.dtype == "fp8":
+            refuse(UnsupportedSamplerConfig, "motion=True runs in the fp16 and the bf16 step, not under the fp8 policy (config.set_dtype('fp8'))")
+        if config.cfg_parallel:
+            refuse(UnsupportedSamplerConfig, "a model with motion modules has no two-chain CFG form (TF_CFG_PARALLEL)")
+        top = min(MOTION_MAX_FRAMES, int(motion_max_len))
+        if isinstance(frames, bool) or not isinstance(frames, (int, np.integer)) or not 1 <= int(frames) <= top:
+            refuse(ValueError, f"motion=True needs frames=F with 1 <= F <= {top} (the adapter's positional tables hold {motion_max_len} frames, the temporal "
+                               f"attention launch takes {MOTION_MAX_FRAMES}), got frames={frames!r}")
+        if latent.shape[0] % int(frames):
+            refuse(ValueError, f"motion=True: the latent holds videos x frames images in (video, frame) order, a batch of {latent.shape[0]} is no multiple of frames={frames}")
+    elif frames is not None:
+        refuse(ValueError, f"frames={frames!r} belongs to motion=True")
     if adm:      # SDXL runs cfg=True / False, every sampler, img2img, inpaint=True, prediction="v", cfg_rescale=True, bf16; the rest is refused by name
         if sampler is None:
             refuse(UnsupportedSamplerConfig, "an SDXL model needs a sampler schedule (sampler=<Schedule>): its time-embedding rows depend on start(pooled=) and are built there")

@@ -25,6 +25,8 @@ guidance group whose self-attentions are the identity in the selected transforme
 ``StableDiffusion(SDXL)`` is the SDXL base model: a UNet with vector conditioning (``start(pooled=, original_size=, crop_top_left=, target_size=)``
 -- everything that depends on it is computed in ``start``, the captured step gains no launch), two text towers under ``conditioner.embedders``
 (``encode_prompt``), the SD-1.5 VAE tree at ``latent_scale`` 0.13025.
+``compile(..., motion=True, frames=F)`` is the AnimateDiff video step (vision/motion.py; ``attach_motion``, ``set_motion_scale``, ``start(motion_scale=)``): the
+latent holds V videos of F frames, every motion module runs inside the one graph, the strength of their residual branch changes without a re-capture.
 
 How the object is laid out.  Everything ``compile`` / ``start`` / ``set_context`` / ``set_adapters`` keep on the model is declared, with its
 "not compiled" value, in ``_reset_state``: ``__init__`` runs all of it, ``compile`` the per-compile part, so a re-compile with other flags drops the
@@ -93,6 +95,7 @@ class StableDiffusion:
         self.control_model = None        # a ControlNet (vision/controlnet.py), under the LDM checkpoint's name: attach_control sets it
         self._ip_model = None            # an IPAdapter (storage/ip_adapter.py): attach_ip_adapter sets it (private: no checkpoint of the model names it)
         self._clip_vision = None         # a ClipVision (vae/clip_vision.py): attach_clip_vision sets it; start(ip_image=) runs it
+        self._motion_model = None        # a MotionAdapter (vision/motion.py): attach_motion sets it (private: no checkpoint of the model names it)
         self._reset_state(everything=True)
 
     def _reset_state(self, everything=False):
@@ -117,6 +120,7 @@ class StableDiffusion:
         self._freeu, self._freeu_scales = False, None                # freeu=True: the device fp32 words [s1, s2, b1, b2]
         self._vpred, self._rescale, self._rescale_phi = False, False, None     # prediction="v"; cfg_rescale=True: the device fp32 word phi (in a 4-word block)
         self._ip, self._ip_model_compiled, self._ip_kv, self._ip_scales, self._ip_keep = False, None, None, None, None     # the adapter the step captured, ip_adapter=True: image-token K|V (G B, T, kv_n), the scales
+        self._motion, self._motion_compiled, self._frames, self._ctx_vid = False, None, None, None     # motion=True: the adapter the step captured, F, the per-video stacked context
         self._seed, self._image_offset, self._cursor = (0, 0), 0, 0  # what start() sets, step_sampler advances
         # a UNet with label_emb (SDXL): y (G B, adm) and label_emb(y) (G B, E), private buffers start(pooled=) fills; the schedule's table of
         # time-embedding rows (S G B, N) built there, and the serial that keys it (a new start invalidates the rows of the previous one)
@@ -168,6 +172,22 @@ class StableDiffusion:
         if self._ip_model is not None:
             self._check_tower_fits(tower, self._ip_model, "attach_clip_vision")
         self._clip_vision = tower
+        return self
+
+    def attach_motion(self, adapter):
+        """Give the model AnimateDiff motion modules (vision/motion.py::MotionAdapter) built for its UNet's configuration: ``compile(..., motion=True,
+        frames=F)`` then captures the video step.  The adapter never touches the UNet's weights; a step compiled with motion=False does not see it."""
+        from ..vision.motion import MotionAdapter
+        if not isinstance(adapter, MotionAdapter):
+            raise TypeError(f"StableDiffusion.attach_motion: takes a MotionAdapter, got {type(adapter).__name__}")
+        if adapter.cfg != self.model.diffusion_model.cfg:
+            raise ValueError(f"StableDiffusion.attach_motion: the adapter was built for {adapter.cfg}, the UNet is {self.model.diffusion_model.cfg}")
+        self._motion_model = adapter
+        return self
+
+    def detach_motion(self):
+        """Forget the motion modules.  A step compiled with motion=True keeps running on the modules it captured until the next compile."""
+        self._motion_model = None
         return self
 
     def detach_ip_adapter(self):
@@ -404,7 +424,7 @@ class StableDiffusion:
 
     # -- whole-step HIP graph ------------------------------------------------------------------------
     def compile(self, unconditional_context, context, latent, stream=None, warmup=2, timesteps=None, sampler=None, inpaint=False, concat=None, control=False,
-                cfg=True, ip_adapter=False, freeu=False, pag=False, prediction="eps", cfg_rescale=False):
+                cfg=True, ip_adapter=False, freeu=False, pag=False, prediction="eps", cfg_rescale=False, motion=False, frames=None):
         """Capture one denoising step for these (static) buffers into a HIP graph.  Afterwards
         ``step(timestep, a_t, a_prev, guidance)`` updates ``latent`` in place with one graph launch.
 
@@ -489,13 +509,28 @@ class StableDiffusion:
         tuned here); ``set_cfg_rescale`` and ``start(cfg_rescale=)`` change it without a re-capture, and at 0 the step computes the cfg_rescale=False
         step's bits.  With the defaults the tail is the entry it always was.  Neither runs under TF_CFG_PARALLEL.
 
+        ``motion=True, frames=F`` (with a sampler and an attached MotionAdapter, ``attach_motion``): the video step of AnimateDiff.  The latent is
+        (V F, 4, h, w), V videos of F frames in (video, frame) order, 1 <= F <= min(32, the adapter's max_len); every motion module runs at its slot of
+        the UNet (vision/unet.py::UNetModel._with_motion) on G V videos, G the guidance groups -- nine launches per module, the temporal attention
+        (tf_sdpa_temporal_16) among them, all inside the one graph; the positional tables pe W^T are built here, outside it.  The context has V F rows,
+        or V rows -- one prompt per video: its K|V is projected once per video in the hoist and the projected rows are replicated to the video's
+        frames (DESIGN 4.3 states the memory this costs).  ``set_motion_scale`` / ``start(motion_scale=)`` change the strength of the modules'
+        residual branch without a re-capture; it is 1 after compile.  Combines with cfg=False, every sampler, prediction="v", cfg_rescale=True,
+        image-to-image starts (an init_latent of V F frames), bf16 and LoRA on the UNet's own weights; not with control=True, ip_adapter=True, concat=,
+        pag=True, freeu=True, inpaint=True, the fp8 policy, TF_CFG_PARALLEL or an SDXL model, each refused by name.  With motion=False an attached
+        adapter changes nothing: the image step's bits and launches.
+
         The arguments are remembered: ``set_adapters`` (LoRA) on a compiled model swaps weight handles and calls ``compile`` again with the same ones."""
         inputs.check_compile(self.model.diffusion_model.cfg.in_channels, self.control_model is not None, config, latent, sampler, inpaint, concat, control, cfg,
                              ip_adapter=ip_adapter, has_ip_adapter=self._ip_model is not None, freeu=freeu,
                              freeu_plan=freeu_stages(self.model.diffusion_model.cfg) if freeu else (), pag=pag,
                              pag_table=pag_layers(self.model.diffusion_model.cfg) if pag else (), prediction=prediction, cfg_rescale=cfg_rescale,
                              head_sizes=head_sizes(self.model.diffusion_model.cfg) if ip_adapter else (),
-                             adm=bool(self.model.diffusion_model.cfg.adm_in_channels))
+                             adm=bool(self.model.diffusion_model.cfg.adm_in_channels), motion=bool(motion), has_motion=self._motion_model is not None,
+                             frames=frames, motion_max_len=self._motion_model.max_len if self._motion_model is not None else 0)
+        if motion and context.shape[0] not in (latent.shape[0], latent.shape[0] // int(frames)):
+            raise ValueError(f"StableDiffusion.compile: motion=True takes one context row per frame ({latent.shape[0]}) or per video ({latent.shape[0] // int(frames)}), "
+                             f"got {context.shape[0]}")
         if (ip_adapter or pag) and warmup < 1:
             raise ValueError(f"StableDiffusion.compile: {'ip_adapter' if ip_adapter else 'pag'}=True needs warmup >= 1 (the first launch of an attention instance cannot be captured)")
         if sampler is not None:
@@ -503,7 +538,7 @@ class StableDiffusion:
         self._reset_state()
         self._compile_args = dict(unconditional_context=unconditional_context, context=context, latent=latent, warmup=warmup, timesteps=timesteps,
                                   sampler=sampler, inpaint=inpaint, concat=concat, control=control, cfg=cfg, ip_adapter=ip_adapter, freeu=freeu, pag=pag,
-                                  prediction=prediction, cfg_rescale=cfg_rescale)
+                                  prediction=prediction, cfg_rescale=cfg_rescale, motion=motion, frames=frames)
         self._stream = stream or Stream()
         self._latent, self._unc, self._ctx = latent, unconditional_context, context
         self._sched, self._inpaint, self._concat, self._control = sampler, bool(inpaint), concat, bool(control)
@@ -514,6 +549,8 @@ class StableDiffusion:
         self._vpred, self._rescale = prediction == "v", bool(cfg_rescale)
         self._adm = bool(self.model.diffusion_model.cfg.adm_in_channels)
         self._ip_model_compiled = self._ip_model if self._ip else None
+        self._motion, self._frames = bool(motion), int(frames) if motion else None
+        self._motion_compiled = self._motion_model if self._motion else None
         if sampler is not None:
             with use_stream(self._stream):
                 self._alloc_sampler_buffers()
@@ -559,12 +596,15 @@ class StableDiffusion:
     def _hoist(self, sp, timesteps):
         """The private stacked context and -- config.hoist_step_invariants -- what depends on it or on the timestep alone: the K|V projections and
         the buffer ``_emb_cur`` the captured step reads its time-embedding row from, with the rows of ``timesteps`` computed up front."""
-        self._ctx2 = self._stack_context(self._unc, self._ctx, self._groups, self._cond_groups())
+        self._ctx2 = self._frame_context(self._stack_context(self._unc, self._ctx, self._groups, self._cond_groups()))
         if self._adm:
             self._refresh_y_emb()
+        if self._motion:                     # the positional tables pe W^T and the live last launches: built once, outside the captured step
+            self._motion_compiled.set_scale(1.0)
+            self._motion_compiled.prepare(self._frames)
         if not config.hoist_step_invariants or config.cfg_parallel:
             return
-        self._kv_all, self._kv_key = self.model.diffusion_model.context_kv(self._ctx2), self._weights_key()
+        self._kv_all, self._kv_key = self._context_kv(), self._weights_key()
         if self._control:
             self._ckv_all = self.control_model.context_kv(self._ctx2)
         row = self._time_row(sp.set(981.0))
@@ -576,6 +616,31 @@ class StableDiffusion:
             return                           # the schedule's rows depend on y: start() builds them all in one pass (_build_adm_table)
         for t in (timesteps if timesteps is not None else ()):
             self._emb_row(float(t))
+
+    def _per_frame(self, a):
+        """(R, ...) rows, one per (group, video) -> (R F, ...): every row F times, adjacent -- the (group, video, frame) order of the stacked latent."""
+        f, per = self._frames, a.nbytes // a.shape[0]
+        out = DeviceArray.empty((a.shape[0] * f,) + a.shape[1:], a.dtype, a.layout)
+        for r in range(a.shape[0]):
+            for k in range(f):
+                hip.tf_memcpy_async(out.ptr + (r * f + k) * per, a.ptr + r * per, per, 3, _sh())
+        out._base = a                        # (referenced until the copies have run)
+        return out
+
+    def _frame_context(self, stacked):
+        """The stacked context the UNet reads, one row per image.  motion=True with one prompt per video: the per-video stack is kept (``_ctx_vid``:
+        what the hoisted K|V is projected from) and its rows are replicated to the video's frames."""
+        self._ctx_vid = None
+        if not self._motion or stacked.shape[0] == self._groups * self._latent.shape[0]:
+            return stacked
+        self._ctx_vid = stacked
+        return self._per_frame(stacked)
+
+    def _context_kv(self):
+        """The UNet's hoisted K|V projection of the stacked context; one prompt per video: projected once per video, the rows replicated to its frames."""
+        if self._ctx_vid is None:
+            return self.model.diffusion_model.context_kv(self._ctx2)
+        return self._per_frame(self.model.diffusion_model.context_kv(self._ctx_vid))
 
     def _warm_up(self, sp, warmup):
         """``warmup`` eager steps at t = 981 on a latent that is put back afterwards: they warm the pool and build the lazily packed weights."""
@@ -628,6 +693,8 @@ class StableDiffusion:
         ip = (self._ip_model_compiled, self._ip_kv, self._ip_scales) if self._ip else None
         b = self._latent.shape[0]
         pag = (self._pag_flags, ((self._groups - 2) * b, (self._groups - 1) * b)) if self._pag else None      # the group in front of the conditional one
+        if self._motion:                     # (refused together with control / ip / freeu / pag: the plain call with the modules in)
+            return unet(x2, sp, ctx, shared=None if row is None else (None, row, self._kv_all), motion=(self._motion_compiled, self._frames))
         if not self._control:
             return unet(x2, sp, ctx, shared=None if row is None else (None, row, self._kv_all), ip=ip, freeu=self._freeu_scales, pag=pag,
                         y_emb=self._y_emb if row is None else None)     # (step() has put this timestep's row -- SDXL: one per image -- into _emb_cur)
@@ -738,7 +805,7 @@ class StableDiffusion:
     def start(self, seed=None, noise=None, image_offset=0, init_image=None, init_latent=None, mask=None, cond_image=None, cond_mask=None,
               cond_latent=None, image_guidance=None, control_image=None, control_hint=None, control_scale=None, ip_image_embeds=None, ip_image=None,
               ip_scale=None, freeu=None, pag=None, cfg_rescale=None, pooled=None, uncond_pooled=None, original_size=None, crop_top_left=None,
-              target_size=None, uncond_size_ids=None):
+              target_size=None, uncond_size_ids=None, motion_scale=None):
         """A new image batch for the compiled sampler: sets the latent in place and rewinds the schedule.  ``seed``: the initial latent is
         drawn on the device (tag 0; image b is global image image_offset + b), and the ancestral noise of every step comes from the same seed
         (tag 1); ``noise``: a host (B,C,H,W) array for the initial latent instead (the ancestral noise then uses ``seed``, default 0).
@@ -784,8 +851,12 @@ class StableDiffusion:
         (0, 0) and the latent's size x 8.  ``uncond_size_ids``: the unconditional group's six ids (B | 1, 6) [original h, w, crop top, left, target
         h, w]; the conditional ones when not given.  y = [pooled | Fourier(ids)] (tf_adm_vector_16), label_emb(y) and the time-embedding rows of
         the whole schedule -- one per step and image -- are computed here: the replay's parameter launch copies G B rows where it copied one.
-        On any other model these arguments raise."""
+        On any other model these arguments raise.
+
+        A video model (compile(..., motion=True)): the latent is V F frames in (video, frame) order -- ``init_latent`` likewise; ``motion_scale`` (one
+        float, or one per motion module in execution order) writes what ``set_motion_scale`` writes; without it the scale keeps its value."""
         self._require_sampler("start")
+        ms = self._check_motion_scale(motion_scale, "start")
         adm = self._check_adm(pooled, uncond_pooled, original_size, crop_top_left, target_size, uncond_size_ids)
         phi = self._check_cfg_rescale(cfg_rescale, "start")
         pg = self._check_pag(pag, "start")
@@ -809,7 +880,33 @@ class StableDiffusion:
             self._write_cfg_rescale(phi)
         if adm is not None:
             self._write_adm(*adm)
+        if ms is not None:
+            self._write_motion_scale(ms)
         return self._latent
+
+    def _check_motion_scale(self, value, who):
+        """The motion scale checked against the compiled model before anything changes: None when not given, else one float per module."""
+        if value is None:
+            return None
+        if not self._motion:
+            raise ValueError(f"StableDiffusion.{who}: " + ("motion_scale= needs" if who == "start" else "needs") + " a model compiled with motion=True")
+        return self._motion_compiled.scales(value)
+
+    def _write_motion_scale(self, scales):
+        """Rewrite every module's live last-launch weight and bias, round16(s base), on the sampler stream behind every step already queued: one
+        elementwise launch per tensor, outside the graph, which reads the live copies (the bfloat16 step forms the products on the host: drained first)."""
+        if config.is_bf16():
+            self.synchronize()
+        with use_stream(self._stream, ordered=False):
+            self._motion_compiled.set_scale(scales)
+
+    def set_motion_scale(self, scale=1.0):
+        """The strength of the motion modules' residual branch, out = x_in + s proj_out(x), from the next step on: one finite float, or one per module
+        in execution order (input blocks, middle block, output blocks), checked before anything is written.  The captured step reads private live
+        copies of each module's last weight and bias, which this rewrites from the kept fp32 base: nothing is captured again.  0 switches the modules'
+        contribution off (the step is then the image step up to the path the GroupNorm statistics take); 1 after compile."""
+        self._require_sampler("set_motion_scale")
+        self._write_motion_scale(self._check_motion_scale(scale, "set_motion_scale"))
 
     def _check_adm(self, pooled, uncond_pooled, original_size, crop_top_left, target_size, uncond_size_ids):
         """start()'s vector-conditioning arguments, checked against the compiled model before anything changes: None for a model without label_emb,
@@ -1283,7 +1380,7 @@ class StableDiffusion:
     def _refresh_kv(self):
         """Recompute the hoisted K|V projections of the stacked context into the buffers the captured step reads; returns what must stay referenced
         until the copies have run."""
-        kv = self.model.diffusion_model.context_kv(self._ctx2)
+        kv = self._context_kv()
         hip.tf_memcpy_async(self._kv_all.ptr, kv.ptr, kv.nbytes, 3, _sh())
         ckv = None
         if self._ckv_all is not None:
@@ -1297,7 +1394,7 @@ class StableDiffusion:
         ``context`` alone: ``unconditional_context`` may be None."""
         self._require_compiled("set_context")
         with use_stream(self._stream):
-            new = self._stack_context(unconditional_context, context, self._groups, self._cond_groups())       # (in the step's 16-bit type)
+            new = self._frame_context(self._stack_context(unconditional_context, context, self._groups, self._cond_groups()))       # (in the step's 16-bit type)
             assert new.nbytes == self._ctx2.nbytes, "set_context: the contexts must have the shape the step was compiled for"
             hip.tf_memcpy_async(self._ctx2.ptr, new.ptr, new.nbytes, 3, _sh())
             self._ctx_tmp = new                                    # (referenced until the copy has run)

@@ -16,7 +16,8 @@ The encoder half (block plan, batched projections, the walk over input_blocks an
 ControlNet (vision/controlnet.py) is a second copy of it, and ``UNetModel.__call__(control=...)`` takes its residuals in (``control_add``).
 ``UNetModel.__call__(freeu=...)`` is FreeU in front of the concats of the first two decoder stages (``freeu_stages``, ``freeu_skips``,
 ``freeu_backbone``).  ``UNetModel.__call__(pag=...)`` is perturbed-attention guidance: one batch range of every selected SpatialTransformer's
-self-attention takes the identity (``pag_layers``; attention/sdpa.py::sdpa_pag_strided).
+self-attention takes the identity (``pag_layers``; attention/sdpa.py::sdpa_pag_strided).  ``UNetModel.__call__(motion=(adapter, F))`` runs AnimateDiff
+motion modules (vision/motion.py) at their slots of the walk (``_with_motion``).
 """
 import ctypes
 from dataclasses import dataclass, replace
@@ -31,6 +32,7 @@ from ..native import ControlEntry, FreeuEntry, hip
 from .. import config
 from ..storage.tensor import Branch, DeviceArray, Tensor, _sh, asarray, bfloat16, dtag, is_bfloat16
 from .conv2d import Conv2d
+from .motion import MotionModule
 from .resnet import ResBlock
 
 
@@ -296,8 +298,9 @@ class StepModel:
             kv_all = self.context_kv(context)                                         # every attn2's K|V of the context
         return emb, emb_all, kv_all, br
 
-    def _runner(self, emb, emb_all, kv_all, context, ip=None, pag=None):
+    def _runner(self, emb, emb_all, kv_all, context, ip=None, pag=None, frames=None):
         bt = self._prepare()
+        # frames: F of ``UNetModel.__call__(motion=(adapter, F))`` -- what a MotionModule of the walked sequence is called with
         # pag = (flags, (b0, b1)): the device fp32 array with one word per SpatialTransformer in execution order, and the perturbed batch range
         pag_idx = {id(st): i for i, st in enumerate(self._all(SpatialTransformer))} if pag is not None else None
         # ip = (kv_ip_all (b, T, kv_n), {id(SpatialTransformer): (column offset, scale index)}, kv_n, scales): an IP-Adapter's image-token K|V
@@ -307,10 +310,10 @@ class StepModel:
             # nxt = the module that reads this one's output as a single tensor (None across a concat): when it opens
             # with a GroupNorm, the statistics are produced by this module's last conv.  force_gn: the output (also) enters
             # an equal-split concat whose GroupNorm merges the two producers' partials (tf_group_norm_apply2_f16)
-            gn = nxt.num_groups if isinstance(nxt, GroupNorm) else 32 if isinstance(nxt, (ResBlock, SpatialTransformer)) else force_gn
+            gn = nxt.num_groups if isinstance(nxt, GroupNorm) else 32 if isinstance(nxt, (ResBlock, SpatialTransformer, MotionModule)) else force_gn
             # ... and where that conv runs split-K its reduce applies the norm too: (the GroupNorm module that opens nxt, silu)
             on = (nxt, True) if isinstance(nxt, GroupNorm) else (nxt.in_layers[0], True) if isinstance(nxt, ResBlock) \
-                else (nxt.norm, False) if isinstance(nxt, SpatialTransformer) else None
+                else (nxt.norm, False) if isinstance(nxt, (SpatialTransformer, MotionModule)) else None      # (a motion module opens with GroupNorm(32, eps 1e-6), no SiLU)
             if isinstance(bb, ResBlock):
                 off, n = bt["emb_off"][id(bb)]
                 if emb_all.shape[0] == 1:                      # one row for every image (time_embedding_all's rule)
@@ -328,6 +331,8 @@ class StepModel:
                 bpag = (pag[0].ptr + 4 * pag_idx[id(bb)], pag[1]) if pag is not None else None
                 kvs = [KVSlice(kv_all, bt["kv_off"][id(blk)], c, bt["kv_n"]) for blk in bb.transformer_blocks]      # each block its own K|V columns
                 return bb(x, context, kv=kvs, out_gn=gn, out_norm=on, ip=bip, pag=bpag)
+            if isinstance(bb, MotionModule):
+                return bb(x, frames, out_gn=gn, out_norm=on)
             if isinstance(bb, (Downsample, Upsample)):
                 return bb(x, out_gn=gn, out_norm=on)
             if isinstance(bb, Conv2d):
@@ -337,17 +342,19 @@ class StepModel:
             return bb(x)
         return run
 
-    def _encode(self, run, x, br=None, concat_stats=True, residual=None, replaced=0):
+    def _encode(self, run, x, br=None, concat_stats=True, residual=None, replaced=0, blocks=None):
         """input_blocks and middle_block over x: (the middle block's output, what every input block saves for the skip concats).  concat_stats:
         the saved tensors and the output enter the output path's concats as they are -- their producers emit the statistics those concats'
         GroupNorms merge (config.concat_stats).  residual: added to the first module's (conv_in's) output.  replaced: the last ``replaced`` saved
-        tensors and the output are replaced before their concats read them (FreeU): their producers are not asked for concat statistics."""
+        tensors and the output are replaced before their concats read them (FreeU): their producers are not asked for concat statistics.  blocks:
+        (input blocks, middle block) to walk in place of the model's own (``UNetModel._with_motion``: the same lists with the motion modules in)."""
+        input_blocks, middle_block = (self.input_blocks, self.middle_block) if blocks is None else blocks
         saved_inputs = []
         joined = br is None
-        seq = [bb for b in self.input_blocks for bb in b] + list(self.middle_block)
+        seq = [bb for b in input_blocks for bb in b] + list(middle_block)
         ends = []                                   # indices after which the tensor is also saved for a skip concat
         i = 0
-        for b in self.input_blocks:
+        for b in input_blocks:
             i += len(b)
             ends.append(i - 1)
         kept = set(ends[:len(ends) - replaced]) if replaced else set(ends)
@@ -493,7 +500,26 @@ class UNetModel(StepModel):
             raise ValueError("UNetModel.ip_slots: the adapter was built for another UNet")
         return {id(st): (offs[k], k) for k, (_, _, st) in enumerate(paths)}
 
-    def __call__(self, x, timesteps=None, context=None, shared=None, control=None, ip=None, freeu=None, pag=None, y_emb=None):
+    def _with_motion(self, adapter):
+        """(input_blocks, middle_block, output_blocks) with the adapter's modules at their slots -- new lists, the model's own stay as they are: behind
+        everything else of an input block, between the middle block's transformer and its second ResBlock, behind the ResBlock / SpatialTransformer
+        of an output block and in front of its Upsample."""
+        if adapter.cfg != self.cfg:
+            raise ValueError(f"UNetModel: the motion adapter was built for {adapter.cfg}, this UNet is {self.cfg}")
+        mods = adapter.modules
+        inp = [list(b) + ([mods[f"input_blocks.{i}"]] if f"input_blocks.{i}" in mods else []) for i, b in enumerate(self.input_blocks)]
+        mid = list(self.middle_block)
+        if "middle_block" in mods:
+            mid.insert(len(mid) - 1, mods["middle_block"])
+        out = []
+        for i, b in enumerate(self.output_blocks):
+            b, m = list(b), mods.get(f"output_blocks.{i}")
+            if m is not None:
+                b.insert(len(b) - 1 if isinstance(b[-1], Upsample) else len(b), m)
+            out.append(b)
+        return inp, mid, out
+
+    def __call__(self, x, timesteps=None, context=None, shared=None, control=None, ip=None, freeu=None, pag=None, y_emb=None, motion=None):
         """y_emb: ``label_embedding(y)``, (batch, E), on a model with label_emb (SDXL) where ``shared`` does not hand the rows in.
         control = (residuals, scales): a ControlNet's len(input_blocks) + 1 residual tensors (or a callable that returns them, called behind
         the middle block) and the device fp32 array of their strengths.  Behind the middle block one launch (control_add) makes new skip tensors
@@ -509,8 +535,18 @@ class UNetModel(StepModel):
         pag = (flags, (b0, b1)): perturbed-attention guidance -- flags a device fp32 array of PAG_WORDS words, one per SpatialTransformer in
         ``pag_layers`` order; the rows [b0, b1) of x are the perturbed guidance group: in every SpatialTransformer whose word is not zero their
         self-attention is the identity, attn1(x) = to_out(to_v(norm1(x))), inside the one attention launch (tf_sdpa_pag_16 in place of tf_sdpa_16).
-        The words are read when the kernels run.  None: the plain launches."""
+        The words are read when the kernels run.  None: the plain launches.
+        motion = (adapter, F): AnimateDiff motion modules (vision/motion.py::MotionAdapter) -- the batch is groups x videos x F images in (group, video,
+        frame) order, and every module of the adapter runs at its slot (``_with_motion``) on batch / F videos of F frames.  A module's output is its
+        block's output: the skip concats save it, and the block in front emits the statistics of the module's GroupNorm(32, eps 1e-6).  None: the
+        sequence as it always was, launch for launch."""
         emb, emb_all, kv_all, br = self._shared(timesteps, context, shared, y_emb)
+        frames, input_blocks, middle_block, output_blocks = None, self.input_blocks, self.middle_block, self.output_blocks
+        if motion is not None:
+            madapter, frames = motion[0], int(motion[1])
+            if frames < 1 or x.shape[0] % frames or frames > madapter.max_len:
+                raise ValueError(f"UNetModel: motion: a batch of {x.shape[0]} images does not hold videos of {frames} frames (1 .. {madapter.max_len}, frames of a video adjacent)")
+            input_blocks, middle_block, output_blocks = self._with_motion(madapter)
         fu = freeu_stages(self.cfg) if freeu is not None else []
         if ip is not None:
             adapter, kv_ip, scales = ip
@@ -523,21 +559,21 @@ class UNetModel(StepModel):
             if flags.dtype != np.float32 or flags.size < n_st or n_st > PAG_WORDS or not 0 <= b0 <= b1 <= x.shape[0]:
                 raise ValueError(f"UNetModel: pag flags {flags} / batch range [{b0}, {b1}) do not fit {n_st} SpatialTransformers (at most {PAG_WORDS}) and a batch of {x.shape[0]}")
             pag = (flags, (int(b0), int(b1)))
-        run = self._runner(emb, emb_all, kv_all, context, ip, pag)
-        x, saved_inputs = self._encode(run, x, br, concat_stats=control is None, replaced=len(fu))
+        run = self._runner(emb, emb_all, kv_all, context, ip, pag, frames)
+        x, saved_inputs = self._encode(run, x, br, concat_stats=control is None, replaced=len(fu), blocks=(input_blocks, middle_block))
         if control is not None:
             residuals, scales = control
             *saved_inputs, x = control_add(saved_inputs + [x], residuals() if callable(residuals) else residuals, scales)
         if fu:
             saved_inputs[-len(fu):] = freeu_skips(saved_inputs[-len(fu):], [st for st, *_ in reversed(fu)], freeu)     # (popped from the end: block order reversed)
-        for bi, b in enumerate(self.output_blocks):
+        for bi, b in enumerate(output_blocks):
             if bi < len(fu):
                 x = freeu_backbone(x, fu[bi][0], freeu)
             x = (x, saved_inputs.pop())            # channel concat (unet.py:72), consumed un-materialised
             for j, bb in enumerate(b):
-                last = bi == len(self.output_blocks) - 1 and j == len(b) - 1
+                last = bi == len(output_blocks) - 1 and j == len(b) - 1
                 nxt = b[j + 1] if j + 1 < len(b) else (self.out[0] if last else None)
-                cout = bb.conv.weight.shape[0] if isinstance(bb, Upsample) else (bb.out_layers[3].weight.shape[0] if isinstance(bb, ResBlock) else bb.proj_out.weight.shape[0])
+                cout = bb.conv.weight.shape[0] if isinstance(bb, Upsample) else (bb.out_layers[3].weight.shape[0] if isinstance(bb, ResBlock) else bb.proj_out.weight.shape[0])      # (SpatialTransformer and MotionModule: proj_out)
                 # the output enters the next concat: emit its statistics in sub-groups as wide as the 32 groups of the saved partner
                 # (32 sub-groups for an equal split, 64 for the 2:1 splits), so that the concat's GroupNorm is apply-only
                 fg = 0

@@ -4,6 +4,7 @@ tf_cfg_sampler_step_f32) against the DDIM step (tf_cfg_ddim_step_f32), 100 graph
 config-3 end-to-end img/s (CLIP x2 -> steps -> VAE decode, batch 1) at 20 DPM++2M steps against 50 DDIM steps.
 
     python tools/sampler_bench.py [--replays 100] [--rounds 5] [--images 3] [--dpm-steps 20] [--inpaint] [--concat inpaint|edit] [--control] [--lora] [--lcm] [--ip-adapter] [--freeu] [--pag]
+    python tools/sampler_bench.py --motion [--replays 80]      # a run of its own: the AnimateDiff video step against the image step at batch 16
 --inpaint adds the masked DPM++2M step (tf_cfg_sampler_step_masked_f32, a model compiled with inpaint=True on the same shape, half the
 latent repainted) to the alternation, and the VAE encoder's time for a 512^2 image (StableDiffusion.encode_image).
 --concat adds the DPM++2M step of a concat-conditioned UNet (SD15_INPAINT: 9 input channels, two CFG groups; SD15_EDIT: 8 input channels, three
@@ -594,6 +595,109 @@ def sdxl_bench(args):
     print(json.dumps(out))
 
 
+def motion_bench(args):
+    """--motion: the AnimateDiff video step (synthetic weights) -- SD-1.5, one 16-frame video on a 64 x 64 latent, CFG pair, --dpm-steps DPM++2M steps --
+    against the plain image step at batch 16, alternating in the same rounds: medians of --rounds rounds of --replays replays with the spread between
+    the rounds, the library entries of both steps, the GEMM shapes that had no row in the tuning table.  The share of the step spent in
+    tf_sdpa_temporal_16 comes from a kernel trace in a run of its own: ``--motion-trace`` replays the video step alone (under rocprofv3 --kernel-trace
+    --stats), ``--kernel-stats CSV`` reads that run's kernel_stats.csv into the result.  Writes profiles/sampler_bench_motion.json."""
+    import csv
+    import tinyfusers_amd.storage.tensor as T
+    from tinyfusers_amd.native import hip
+    from tinyfusers_amd.storage.state import param_shapes, update_state
+    from tinyfusers_amd.storage.synth import synth_motion_state_dict, synth_normal, synth_state_dict
+    from tinyfusers_amd.variants.samplers import DPMSolverPP2M, linear_alphas_cumprod
+    from tinyfusers_amd.variants.sd import StableDiffusion
+    from tinyfusers_amd.vision.motion import MotionAdapter
+    from tinyfusers_amd.vision.unet import SD15
+
+    T.ensure_init(0)
+
+    def table_keys():
+        n, key, cfg_ = ctypes.c_int(0), (ctypes.c_int * 10)(), (ctypes.c_int * 5)()
+        hip.tf_gemm_tune_count(ctypes.byref(n))
+        keys = set()
+        for i in range(n.value):
+            hip.tf_gemm_tune_entry(i, key, cfg_)
+            keys.add(tuple(key))
+        return keys
+    shipped = table_keys()
+    frames, side = 16, args.motion_side
+    sched = DPMSolverPP2M().schedule(args.dpm_steps, alphas_cumprod=linear_alphas_cumprod())
+    ctx = T.DeviceArray.from_numpy(synth_normal(1234, "sd.context", (1, 77, 768)))
+    unc = T.DeviceArray.from_numpy(synth_normal(1234, "sd.uncond", (1, 77, 768)))
+    rep = lambda a: T.DeviceArray.from_numpy(np.repeat(a.numpy(), frames, axis=0))
+    arms = {}
+    for name in ("video",) if args.motion_trace else ("video", "image"):
+        m = StableDiffusion(SD15)
+        with contextlib.redirect_stdout(io.StringIO()):
+            update_state(m.model.diffusion_model, synth_state_dict(param_shapes(m.model.diffusion_model), 0), "")
+        lat = m.latent_from_numpy(np.zeros((frames, 4, side, side), np.float32))
+        if name == "video":
+            m.attach_motion(MotionAdapter.load(SD15, synth_motion_state_dict(SD15, 1, max_len=24)))
+            m.compile(unc, ctx, lat, sampler=sched, motion=True, frames=frames)          # one prompt for the video
+        else:
+            m.compile(rep(unc), rep(ctx), lat, sampler=sched)                            # the same 16 latents as 16 images
+        m.start(seed=1234); m.synchronize()
+        arms[name] = (m, lat, T.DeviceArray.from_numpy(lat.numpy(), np.float32, "row"))
+    ev0, ev1, ms = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_float()
+    hip.tf_event_create(ctypes.byref(ev0)); hip.tf_event_create(ctypes.byref(ev1))
+
+    def replays(name, n):
+        m, lat, lat0 = arms[name]
+        m.synchronize()
+        hip.tf_event_record(ev0, m._stream.handle)
+        for s_ in range(n):
+            i = s_ % len(sched.timesteps)
+            if i == 0:
+                hip.tf_memcpy_async(lat.ptr, lat0.ptr, lat.nbytes, 3, m._stream.handle)
+            m.step_sampler(i, 7.5)
+        hip.tf_event_record(ev1, m._stream.handle)
+        m.synchronize()
+        hip.tf_event_elapsed_ms(ctypes.byref(ms), ev0, ev1)
+        return ms.value / n
+    if args.motion_trace:
+        replays("video", 2 * len(sched.timesteps))
+        assert np.isfinite(arms["video"][1].numpy()).all()
+        return print(json.dumps({"traced_replays": 2 * len(sched.timesteps)}))
+    per = {k: [] for k in arms}
+    for k in arms:
+        replays(k, len(sched.timesteps))
+    for _ in range(args.rounds):
+        for k in arms:
+            per[k].append(replays(k, args.replays))
+    for k in arms:
+        assert np.isfinite(arms[k][1].numpy()).all()
+    out = {"protocol": f"median of {args.rounds} rounds of {args.replays} replays, alternating video / image in the same run, (median ms, max - min over the rounds); "
+                       f"SD-1.5, {side} x {side} latent, one {frames}-frame video (one prompt) against {frames} images, CFG pair, {args.dpm_steps}-step DPM++2M on the "
+                       "linear-beta table, synthetic weights"}
+    med = {k: float(np.median(v)) for k, v in per.items()}
+    out["video_step_ms"] = (round(med["video"], 4), round(max(per["video"]) - min(per["video"]), 4))
+    out["image_step_ms"] = (round(med["image"], 4), round(max(per["image"]) - min(per["image"]), 4))
+    out["video_over_image"] = round(med["video"] / med["image"], 4)
+    for k in arms:
+        ent = step_entries(T, arms[k][0])
+        out[f"{k}_step_entries"] = sum(ent.values())
+        out[f"{k}_step_entries_by_name"] = dict(sorted(ent.items()))
+    out["motion_modules"] = len(arms["video"][0]._motion_compiled.modules)
+    share = "not measured"
+    if args.kernel_stats:
+        rows = list(csv.DictReader(open(args.kernel_stats)))
+        total = sum(float(r["TotalDurationNs"]) for r in rows)
+        temporal = sum(float(r["TotalDurationNs"]) for r in rows if "sdpa_temporal" in r["Name"])
+        share = {"share_of_kernel_time": round(temporal / total, 4), "calls": sum(int(r["Calls"]) for r in rows if "sdpa_temporal" in r["Name"]),
+                 "source": "rocprofv3 --kernel-trace --stats over --motion-trace's replays of the video step alone"}
+    out["sdpa_temporal_16_share"] = share
+    out["gemm_shapes_autotuned_MNK"] = sorted({tuple(k[:3]) for k in table_keys() - shipped})
+    hip.tf_event_destroy(ev0); hip.tf_event_destroy(ev1)
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sampler_bench_motion.json")
+    if not args.motion_no_write:
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--replays", type=int, default=100)
@@ -612,7 +716,14 @@ def main():
     ap.add_argument("--sdxl", action="store_true", help="a run of its own: the SDXL base step, start() with the time-embedding rows in one pass against one pass per timestep, both text towers; writes profiles/sampler_bench_sdxl.json")
     ap.add_argument("--sdxl-side", type=int, default=128, help="with --sdxl: the latent's side (default 128: a 1024 x 1024 image)")
     ap.add_argument("--sdxl-no-write", action="store_true", help="with --sdxl: print the result only")
+    ap.add_argument("--motion", action="store_true", help="a run of its own: the AnimateDiff video step (one 16-frame video) against the image step at batch 16; writes profiles/sampler_bench_motion.json")
+    ap.add_argument("--motion-side", type=int, default=64, help="with --motion: the latent's side (default 64: 512 x 512 frames)")
+    ap.add_argument("--motion-trace", action="store_true", help="with --motion: replay the video step alone and write nothing (the run to put under rocprofv3 --kernel-trace --stats)")
+    ap.add_argument("--kernel-stats", default="", help="with --motion: the kernel_stats.csv of the --motion-trace run, for the share of tf_sdpa_temporal_16")
+    ap.add_argument("--motion-no-write", action="store_true", help="with --motion: print the result only")
     args = ap.parse_args()
+    if args.motion:
+        return motion_bench(args)
     if args.sd2:
         return sd2_bench(args)
     if args.sdxl:
