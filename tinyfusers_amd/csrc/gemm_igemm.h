@@ -1,7 +1,7 @@
 // Part of the implicit-GEMM family of csrc/gemm.hip (see its head comment); split into translation units so that the
 // instances compile in parallel.
 #pragma once
-#include "gemm_common.h"
+#include "gemm_ring.h"
 
 // GENERIC = false: every channel count is a multiple of 64, so a 64-wide K tile lies inside one filter tap and one
 // concat source and (tap, channel) advance as wave-uniform scalars; GENERIC = true recomputes them per lane.
@@ -35,55 +35,12 @@ __global__ void __launch_bounds__(512, WIDE ? 4 : 2) k_igemm(const GemmP p) {
   static_assert((NS - 2) * LPS <= 63 || WIDE, "vmcnt immediate is 6 bits");
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const bool loader = wid >= 4;
-  const int w4 = wid & 3;
-  const int ntiles = p.ntm * p.ntn;
-  const int nblk = ntiles * p.splitk;
-  const int bid = xcd_order(blockIdx.x, nblk);
-  const int split = bid / ntiles;
-  const TileMN tmn = tile_decode(bid - split * ntiles, p.order, p.ntm, p.ntn);
-  const int m0 = tmn.m * BM, n0 = tmn.n * BN;
-  const int kt_begin = split * p.ktiles_per_split;
-  const int kt_end = min(p.ktiles, kt_begin + p.ktiles_per_split);
-#if TF_IGEMM_STAMP
-  // diagnostic build: wave 0 (a consumer) and wave 4 (a loader) of every block keep four stamps of the constant 100 MHz clock each and store them when
-  // they leave: [0] entry [1] K loop done (behind barrier X) [2] epilogue stores issued [3] stores drained | [4] entry [5] K tile 0 landed
-  // [6] last stage issued [7] left.  The fences idle nothing the shipped kernel overlaps across these points (they sit at barriers).
-  unsigned long long stp0 = __builtin_amdgcn_s_memrealtime(), stp1 = 0, stp2 = 0, stp3 = 0;
-  auto stamp_out = [&](int base) {
-    if (p.stamp && lane == 0 && blockIdx.x < 8192) { unsigned long long* d = p.stamp + (size_t)blockIdx.x * 8 + base; d[0] = stp0; d[1] = stp1; d[2] = stp2; d[3] = stp3; }
-  };
-#define IG_STAMP(v) do { __builtin_amdgcn_sched_barrier(0); v = __builtin_amdgcn_s_memrealtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
-  // TF_IGEMM_STAMP == 2: per-K-tile stamps (s_memtime, core clock) of block 0's wave 4 (loader: 0 top, 1 tile it + 1 landed, 2 behind barrier(it), 3 next stage
-  // issued) and wave 0 (consumer: 4 fragments of tile it in registers, 5 behind barrier(it)) for K tiles 4 .. 4 + 255, kept in the LDS above the ring
-  // (the launch gets all 160 KiB) and copied out when the waves leave.  Only where lgkmcnt is 0 anyway, so no overlap of the shipped loop is fenced off.
-  const bool lp_on = TF_IGEMM_STAMP == 2 && blockIdx.x == 0 && lane == 0 && (wid == 0 || wid == 4) && p.stamp && !WIDE && BM != 256;
-  const unsigned lp_base = lds_off(smem) + 163840u - 256u * 32u;
-  auto lp = [&](int it, int k) {
-    if (TF_IGEMM_STAMP != 2) return;
-    if (!lp_on || it < 4 || it >= 260) return;
-    unsigned long long t_;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory");
-    asm volatile("ds_write_b32 %0, %1" :: "v"(lp_base + (unsigned)((it - 4) * 8 + k) * 4u), "v"((unsigned)t_) : "memory");
-  };
-  auto lp_out = [&]() {
-    if (TF_IGEMM_STAMP != 2 || !lp_on) return;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    for (int i = 0; i < 256 * 8; ++i) {
-      if (((i & 7) < 4) != (wid == 4)) continue;           // each wave copies its own columns
-      unsigned v_;
-      asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v_) : "v"(lp_base + (unsigned)i * 4u) : "memory");
-      reinterpret_cast<unsigned*>(p.stamp + 8192 * 8)[i] = v_;
-    }
-  };
-#else
-#define IG_STAMP(v) do { } while (0)
-#endif
+  const RingBlock b = ring_block<BM, BN>(p);
+  const int lane = b.lane, w4 = b.w4, m0 = b.m0, n0 = b.n0, split = b.split, kt_begin = b.kt_begin, nt = b.nt;
+  RingStamps stamps;                                       // diagnostics of the tagged builds (gemm_stamp.h); empty in the shipped library
+  stamps.init(p, smem, lane, b.wid, !WIDE && BM != 256);
 
-  if (loader) {
+  if (b.loader) {
     // =============================== LOADER WAVES ===============================================
     const rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
     const rsrc_t rs_x2 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x2 ? p.x2 : p.x), 0, p.x2_bytes, 0x00020000);
@@ -94,7 +51,7 @@ __global__ void __launch_bounds__(512, WIDE ? 4 : 2) k_igemm(const GemmP p) {
     // XOR swizzle on the SOURCE chunk (LDS image stays lane-linear): chunk ^ ((row >> 1) & 7); g = w4 (mod 4), so the
     // swizzle term (4 (g & 1) + (sub >> 1)) & 7 is a per-thread constant.
     const int sub = lane >> 3;
-    const int cs = (lane & 7) ^ ((4 * (w4 & 1) + (sub >> 1)) & 7);
+    const int cs = ring_src_chunk128(lane, w4);
     int g_a[LPS], g_b[LPS], g_c[LPS];                     // A row: (hi0, wi0, pixel base); W row: (-, -, byte offset)
 #pragma unroll
     for (int i = 0; i < LPS; ++i) {
@@ -111,7 +68,7 @@ __global__ void __launch_bounds__(512, WIDE ? 4 : 2) k_igemm(const GemmP p) {
         }
       } else {
         int n = n0 + row - BM;
-        if (n < p.N) g_c[i] = (int)((unsigned)(n * p.K + cs * 8) * 2u);
+        if (n < p.N) g_c[i] = (int)ring_weight_off<2>(p, n, cs);
       }
     }
     const int Hl = p.H << p.ups, Wl = p.W << p.ups;        // logical (post-upsample) input extent
@@ -233,7 +190,6 @@ __global__ void __launch_bounds__(512, WIDE ? 4 : 2) k_igemm(const GemmP p) {
         }
       }
     };
-    const int nt = kt_end - kt_begin;
     if (WIDE) {
       // 2-slot ring: barrier(it) hands tile it to the consumers and slot (it-1) % 2 back; tile it+1 is in flight
       // while tile it is multiplied.
@@ -241,12 +197,9 @@ __global__ void __launch_bounds__(512, WIDE ? 4 : 2) k_igemm(const GemmP p) {
       if (gi_on) { __builtin_amdgcn_s_barrier(); __builtin_amdgcn_s_barrier(); }   // barriers A, B of gi_prologue (consumer waves)
       for (int it = 0; it < nt; ++it) {
         wait_vm<0>();
-#if TF_IGEMM_STAMP
-        if (it == 0) IG_STAMP(stp1);
-#endif
+        if (it == 0) stamps.mark(1);
         if (gi_on) gi_tile(it & 1, kt_begin + it);
-        __builtin_amdgcn_s_barrier();                     // barrier(it)
-        asm volatile("" ::: "memory");
+        ring_barrier();                                   // barrier(it)
         if (it + 1 < nt) stage((it + 1) & 1, kt_begin + it + 1);
         if (ln_on) ln_tile(it & 1);                       // off the barrier's critical path; slot refilled after barrier(it+1)
       }
@@ -254,43 +207,26 @@ __global__ void __launch_bounds__(512, WIDE ? 4 : 2) k_igemm(const GemmP p) {
       // Ring protocol (NS slots, tile t lives in slot t % NS).  Barrier P hands tile 0 to the consumers; barrier(it)
       // guarantees tile it+1 has landed (the consumers prefetch its fragments while multiplying tile it) and hands
       // slot it % NS back (the consumers drained their reads of tile it before arriving).  NS-1 tiles stay in flight.
-      // (TF_IGEMM_PRE stages are issued in front of barrier P -- gemm_common.h; with 2, tried in round 5, the stamps showed the consumers no longer waiting 0.6-1.2 us for nothing but the
-      // ISSUE of ring slots 2 .. NS-1, at 60-100 cycles per 1-KiB piece; the rest of the ring follows right behind the barrier)
-      constexpr int PRE = NS < TF_IGEMM_PRE ? NS : TF_IGEMM_PRE;
+      // The whole ring is issued in front of barrier P (issuing only two stages there was measured slower in the step: DESIGN 4.1).
 #pragma unroll
-      for (int s_ = 0; s_ < PRE; ++s_)
+      for (int s_ = 0; s_ < NS; ++s_)
         if (s_ < nt) stage(s_, kt_begin + s_);
       if (gi_on) { __builtin_amdgcn_s_barrier(); __builtin_amdgcn_s_barrier(); }   // barriers A, B of gi_prologue (consumer waves)
-      wait_stages<LPS, PRE - 1>(nt - 1);                   // tile 0 landed; up to PRE-1 newer stages in flight
-#if TF_IGEMM_STAMP
-      IG_STAMP(stp1);
-#endif
+      wait_stages<LPS, NS - 1>(nt - 1);                    // tile 0 landed; up to NS-1 newer stages in flight
+      stamps.mark(1);
       if (gi_on && nt > 0) gi_tile(0, kt_begin);
-      __builtin_amdgcn_s_barrier();                       // barrier P
-      asm volatile("" ::: "memory");
-#pragma unroll
-      for (int s_ = PRE; s_ < NS; ++s_)
-        if (s_ < nt) stage(s_, kt_begin + s_);
-      if (ln_on && nt > 0) ln_tile(0);                    // slot 0 is refilled only after barrier(0)
+      ring_barrier();                                     // barrier P
+      if (ln_on && nt > 0) ln_tile(0);                   // slot 0 is refilled only after barrier(0)
       asm volatile("" ::: "memory");
       for (int it = 0; it < nt; ++it) {
-#if TF_IGEMM_STAMP == 2
-        lp(it, 0);
-#endif
+        stamps.loop(it, 0);
         if (it + 1 < nt) wait_stages<LPS, NS - 2>(nt - 2 - it);   // tile it+1 landed (ring holds up to tile it+NS-1 here)
-#if TF_IGEMM_STAMP == 2
-        lp(it, 1);
-#endif
+        stamps.loop(it, 1);
         if (gi_on && it + 1 < nt) gi_tile((it + 1) % NS, kt_begin + it + 1);
-        __builtin_amdgcn_s_barrier();                     // barrier(it)
-        asm volatile("" ::: "memory");
-#if TF_IGEMM_STAMP == 2
-        lp(it, 2);
-#endif
+        ring_barrier();                                   // barrier(it)
+        stamps.loop(it, 2);
         if (it + NS < nt) stage(it % NS, kt_begin + it + NS);
-#if TF_IGEMM_STAMP == 2
-        lp(it, 3);
-#endif
+        stamps.loop(it, 3);
         if (ln_on && it + 1 < nt) ln_tile((it + 1) % NS);  // tile it+1 stays in its slot until barrier(it+1)
       }
     }
@@ -310,11 +246,8 @@ __global__ void __launch_bounds__(512, WIDE ? 4 : 2) k_igemm(const GemmP p) {
         lstat[i] = (f2){mean, rsqrtf(var + p.ln_eps)};
       }
     }
-#if TF_IGEMM_STAMP
-    IG_STAMP(stp2);
-#endif
-    __builtin_amdgcn_s_barrier();                         // barrier X: matches the consumers' "ring is free" barrier
-    asm volatile("" ::: "memory");
+    stamps.mark(2);
+    ring_barrier();                                       // barrier X: matches the consumers' "ring is free" barrier
     if (TF_ABL(p.dbg & 1)) return;
     if (ln_on) {
       constexpr int TMl = BM / 2, TNl = BN / 2;
@@ -325,19 +258,14 @@ __global__ void __launch_bounds__(512, WIDE ? 4 : 2) k_igemm(const GemmP p) {
         if (g * 8 < BM && (lane & 7) == 0) stats[8 * g + sub] = lstat[i];
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();                       // barrier Z
-      asm volatile("" ::: "memory");
+      ring_barrier();                                     // barrier Z
     }
-    __builtin_amdgcn_s_barrier();                         // barrier Y: the consumers' tiles are in the LDS scratch
-    asm volatile("" ::: "memory");
+    ring_barrier();                                       // barrier Y: the consumers' tiles are in the LDS scratch
     igemm_epilogue<BM, BN, false, BF, 4, false, EPRE, true>(p, smem, m0, n0, split, w4, 1, lane, nullptr, 0, 0, epre);
     if (p.gn_part) igemm_gn_stats<BM, BN>(p, smem, m0, n0, w4, 1, lane);
-#if TF_IGEMM_STAMP
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    IG_STAMP(stp3);
-    if (wid == 4) stamp_out(4);
-    lp_out();
-#endif
+    stamps.drain();
+    stamps.mark(3);
+    stamps.leave(4);
     return;
   }
 
@@ -375,19 +303,13 @@ __global__ void __launch_bounds__(512, WIDE ? 4 : 2) k_igemm(const GemmP p) {
     int row = wave_m * TM + j * 16 + lr;
     xa[j] = row * 128 + ((lg ^ ((row >> 1) & 7)) << 4);
   }
-  const int nt = kt_end - kt_begin;
   // ALL8: this wave's share of the weight rows (groups NG - 4 LPC + w4 + 4 i), same lane -> (row, swizzled chunk) map as the loaders
   unsigned cw[LPC > 0 ? LPC : 1];
   rsrc_t rs_cw;
   if constexpr (ALL8) {
     rs_cw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
-    const int sub = lane >> 3;
-    const int cs = (lane & 7) ^ ((4 * (w4 & 1) + (sub >> 1)) & 7);
 #pragma unroll
-    for (int i = 0; i < LPC; ++i) {
-      int n = n0 + 8 * (NG - 4 * LPC + w4 + 4 * i) + sub - BM;
-      cw[i] = n < p.N ? (unsigned)(n * p.K + cs * 8) * 2u : TF_OOB;
-    }
+    for (int i = 0; i < LPC; ++i) cw[i] = ring_weight_row<2>(p, n0 + 8 * (NG - 4 * LPC + w4 + 4 * i) + (lane >> 3) - BM, ring_src_chunk128(lane, w4));
   }
   auto cstage = [&](int buf, int kt) {                    // the consumer's pieces of stage (buf, kt)
     if constexpr (ALL8) {
@@ -416,8 +338,7 @@ __global__ void __launch_bounds__(512, WIDE ? 4 : 2) k_igemm(const GemmP p) {
 #pragma unroll
         for (int j = 0; j < MJ; ++j) acc[i][j] = mfma16<BF>(wf[i], xf[j], acc[i][j]);
     };
-    __builtin_amdgcn_s_barrier();                         // barrier P: tile 0 landed
-    asm volatile("" ::: "memory");
+    ring_barrier();                                       // barrier P: tile 0 landed
     if (nt > 0) read_k(0, 0, wfA, xfA);
     for (int it = 0; it < nt; ++it) {
       read_k(it % NS, 1, wfB, xfB);                       // (it, k-step 1) in flight under the MFMAs of (it, k-step 0)
@@ -425,8 +346,7 @@ __global__ void __launch_bounds__(512, WIDE ? 4 : 2) k_igemm(const GemmP p) {
       mma1(wfA, xfA);
       __builtin_amdgcn_sched_barrier(0);
       wait_lds_reads();  // every fragment of tile it is in registers: its slot may be refilled
-      __builtin_amdgcn_s_barrier();                       // barrier(it): tile it+1 landed
-      asm volatile("" ::: "memory");
+      ring_barrier();                                     // barrier(it): tile it+1 landed
       if (it + 1 < nt) read_k((it + 1) % NS, 0, wfA, xfA);
       __builtin_amdgcn_sched_barrier(0);
       mma1(wfB, xfB);
@@ -434,8 +354,7 @@ __global__ void __launch_bounds__(512, WIDE ? 4 : 2) k_igemm(const GemmP p) {
     }
   } else if (WIDE) {
     for (int it = 0; it < nt; ++it) {
-      __builtin_amdgcn_s_barrier();                       // barrier(it): tile it landed
-      asm volatile("" ::: "memory");
+      ring_barrier();                                     // barrier(it): tile it landed
       const char* sb = smem + (it & 1) * STAGE;
 #pragma unroll
       for (int k2 = 0; k2 < 2; ++k2) {
@@ -491,32 +410,20 @@ __global__ void __launch_bounds__(512, WIDE ? 4 : 2) k_igemm(const GemmP p) {
 #pragma unroll
         for (int j = 0; j < MJ; ++j) acc[i][j] = mfma16<BF>(wf[k2][i], xf[k2][j], acc[i][j]);
   };
-  constexpr int PRE = NS < TF_IGEMM_PRE ? NS : TF_IGEMM_PRE;   // (as the loaders: two stages in front of barrier P, the rest of the ring behind it)
-  if constexpr (ALL8) {
+  if constexpr (ALL8) {                                   // (as the loaders: the whole ring in front of barrier P)
 #pragma unroll
-    for (int s_ = 0; s_ < PRE; ++s_)
+    for (int s_ = 0; s_ < NS; ++s_)
       if (s_ < nt) cstage(s_, kt_begin + s_);
-    wait_stages<LPC, PRE - 1>(nt - 1);                     // this wave's pieces of tile 0 landed
+    wait_stages<LPC, NS - 1>(nt - 1);                      // this wave's pieces of tile 0 landed
   }
-  __builtin_amdgcn_s_barrier();                           // barrier P: tile 0 landed
-  asm volatile("" ::: "memory");
-  if constexpr (ALL8) {
-#pragma unroll
-    for (int s_ = PRE; s_ < NS; ++s_)
-      if (s_ < nt) cstage(s_, kt_begin + s_);
-  }
+  ring_barrier();                                         // barrier P: tile 0 landed
   if (nt > 0) read_frags(0, wfA, xfA);
   for (int it = 0; it < nt; it += 2) {
     wait_lds_reads();    // fragments of tile it are in registers: its slot may be refilled
-#if TF_IGEMM_STAMP == 2
-    lp(it, 4);
-#endif
+    stamps.loop(it, 4);
     if constexpr (ALL8) { if (it + 1 < nt) wait_stages<LPC, NS - 2>(nt - 2 - it); }   // ... and this wave's pieces of tile it+1 landed
-    __builtin_amdgcn_s_barrier();                         // barrier(it): tile it+1 landed
-    asm volatile("" ::: "memory");
-#if TF_IGEMM_STAMP == 2
-    lp(it, 5);
-#endif
+    ring_barrier();                                       // barrier(it): tile it+1 landed
+    stamps.loop(it, 5);
     if constexpr (ALL8) { if (it + NS < nt) cstage(it % NS, kt_begin + it + NS); }
     if (it + 1 < nt) read_frags((it + 1) % NS, wfB, xfB);
     __builtin_amdgcn_sched_barrier(0);
@@ -524,15 +431,10 @@ __global__ void __launch_bounds__(512, WIDE ? 4 : 2) k_igemm(const GemmP p) {
     __builtin_amdgcn_sched_barrier(0);
     if (it + 1 >= nt) break;
     wait_lds_reads();
-#if TF_IGEMM_STAMP == 2
-    lp(it + 1, 4);
-#endif
+    stamps.loop(it + 1, 4);
     if constexpr (ALL8) { if (it + 2 < nt) wait_stages<LPC, NS - 2>(nt - 3 - it); }
-    __builtin_amdgcn_s_barrier();                         // barrier(it+1)
-    asm volatile("" ::: "memory");
-#if TF_IGEMM_STAMP == 2
-    lp(it + 1, 5);
-#endif
+    ring_barrier();                                       // barrier(it+1)
+    stamps.loop(it + 1, 5);
     if constexpr (ALL8) { if (it + 1 + NS < nt) cstage((it + 1) % NS, kt_begin + it + 1 + NS); }
     if (it + 2 < nt) read_frags((it + 2) % NS, wfA, xfA);
     __builtin_amdgcn_sched_barrier(0);
@@ -542,11 +444,8 @@ __global__ void __launch_bounds__(512, WIDE ? 4 : 2) k_igemm(const GemmP p) {
   }
   EpiPre<BM, BN> epre;
   if constexpr (EPRE) igemm_epilogue_prefetch<BM, BN>(p, m0, n0, w4, 0, lane, epre);       // the K loop is over (its fragments are dead): the epilogue's loads fly under barriers X / Y and the scratch write
-  __builtin_amdgcn_s_barrier();                           // barrier X: every consumer is done with the ring
-  asm volatile("" ::: "memory");
-#if TF_IGEMM_STAMP
-  IG_STAMP(stp1);
-#endif
+  ring_barrier();                                         // barrier X: every consumer is done with the ring
+  stamps.mark(1);
   if (TF_ABL(p.dbg & 1)) {
 #pragma unroll
     for (int i = 0; i < NI; ++i)
@@ -556,21 +455,15 @@ __global__ void __launch_bounds__(512, WIDE ? 4 : 2) k_igemm(const GemmP p) {
   }
   if constexpr (CSUM_LATE) load_csum();
   if (p.ln_colsum) {
-    __builtin_amdgcn_s_barrier();                         // barrier Z: the loaders' (mean, rstd) table is in LDS
-    asm volatile("" ::: "memory");
+    ring_barrier();                                       // barrier Z: the loaders' (mean, rstd) table is in LDS
   }
   igemm_scratch_write<BM, BN>(p, acc, csum, smem, w4, lane);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();                           // barrier Y
-  asm volatile("" ::: "memory");
+  ring_barrier();                                         // barrier Y
   igemm_epilogue<BM, BN, false, BF, 4, false, EPRE, true>(p, smem, m0, n0, split, w4, 0, lane, nullptr, 0, 0, epre);
   if (p.gn_part) igemm_gn_stats<BM, BN>(p, smem, m0, n0, w4, 0, lane);
-#if TF_IGEMM_STAMP
-  IG_STAMP(stp2);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  IG_STAMP(stp3);
-  if (wid == 0) stamp_out(0);
-  lp_out();
-#endif
+  stamps.mark(2);
+  stamps.drain();
+  stamps.mark(3);
+  stamps.leave(0);
 }
-#undef IG_STAMP

@@ -1,7 +1,7 @@
 // Part of the implicit-GEMM family of csrc/gemm.hip (see its head comment); split into translation units so that the
 // instances compile in parallel.
 #pragma once
-#include "gemm_common.h"
+#include "gemm_ring.h"
 
 // =====================================================================================================================
 // fp8 (OCP e4m3) variant, BASELINE config 5: same 4 loader + 4 consumer waves, LDS-DMA ring, raw barriers and epilogue as the deep
@@ -33,22 +33,10 @@ __global__ void __launch_bounds__(512, 2) k_igemm8(const GemmP p) {
   const unsigned char* X2 = reinterpret_cast<const unsigned char*>(p.x2);
   const unsigned char* Wt = reinterpret_cast<const unsigned char*>(p.w);
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const bool loader = wid >= 4;
-  const int w4 = wid & 3;
-  const int ntiles = p.ntm * p.ntn;
-  const int nblk = ntiles * p.splitk;
-  const int bid = xcd_order(blockIdx.x, nblk);
-  const int split = bid / ntiles;
-  const TileMN tmn = tile_decode(bid - split * ntiles, p.order, p.ntm, p.ntn);
-  const int m0 = tmn.m * BM, n0 = tmn.n * BN;
-  const int kt_begin = split * p.ktiles_per_split;
-  const int kt_end = min(p.ktiles, kt_begin + p.ktiles_per_split);
-  const int nt = kt_end - kt_begin;
+  const RingBlock b = ring_block<BM, BN>(p);
+  const int lane = b.lane, w4 = b.w4, m0 = b.m0, n0 = b.n0, split = b.split, kt_begin = b.kt_begin, nt = b.nt;
 
-  if (loader) {
+  if (b.loader) {
     const rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)Wt, 0, p.w_bytes, 0x00020000);
     // lane -> row 2 (lane >> 3) + ((lane >> 2) & 1) of its 16-row piece, LDS chunk lane & 3; source chunk = LDS chunk ^ swizzle(row),
     // swizzle(row) = -(row >> 2) & 3 = -(lane >> 4) & 3 for every piece (pieces start at multiples of 16 rows)
@@ -70,7 +58,7 @@ __global__ void __launch_bounds__(512, 2) k_igemm8(const GemmP p) {
         }
       } else {
         int n = n0 + row - BM;
-        if (n < p.N) g_c[i] = (int)((unsigned)n * (unsigned)p.K + (unsigned)kc * 16u);
+        if (n < p.N) g_c[i] = (int)ring_weight_off<1>(p, n, kc);
       }
     }
     const int Hl = p.H << p.ups, Wl = p.W << p.ups;
@@ -110,18 +98,14 @@ __global__ void __launch_bounds__(512, 2) k_igemm8(const GemmP p) {
     for (int s_ = 0; s_ < NS; ++s_)
       if (s_ < nt) stage(s_, kt_begin + s_);
     wait_stages<LPS, NS - 1>(nt - 1);
-    __builtin_amdgcn_s_barrier();                         // barrier P
-    asm volatile("" ::: "memory");
+    ring_barrier();                                        // barrier P
     for (int it = 0; it < nt; ++it) {
       if (it + 1 < nt) wait_stages<LPS, NS - 2>(nt - 2 - it);
-      __builtin_amdgcn_s_barrier();                       // barrier(it)
-      asm volatile("" ::: "memory");
+      ring_barrier();                                      // barrier(it)
       if (it + NS < nt) stage(it % NS, kt_begin + it + NS);
     }
-    __builtin_amdgcn_s_barrier();                         // barrier X
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();                         // barrier Y
-    asm volatile("" ::: "memory");
+    ring_barrier();                                        // barrier X
+    ring_barrier();                                        // barrier Y
     if (p.out8) igemm_epilogue<BM, BN, true>(p, smem, m0, n0, split, w4, 1, lane);
     else igemm_epilogue<BM, BN, false>(p, smem, m0, n0, split, w4, 1, lane);
     if (p.gn_part) igemm_gn_stats<BM, BN>(p, smem, m0, n0, w4, 1, lane);
@@ -174,28 +158,24 @@ __global__ void __launch_bounds__(512, 2) k_igemm8(const GemmP p) {
         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(wf[i][1], xf[j][1], acc[i][j], 0, 0, 0);
       }
   };
-  __builtin_amdgcn_s_barrier();                           // barrier P: tile 0 landed
-  asm volatile("" ::: "memory");
+  ring_barrier();                                          // barrier P: tile 0 landed
   if (nt > 0) read_frags(0, wfA, xfA);
   for (int it = 0; it < nt; it += 2) {
     wait_lds_reads();
-    __builtin_amdgcn_s_barrier();                         // barrier(it): tile it+1 landed
-    asm volatile("" ::: "memory");
+    ring_barrier();                                        // barrier(it): tile it+1 landed
     if (it + 1 < nt) read_frags((it + 1) % NS, wfB, xfB);
     __builtin_amdgcn_sched_barrier(0);
     mma(wfA, xfA);
     __builtin_amdgcn_sched_barrier(0);
     if (it + 1 >= nt) break;
     wait_lds_reads();
-    __builtin_amdgcn_s_barrier();                         // barrier(it+1)
-    asm volatile("" ::: "memory");
+    ring_barrier();                                        // barrier(it+1)
     if (it + 2 < nt) read_frags((it + 2) % NS, wfA, xfA);
     __builtin_amdgcn_sched_barrier(0);
     mma(wfB, xfB);
     __builtin_amdgcn_sched_barrier(0);
   }
-  __builtin_amdgcn_s_barrier();                           // barrier X: every consumer is done with the ring
-  asm volatile("" ::: "memory");
+  ring_barrier();                                          // barrier X: every consumer is done with the ring
 #pragma unroll
   for (int i = 0; i < NI; ++i)
 #pragma unroll
@@ -205,8 +185,7 @@ __global__ void __launch_bounds__(512, 2) k_igemm8(const GemmP p) {
   for (int i = 0; i < NI; ++i) csum[i] = (f4){0.f, 0.f, 0.f, 0.f};
   igemm_scratch_write<BM, BN>(p, acc, csum, smem, w4, lane);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();                           // barrier Y
-  asm volatile("" ::: "memory");
+  ring_barrier();                                          // barrier Y
   if (p.out8) igemm_epilogue<BM, BN, true>(p, smem, m0, n0, split, w4, 0, lane);
   else igemm_epilogue<BM, BN, false>(p, smem, m0, n0, split, w4, 0, lane);
   if (p.gn_part) igemm_gn_stats<BM, BN>(p, smem, m0, n0, w4, 0, lane);

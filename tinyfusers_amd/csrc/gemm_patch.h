@@ -1,7 +1,7 @@
 // Part of the implicit-GEMM family of csrc/gemm.hip (see its head comment); split into translation units so that the
 // instances compile in parallel.
 #pragma once
-#include "gemm_common.h"
+#include "gemm_ring.h"
 
 // =====================================================================================================================
 // PATCH variant for 3x3 / stride 1 / pad 1 convolutions (no up-sampling, channel counts multiples of 64) whose m-tile is a
@@ -23,22 +23,11 @@ __global__ void __launch_bounds__(512, 2) k_igemm_patch(const GemmP p) {
   constexpr int TM = BM / 2, TN = BN / 2, MJ = TM / 16, NI = TN / 16;
   constexpr int BNP = BN / 32;                            // weight pieces per loader wave per K tile
   constexpr int AXP = BM / 32;                            // activation pieces per loader wave of an extra (1x1) K tile
+  constexpr bool EPRE = TF_IGEMM_EPRE;                    // epilogue loads requested when the K loop ends (igemm_epilogue_prefetch), as k_igemm
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const bool loader = wid >= 4;
-  const int w4 = wid & 3;
-  const int ntiles = p.ntm * p.ntn;
-  const int nblk = ntiles * p.splitk;
-  const int bid = xcd_order(blockIdx.x, nblk);
-  const int split = bid / ntiles;
-  const TileMN tmn = tile_decode(bid - split * ntiles, p.order, p.ntm, p.ntn);
-  const int m0 = tmn.m * BM, n0 = tmn.n * BN;
-  const int kt_begin = split * p.ktiles_per_split;
-  const int kt_end = min(p.ktiles, kt_begin + p.ktiles_per_split);
-  const int nt = kt_end - kt_begin;
+  const RingBlock b = ring_block<BM, BN>(p);
+  const int lane = b.lane, w4 = b.w4, m0 = b.m0, n0 = b.n0, split = b.split, kt_begin = b.kt_begin, kt_end = b.kt_end, nt = b.nt;
 
   const int PC = p.W + 2;                                 // patch row pitch (pixels)
   const int PPC = p.pt_ppc;                               // 1-KiB pieces (8 pixels x 64 channels) of one patch
@@ -47,18 +36,15 @@ __global__ void __launch_bounds__(512, 2) k_igemm_patch(const GemmP p) {
   const int STG = p.pt_stage, NS = p.pt_ns;
   const int G1 = p.C >> 6, T1 = 9 * G1;
 
-  if (loader) {
+  if (b.loader) {
     // =============================== LOADER WAVES ===============================================
     const rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
     const int sub = lane >> 3;
-    const int cs = (lane & 7) ^ ((4 * (w4 & 1) + (sub >> 1)) & 7);      // source chunk of this lane (gemm_common.h's head comment)
+    const int cs = ring_src_chunk128(lane, w4);            // source chunk of this lane
     unsigned gw[BNP];
     int ga[AXP], pp[TF_PATCH_PPW];
 #pragma unroll
-    for (int i = 0; i < BNP; ++i) {
-      int n = n0 + 8 * (w4 + 4 * i) + sub;
-      gw[i] = n < p.N ? (unsigned)(n * p.K + cs * 8) * 2u : TF_OOB;
-    }
+    for (int i = 0; i < BNP; ++i) gw[i] = ring_weight_row<2>(p, n0 + 8 * (w4 + 4 * i) + sub, cs);
 #pragma unroll
     for (int i = 0; i < AXP; ++i) ga[i] = m0 + 8 * (w4 + 4 * i) + sub;   // the 1x1 segment reads the output pixel itself
     {
@@ -174,18 +160,15 @@ __global__ void __launch_bounds__(512, 2) k_igemm_patch(const GemmP p) {
     auto advance = [&]() { if (ng >= G1) ++ng; else if (++ntap == 9) { ntap = 0; ++ng; } };
     advance();                                             // tile 1
     {
-      // TF_IGEMM_PRE stages in front of barrier P, the rest of the ring right behind it (gemm_common.h: 99 = the whole ring, shipped; 2 was measured slower in the step)
-      int s_ = 0;
-      for (; s_ < TF_IGEMM_PRE && s_ < NS && s_ < nt; ++s_) { int n = stage(s_); if (s_ > 0) W += n; }
+      // the whole ring in front of barrier P (two stages there and the rest behind it was measured slower in the step: DESIGN 4.1)
+      for (int s_ = 0; s_ < NS && s_ < nt; ++s_) { int n = stage(s_); if (s_ > 0) W += n; }
       if (gi_on) { __builtin_amdgcn_s_barrier(); __builtin_amdgcn_s_barrier(); }   // barriers A, B of gi_prologue (consumer waves)
       wait_vm_dyn(W);                                      // tile 0 (and everything issued before it) landed
       if (gi_on && pro_g >= 0) {
         gi_range(pro_g, 0, TF_PATCH_PPW);
         if (pro_next > 0) gi_range(pro_g + 1, 0, pro_next);
       }
-      __builtin_amdgcn_s_barrier();                       // barrier P
-      asm volatile("" ::: "memory");
-      for (; s_ < NS && s_ < nt; ++s_) W += stage(s_);
+      ring_barrier();                                      // barrier P
     }
     int slot = 0;
     for (int it = 0; it < nt; ++it) {
@@ -198,18 +181,15 @@ __global__ void __launch_bounds__(512, 2) k_igemm_patch(const GemmP p) {
         // read that patch from tile 9 (group + 1) on, behind barrier(9 group + 8) at the earliest)
         if (gi_on && lg_ < G1 && carries(lg_, lt_)) gi_range(lg_ + 1, (lt_ - TAP0) * PQ, (lt_ - TAP0 + 1) * PQ);
       }
-      __builtin_amdgcn_s_barrier();                       // barrier(it)
-      asm volatile("" ::: "memory");
+      ring_barrier();                                      // barrier(it)
       if (it + NS < nt) W += stage(slot);
       if (++slot == NS) slot = 0;
     }
     EpiPre<BM, BN> epre;
-    igemm_epilogue_prefetch<BM, BN>(p, m0, n0, w4, 1, lane, epre);     // the epilogue's first loads, requested now (no counted vmcnt wait follows in this wave)
-    __builtin_amdgcn_s_barrier();                         // barrier X
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();                         // barrier Y: the consumers' tiles are in the LDS scratch
-    asm volatile("" ::: "memory");
-    igemm_epilogue<BM, BN, 0, BF, 4, false, true, true>(p, smem, m0, n0, split, w4, 1, lane, nullptr, 0, 0, epre);
+    if constexpr (EPRE) igemm_epilogue_prefetch<BM, BN>(p, m0, n0, w4, 1, lane, epre);     // the epilogue's first loads, requested now (no counted vmcnt wait follows in this wave)
+    ring_barrier();                                        // barrier X
+    ring_barrier();                                        // barrier Y: the consumers' tiles are in the LDS scratch
+    igemm_epilogue<BM, BN, 0, BF, 4, false, EPRE, true>(p, smem, m0, n0, split, w4, 1, lane, nullptr, 0, 0, epre);
     if (p.gn_part) igemm_gn_stats<BM, BN>(p, smem, m0, n0, w4, 1, lane);
     return;
   }
@@ -278,35 +258,30 @@ __global__ void __launch_bounds__(512, 2) k_igemm_patch(const GemmP p) {
 #pragma unroll
         for (int j = 0; j < MJ; ++j) acc[i][j] = mfma16<BF>(wf[k2][i], xf[k2][j], acc[i][j]);
   };
-  __builtin_amdgcn_s_barrier();                           // barrier P: tile 0 (and its patch) landed
-  asm volatile("" ::: "memory");
+  ring_barrier();                                          // barrier P: tile 0 (and its patch) landed
   int rslot = 0;
   if (nt > 0) { read_frags(0, wfA, xfA); rslot = 1; }
   for (int it = 0; it < nt; it += 2) {
     wait_lds_reads();
-    __builtin_amdgcn_s_barrier();                         // barrier(it): tile it+1 landed
-    asm volatile("" ::: "memory");
+    ring_barrier();                                        // barrier(it): tile it+1 landed
     if (it + 1 < nt) { read_frags(rslot, wfB, xfB); if (++rslot == NS) rslot = 0; }
     __builtin_amdgcn_sched_barrier(0);
     mma(wfA, xfA);
     __builtin_amdgcn_sched_barrier(0);
     if (it + 1 >= nt) break;
     wait_lds_reads();
-    __builtin_amdgcn_s_barrier();                         // barrier(it+1)
-    asm volatile("" ::: "memory");
+    ring_barrier();                                        // barrier(it+1)
     if (it + 2 < nt) { read_frags(rslot, wfA, xfA); if (++rslot == NS) rslot = 0; }
     __builtin_amdgcn_sched_barrier(0);
     mma(wfB, xfB);
     __builtin_amdgcn_sched_barrier(0);
   }
   EpiPre<BM, BN> epre;
-  igemm_epilogue_prefetch<BM, BN>(p, m0, n0, w4, 0, lane, epre);       // the K loop is over: the epilogue's loads fly under barriers X / Y and the scratch write
-  __builtin_amdgcn_s_barrier();                           // barrier X: every consumer is done with the ring and the patches
-  asm volatile("" ::: "memory");
+  if constexpr (EPRE) igemm_epilogue_prefetch<BM, BN>(p, m0, n0, w4, 0, lane, epre);       // the K loop is over: the epilogue's loads fly under barriers X / Y and the scratch write
+  ring_barrier();                                          // barrier X: every consumer is done with the ring and the patches
   igemm_scratch_write<BM, BN>(p, acc, csum, smem, w4, lane);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();                           // barrier Y
-  asm volatile("" ::: "memory");
-  igemm_epilogue<BM, BN, 0, BF, 4, false, true, true>(p, smem, m0, n0, split, w4, 0, lane, nullptr, 0, 0, epre);
+  ring_barrier();                                          // barrier Y
+  igemm_epilogue<BM, BN, 0, BF, 4, false, EPRE, true>(p, smem, m0, n0, split, w4, 0, lane, nullptr, 0, 0, epre);
   if (p.gn_part) igemm_gn_stats<BM, BN>(p, smem, m0, n0, w4, 0, lane);
 }
